@@ -121,7 +121,7 @@ def test_full_line_schema_and_size():
     import bench
 
     env = dict(os.environ, DFX_BENCH_STUB="full")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--full"],
                        capture_output=True, text=True, env=env, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stdout + r.stderr
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -162,6 +162,55 @@ def test_full_line_schema_and_size():
         assert isinstance(out[top], dict)
     assert {"bound", "achieved", "peak", "unit", "frac", "traffic"} <= set(out["roofline"])
     assert {"value", "unit", "cores", "kind", "sample"} <= set(out["cpu_baseline"])
+
+
+def test_plain_line_runs_no_side_legs():
+    """Without --full the N = 1 line is the headline alone: the stub engine that --full walks through every leg
+    (DFX_BENCH_STUB=full) runs no PCIe-inclusive leg, no parity check, no other workload and no CPU comparator."""
+    env = dict(os.environ, DFX_BENCH_STUB="full")
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1"],
+                       capture_output=True, text=True, env=env, timeout=120, cwd=ROOT)
+    assert r.returncode == 0, r.stdout + r.stderr
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    out = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in out, k
+    assert out["steps"] == 3 and out["warmup"] == 1 and out["unit"] == "frame-pairs/s" and out["dtype"] == "f32"
+    assert abs(out["value"] - 3 * out["config"]["pairs_per_step"] / (out["ms_per_step"] * 3e-3)) < 1e-6 * out["value"]
+    assert "cpu_baseline" not in out and "parity_check" not in out
+    assert "pcie_inclusive" not in out["config"] and "other_workloads" not in out["config"]
+
+
+def test_dump_outputs_whole_and_sampled(tmp_path):
+    """--dump-outputs: the step's flows whole when they fit, else the first and last flow and a seeded pixel sample at
+    recorded positions — float only, under 64 MB, the same sample in every run."""
+    import numpy as np
+    import torch
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    small = torch.arange(3 * 4 * 5 * 2, dtype=torch.float32).reshape(3, 4, 5, 2)
+    shapes = bench.dump_outputs(torch.cat([small, small[:1]]), 3, str(tmp_path / "a"))  # rows past `pairs` are not output
+    assert shapes == {"flows": (3, 4, 5, 2)}
+    assert np.array_equal(np.load(tmp_path / "a" / "flows.npy"), small.numpy())
+
+    n, H, W = 6, 1080, 1920  # 6 flows of 1080p: 99.5 MB, over the budget
+    big = torch.randn((n, H, W, 2), generator=torch.Generator().manual_seed(1), dtype=torch.float32)
+    for d in ("b", "c"):
+        bench.dump_outputs(big, n, str(tmp_path / d))
+    files = sorted(os.listdir(tmp_path / "b"))
+    assert files == ["flow_first.npy", "flow_last.npy", "flows_sample.npy", "flows_sample_at.npy"]
+    assert sum(os.path.getsize(tmp_path / "b" / f) for f in files) <= 64_000_000
+    arr = {f: np.load(tmp_path / "b" / f) for f in files}
+    assert all(a.dtype in (np.float32, np.float64) for a in arr.values())
+    assert np.array_equal(arr["flow_first.npy"], big[0].numpy()) and np.array_equal(arr["flow_last.npy"], big[-1].numpy())
+    at = arr["flows_sample_at.npy"].astype(np.int64)
+    assert at[:, 0].max() < n and at[:, 1].max() < H and at[:, 2].max() < W and len(np.unique(at[:, 0])) == n
+    assert np.array_equal(arr["flows_sample.npy"], big.numpy()[at[:, 0], at[:, 1], at[:, 2]])
+    for f in files:
+        assert np.array_equal(arr[f], np.load(tmp_path / "c" / f)), f
 
 
 def _world8(cmd_prefix, env_drop):

@@ -1,8 +1,8 @@
 """CPU checks of the flow-bounding oracle (oracle/quant_oracle.c = reference src/common.cpp:4-16).
 
 Pinned: the golden file was produced by the reference's own source lines (tests/golden/
-make_quant_golden.py), and when oracle/_ref/libref_quant.so is present the oracle is compared with it
-directly on fresh inputs as well.
+make_quant_golden.py), and so were the outputs for the fresh inputs (tests/golden/make_ref_fresh_golden.py); when
+oracle/_ref/libref_quant.so is present the oracle is compared with it directly on those inputs as well.
 """
 import os
 
@@ -11,6 +11,7 @@ import pytest
 
 from tests import numpy_restatement as NR
 from tests.golden.make_quant_golden import CASES, adversarial_flow
+from tests.golden.make_ref_fresh_golden import GOLDEN as REF_FRESH, png_fresh_flows, quant_fresh_flows
 
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden", "quant_golden.npz")
 
@@ -62,12 +63,14 @@ def test_golden_inputs_are_reproducible():
 
 
 def test_oracle_equals_compiled_reference_on_fresh_inputs(oracle):
-    if not oracle.ref_quant_available():
-        pytest.skip("oracle/_ref/libref_quant.so not built (needs /root/reference: make -C oracle ref)")
-    for seed, (lo, hi) in enumerate([(-20, 20), (-32, 32), (-1, 1), (-5, 20), (0, 0), (3, -3)]):
-        flow = adversarial_flow(max(abs(hi), 1), 80, 50, 100 + seed)
+    """Against the reference's lines: their stored outputs always, the live oracle/_ref library too where it is built."""
+    g = np.load(REF_FRESH)
+    for i, (lo, hi, flow) in enumerate(quant_fresh_flows()):
         ox, oy = oracle.flow_to_u8(flow, lo, hi)
-        rx, ry = oracle.ref_flow_to_u8(flow, lo, hi)
+        rx, ry = g[f"quant_{i}_x"], g[f"quant_{i}_y"]
+        if oracle.ref_quant_available():
+            lx, ly = oracle.ref_flow_to_u8(flow, lo, hi)
+            assert np.array_equal(lx, rx) and np.array_equal(ly, ry), (lo, hi)
         assert np.array_equal(ox, rx) and np.array_equal(oy, ry), (lo, hi)
         nx, ny = NR.flow_to_u8(flow, lo, hi)
         assert np.array_equal(nx, rx) and np.array_equal(ny, ry), (lo, hi)
@@ -114,14 +117,13 @@ def test_png_scheme_golden_inputs_are_reproducible():
 
 
 def test_png_scheme_oracle_equals_compiled_reference_on_fresh_inputs(oracle):
-    if not oracle.ref_png_available():
-        pytest.skip("oracle/_ref/libref_png.so not built (needs /root/reference: make -C oracle ref)")
-    rng = np.random.default_rng(3)
-    for k in range(12):
-        w, h = int(rng.integers(1, 90)), int(rng.integers(1, 70))
-        flow = flow_with_extrema(w, h, float(rng.choice([0.0, 0.3, 7.9, 15.5, 31.7, 300.0])),
-                                 float(rng.choice([0.0, 1.0, 3.9, 23.6, 64.0])), 200 + k, bool(k & 1))
-        assert np.array_equal(oracle.flow_to_png_planes(flow)[3], oracle.ref_flow_to_png_image(flow)), (w, h, k)
+    """Against the reference's lines: their stored outputs always, the live oracle/_ref library too where it is built."""
+    g = np.load(REF_FRESH)
+    for w, h, k, flow in png_fresh_flows():
+        want = g[f"png_{k}_bgr"]
+        if oracle.ref_png_available():
+            assert np.array_equal(oracle.ref_flow_to_png_image(flow), want), (w, h, k)
+        assert np.array_equal(oracle.flow_to_png_planes(flow)[3], want), (w, h, k)
 
 
 def _nan_flows(w=33, h=21):
