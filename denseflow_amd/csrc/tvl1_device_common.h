@@ -23,7 +23,9 @@ __device__ __forceinline__ float *pair_plane(const Tvl1LevelCtx &c, int pair, in
 // warp-and-head kernel's 15 719) in kernels that are bound by vector-ALU issue.  A buffer instruction takes the slot's base from
 // a 128-bit descriptor in scalar registers, the plane's byte offset from ONE scalar register (soffset) and the pixel's byte
 // offset inside the plane from ONE 32-bit vector register: no vector instruction per access.  Offsets are bytes in 32 bits: the
-// engine refuses frame sizes whose pair slot reaches 4 GB (16 planes: beyond 8192 x 8192).  The descriptor's size field bounds
+// engine refuses frame sizes whose pair slot reaches 4 GiB (round_up(w, 64) x h x 64 B >= 2^32: 8192 x 8192 is refused, 8192 x
+// 8191 accepted), and below that the scalar offsets of the upper planes may have bit 31 set - the hardware reads all three
+// offsets as unsigned (tests/test_device_math_gpu.py probes this at 8192 x 8191).  The descriptor's size field bounds
 // vector + scalar offset (measured on gfx950, scripts/round6/probe_buffer.py: the scalar offset IS part of the range check), so it is
 // set to the slot's size: every plane of the slot is in range, anything beyond it reads 0 / is not written.
 // Only dword accesses: this compiler's __builtin_amdgcn_raw_buffer_load_b128 emits a one-dword load and splats it.

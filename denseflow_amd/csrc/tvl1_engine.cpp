@@ -168,7 +168,7 @@ int Tvl1Engine::create() {
     slot_stride = plane_stride * PL_COUNT;
     // the tile kernels address a pair slot with 32-bit byte offsets behind a buffer descriptor (tvl1_device_common.h)
     if ((unsigned long long)slot_stride * sizeof(float) >= (1ull << 32))
-        return dfx_fail(c, DFX_ERR_INVALID, "tvl1: frame too large (a pair's 16 work planes must stay below 4 GB: about 8192 x 8192)");
+        return dfx_fail(c, DFX_ERR_INVALID, "tvl1: frame too large (a pair's 16 work planes must stay below 4 GiB: round_up(width, 64) x height x 64 B < 2^32)");
     B = p.max_batch;
     if (B <= 0) {
         const long long px0 = (long long)c->W * c->H;
