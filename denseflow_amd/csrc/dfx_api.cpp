@@ -1525,6 +1525,23 @@ int dfx_get_stats(dfx_handle h, dfx_stats *out) {
     return DFX_OK;
 }
 
+// Test hook, not part of the ABI (include/dfx.h does not declare it).  For every pair of the most recent device batch of
+// a TVL1 handle, in pair order (the order of the batch's flows in the FlowBuffer), fills
+//     iters[pair][DFX_MAX_LEVELS][DFX_MAX_WARPS]  executed inner iterations per pyramid level and warp,
+//     checks[pair][DFX_MAX_LEVELS]                convergence sums evaluated per level,
+// zero beyond the pyramid and the warps, and returns the number of pairs.  dfx_stats.tvl1_iters / tvl1_checks hold the
+// last of these pairs only.  Valid after a synchronous call has returned, or after dfx_wait(h, 0).  Returns
+// -DFX_ERR_UNSUPPORTED for a handle of another algorithm, -DFX_ERR_INVALID before any batch has completed, after a failed
+// one, or when max_pairs is smaller than the batch.  However the engine dispatches a batch, the tables stay in pair
+// order.
+int dfxi_tvl1_batch_tables(dfx_handle h, int max_pairs, int *iters, int *checks) {
+    if (!h || !h->engine)
+        return -DFX_ERR_INVALID;
+    if (h->algo != DFX_ALGO_TVL1)
+        return -DFX_ERR_UNSUPPORTED;
+    return h->engine->batch_tables(max_pairs, iters, checks);
+}
+
 void dfx_reset_stats(dfx_handle h) {
     if (h)
         std::memset(&h->stats, 0, sizeof h->stats);

@@ -42,6 +42,11 @@ class AlgoEngine {
                              const int *h_slots) = 0;
     virtual int run_pairs(int nb, const PairDesc *h_pairs, float *d_out, long long out_stride) = 0;
     virtual int account(int nb) = 0; // reads per-batch event timers; stream is idle
+    // dfxi_tvl1_batch_tables (dfx_api.cpp): the per-pair TVL1 tables of the last accounted batch, in pair order
+    virtual int batch_tables(int max_pairs, int *iters, int *checks) const {
+        (void)max_pairs, (void)iters, (void)checks;
+        return -DFX_ERR_UNSUPPORTED;
+    }
 };
 
 struct dfx_context {

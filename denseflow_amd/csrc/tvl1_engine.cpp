@@ -37,6 +37,7 @@ class Tvl1Engine final : public AlgoEngine {
                      const int *h_slots) override;
     int run_pairs(int nb, const PairDesc *h_pairs, float *d_out, long long out_stride) override;
     int account(int nb) override;
+    int batch_tables(int max_pairs, int *iters, int *checks) const override;
 
   private:
     void destroy();
@@ -75,6 +76,7 @@ class Tvl1Engine final : public AlgoEngine {
     int geom = 0;            // 1 = tile columns of the step kernel start at x = 0 (Tvl1LevelCtx::geom)
     bool warp_head = false;  // the warp kernel also runs the head of the loop it starts (k_tvl1_warp_head)
     int launched_steps[DFX_LVL_MAX] = {0};
+    int last_nb = 0; // pairs of the batch whose read-backs h_iters / h_checks hold (set by account)
 
     Tvl1LoopCfg loop{};
     Tvl1Consts kc{};
@@ -302,6 +304,7 @@ int Tvl1Engine::steps_per_group(int s, int nb) const {
 }
 
 int Tvl1Engine::run_pairs(int nb, const PairDesc *h_pairs, float *d_out, long long out_stride) {
+    last_nb = 0; // the read-backs below overwrite the last batch's tables
     std::memcpy(h_pairs_pinned, h_pairs, sizeof(PairDesc) * nb);
     HIPCHK(c, hipMemcpyAsync(d_pairs, h_pairs_pinned, sizeof(PairDesc) * nb, hipMemcpyHostToDevice, c->stream));
     const int impl = c->prm.impl, math = c->prm.tvl1_math;
@@ -399,6 +402,7 @@ int Tvl1Engine::account(int nb) {
         }
         st.pairs += 1;
     }
+    last_nb = nb;
     const int b = nb - 1;
     st.levels = nlevels;
     st.tvl1_checks = 0;
@@ -410,6 +414,26 @@ int Tvl1Engine::account(int nb) {
         st.tvl1_checks += h_checks[(b * DFX_LVL_MAX + s) * 2];
     }
     return DFX_OK;
+}
+
+// The read-backs of the last accounted batch, pair by pair: iters[pair][DFX_MAX_LEVELS][DFX_MAX_WARPS] and
+// checks[pair][DFX_MAX_LEVELS], zero beyond the pyramid and the warps.
+int Tvl1Engine::batch_tables(int max_pairs, int *iters, int *checks) const {
+    if (last_nb <= 0)
+        return -DFX_ERR_INVALID;
+    if (max_pairs < last_nb || !iters || !checks)
+        return -DFX_ERR_INVALID;
+    static_assert(DFX_LVL_MAX <= DFX_MAX_LEVELS && TVL1_MAX_WARPS <= DFX_MAX_WARPS, "tables do not fit dfx.h's");
+    std::memset(iters, 0, sizeof(int) * (size_t)last_nb * DFX_MAX_LEVELS * DFX_MAX_WARPS);
+    std::memset(checks, 0, sizeof(int) * (size_t)last_nb * DFX_MAX_LEVELS);
+    for (int b = 0; b < last_nb; ++b)
+        for (int s = 0; s < nlevels; ++s) {
+            for (int w = 0; w < loop.warps; ++w)
+                iters[((size_t)b * DFX_MAX_LEVELS + s) * DFX_MAX_WARPS + w] =
+                    h_iters[(b * DFX_LVL_MAX + s) * TVL1_MAX_WARPS + w];
+            checks[(size_t)b * DFX_MAX_LEVELS + s] = h_checks[(b * DFX_LVL_MAX + s) * 2];
+        }
+    return last_nb;
 }
 
 } // namespace

@@ -213,6 +213,9 @@ def load_library():
     L.dfx_get_stats.argtypes = [vp, C.POINTER(DfxStats)]
     L.dfx_get_stats.restype = i
     L.dfx_reset_stats.argtypes = [vp]
+    if hasattr(L, "dfxi_tvl1_batch_tables"):  # test hook; a library built before it (DFX_LIBRARY A/B) still loads
+        L.dfxi_tvl1_batch_tables.argtypes = [vp, i, C.POINTER(i), C.POINTER(i)]
+        L.dfxi_tvl1_batch_tables.restype = i
     L.dfx_last_error.argtypes = [vp]
     L.dfx_last_error.restype = C.c_char_p
     L.dfx_destroy.argtypes = [vp]
@@ -562,3 +565,18 @@ class FlowEngine:
 
     def reset_stats(self):
         self._L.dfx_reset_stats(self._h)
+
+    def tvl1_batch_tables(self):
+        """dfxi_tvl1_batch_tables (test hook): for every pair of the last device batch, in pair order, the executed inner
+        iterations as a [levels][DFX_MAX_WARPS] table (the layout of DfxStats.iters_table) and the convergence sums
+        evaluated per level.  Returns (tables, checks)."""
+        st = self.stats()
+        cap = max(int(st.batch), 1)
+        iters = (C.c_int * (cap * DFX_MAX_LEVELS * DFX_MAX_WARPS))()
+        checks = (C.c_int * (cap * DFX_MAX_LEVELS))()
+        n = self._L.dfxi_tvl1_batch_tables(self._h, cap, iters, checks)
+        if n < 0:
+            raise DfxError(-n, f"dfxi_tvl1_batch_tables failed with status {-n}")
+        it = np.ctypeslib.as_array(iters).reshape(cap, DFX_MAX_LEVELS, DFX_MAX_WARPS)
+        ck = np.ctypeslib.as_array(checks).reshape(cap, DFX_MAX_LEVELS)
+        return ([it[b, :st.levels].tolist() for b in range(n)], [ck[b, :st.levels].tolist() for b in range(n)])

@@ -28,6 +28,13 @@ def test_library_exports_every_declared_symbol(dfx):
         assert hasattr(L, name), f"libdfx.so does not export {name}"
 
 
+def test_library_exports_the_tvl1_batch_tables_test_hook(dfx):
+    """dfxi_tvl1_batch_tables is exported for the GPU tests but stays out of the public header."""
+    L = C.CDLL(dfx.library_path())
+    assert hasattr(L, "dfxi_tvl1_batch_tables")
+    assert "dfxi_tvl1_batch_tables" not in open(os.path.join(ROOT, "include", "dfx.h")).read()
+
+
 def test_no_torch_or_cxx_types_in_signatures():
     src = open(os.path.join(ROOT, "include", "dfx.h")).read()
     assert "torch" not in src and "std::" not in src and "hip" not in src.replace("HIP", "").replace("gfx", "").lower().replace("ship", "") or True
