@@ -308,6 +308,7 @@ int Tvl1Engine::run_pairs(int nb, const PairDesc *h_pairs, float *d_out, long lo
     std::memcpy(h_pairs_pinned, h_pairs, sizeof(PairDesc) * nb);
     HIPCHK(c, hipMemcpyAsync(d_pairs, h_pairs_pinned, sizeof(PairDesc) * nb, hipMemcpyHostToDevice, c->stream));
     const int impl = c->prm.impl, math = c->prm.tvl1_math;
+    const bool nbr_lds = (c->prm.variant & DFX_VAR_TVL1_STEP_NBR_LDS) != 0;
     const float up = (float)(1.0 / c->prm.tvl1_scale_step);
     const int hard_limit = loop.warps * (loop.iterations + 2) + 64;
 
@@ -327,7 +328,7 @@ int Tvl1Engine::run_pairs(int nb, const PairDesc *h_pairs, float *d_out, long lo
                         tvl1_launch_warp_head(c->stream, x, step_id, math);
                     else if (split_warp)
                         tvl1_launch_warp(c->stream, x, step_id);
-                    tvl1_launch_step(c->stream, x, step_id++, impl, math);
+                    tvl1_launch_step(c->stream, x, step_id++, impl, math, nbr_lds);
                 }
                 c->stats.kernel_launches += (uint64_t)G * (split_warp ? 2 : 1);
                 HIPCHK(c, hipEventRecord(ev_group[g & 1], c->stream));

@@ -19,7 +19,7 @@ void tvl1_launch_warp(hipStream_t s, const Tvl1LevelCtx &c, int step_id); // ded
 // the warp AND the head of the loop it starts (tvl1_head_kernels.hip), in place of tvl1_launch_warp
 void tvl1_launch_warp_head(hipStream_t s, const Tvl1LevelCtx &c, int step_id, int math);
 int tvl1_head_blocks(const Tvl1LevelCtx &c); // workgroups per pair of that launch
-void tvl1_launch_step(hipStream_t s, const Tvl1LevelCtx &c, int step_id, int impl, int math);
+void tvl1_launch_step(hipStream_t s, const Tvl1LevelCtx &c, int step_id, int impl, int math, bool nbr_lds);
 int tvl1_step_blocks(const Tvl1LevelCtx &c, int impl); // workgroups per pair of a step launch
 int tvl1_fused_max_k();                                // largest supported inner-iteration fusion
 void tvl1_launch_upsample_u(hipStream_t s, const Tvl1LevelCtx &c_src, int dw, int dh, int dpitch, float ifx, float ify,

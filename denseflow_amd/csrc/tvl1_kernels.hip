@@ -546,7 +546,7 @@ __device__ __forceinline__ void tile_warp(const Tvl1LevelCtx &c, int b, int cur,
     }
 }
 
-template <int TH, int NW, bool INTERIOR, int MATH>
+template <int TH, int NW, bool INTERIOR, int MATH, bool LK>
 __device__ __forceinline__ double fused_tile_iterate_trap(const Tvl1LevelCtx &c, int b, float (*lds)[TH][64],
                                                           float (*bnd)[2 * NW][64], int S, int n_iters, bool do_check,
                                                           int K, int x0, int y0, bool own_lo, bool own_hi) {
@@ -554,15 +554,15 @@ __device__ __forceinline__ double fused_tile_iterate_trap(const Tvl1LevelCtx &c,
     TileState<TH / NW / 2> T;
     const int role = RowMap<TH, NW>::who();
     tile_issue_loads<TH, NW, INTERIOR>(c, b, S, x0, y0, pf);
-    tile_consume<TH, NW, INTERIOR, MATH>(c, x0, y0, pf, T, lds, bnd);
+    tile_consume<TH, NW, INTERIOR, MATH, LK>(c, x0, y0, pf, T, lds, bnd);
     __syncthreads();
     double dsum;
     if (role * (TH / NW / 2) < K) // only roles that hold halo rows carry the per-float2 skip tests
-        dsum = tile_iterate_trap<TH, NW, INTERIOR, true, MATH>(c, T, lds, bnd, n_iters, do_check, K, x0, y0, role, own_lo,
-                                                               own_hi);
+        dsum = tile_iterate_trap<TH, NW, INTERIOR, true, MATH, LK>(c, T, lds, bnd, n_iters, do_check, K, x0, y0, role,
+                                                                   own_lo, own_hi);
     else
-        dsum = tile_iterate_trap<TH, NW, INTERIOR, false, MATH>(c, T, lds, bnd, n_iters, do_check, K, x0, y0, role, own_lo,
-                                                                own_hi);
+        dsum = tile_iterate_trap<TH, NW, INTERIOR, false, MATH, LK>(c, T, lds, bnd, n_iters, do_check, K, x0, y0, role,
+                                                                    own_lo, own_hi);
     tile_store<TH, NW, INTERIOR>(c, b, S ^ 1, K, x0, y0, T, own_lo, own_hi);
     return dsum;
 }
@@ -613,22 +613,31 @@ __device__ __forceinline__ void end_iter_tile(const Tvl1LevelCtx &c, int b, Tvl1
 
 // The fused step kernel: 64 x 32 tile, 4 waves, up to K inner iterations per launch.
 //   PK = true : the packed-math tile function on the trapezoid row layout (the tuned default, impl 0), MATH as above;
+//               LK = true: its lean form (tvl1_tile.h: DPP lane neighbours, loop constants in LDS), 128 VGPRs = 4 waves
+//               per SIMD (k_tvl1_step_fused<true, MATH>, the default); LK = false: lane neighbours through LDS planes,
+//               constants in registers, 168 VGPRs = 3 waves per SIMD (rounds 2-6: k_tvl1_step_fused_nbr_lds<MATH>,
+//               dfx_params.variant & DFX_VAR_TVL1_STEP_NBR_LDS; the same bits);
 //   PK = false: the round-1 scalar tile function, kept as a cross-check (impl 2).
-// Register budget: 3 waves per SIMD (168 VGPRs); tighter budgets spill.
 #ifndef DFX_FT_TH // tile height / waves / waves per SIMD of the step kernel (A/B builds: scripts/build_variant.sh)
 #define DFX_FT_TH 32
 #define DFX_FT_NW 4
 #define DFX_FT_WGS 3
 #endif
+#ifndef DFX_FT_WGS_LK // waves per SIMD of the lean form
+#define DFX_FT_WGS_LK 4
+#endif
 constexpr int FT_TH = DFX_FT_TH, FT_NW = DFX_FT_NW;
 
-template <bool PK, int MATH>
-__global__ __launch_bounds__(64 * FT_NW, DFX_FT_WGS) void k_tvl1_step_fused(Tvl1LevelCtx c, int step_id, int tiles_x, int tiles_y) {
+template <bool PK, int MATH, bool LK>
+__device__ __forceinline__ void step_fused(const Tvl1LevelCtx &c, int step_id, int tiles_x, int tiles_y) {
     constexpr int TW = 64, TH = FT_TH, NW = FT_NW;
-    constexpr int LDS_FLOATS = PK ? (Q_PLANES * TH + 4 * NW) * TW : L_PLANES * TH * TW;
-    __shared__ float lds_raw[LDS_FLOATS];
+    // lean: KC_PLANES float2 planes of TH/2 rows (= as many float planes of TH rows) + B_PLANES boundary planes
+    constexpr int LDS_FLOATS = !PK ? L_PLANES * TH * TW : LK ? (KC_PLANES * TH + B_PLANES * 2 * NW) * TW
+                                                             : (Q_PLANES * TH + 4 * NW) * TW;
+    constexpr int LDS_PLANES = !PK ? 0 : LK ? KC_PLANES : Q_PLANES; // float planes of TH rows in front of bnd
+    __shared__ __attribute__((aligned(16))) float lds_raw[LDS_FLOATS];
     float (*lds)[TH][TW] = reinterpret_cast<float (*)[TH][TW]>(lds_raw);
-    float (*bnd2)[2 * NW][TW] = reinterpret_cast<float (*)[2 * NW][TW]>(lds_raw + (PK ? Q_PLANES * TH * TW : 0));
+    float (*bnd2)[2 * NW][TW] = reinterpret_cast<float (*)[2 * NW][TW]>(lds_raw + LDS_PLANES * TH * TW);
     __shared__ double lds_red[8];
     __shared__ int lds_flag;
 
@@ -642,7 +651,9 @@ __global__ __launch_bounds__(64 * FT_NW, DFX_FT_WGS) void k_tvl1_step_fused(Tvl1
     const unsigned nblk = gridDim.x; // = tiles of a step of this geometry (tvl1_step_grid)
 
     if (phase == TVL1_PH_WARP) {
-        if (c.split_warp) // k_tvl1_warp handles (or, with zero iterations, has just handled) this pair's warps
+        // k_tvl1_warp handles (or, with zero iterations, has just handled) this pair's warps; the lean form runs only then
+        // (tvl1_launch_step), so that the in-kernel warp's registers do not count against its 128
+        if (c.split_warp || LK)
             return;
         // in-kernel warp phase (scalar tile function, zero-iteration runs, the WARP_IN_STEP cross-check): classic tiling
         const int tile = dfx_xcd_tile_index((int)blockIdx.x, (int)nblk);
@@ -668,12 +679,12 @@ __global__ __launch_bounds__(64 * FT_NW, DFX_FT_WGS) void k_tvl1_step_fused(Tvl1
     double dsum;
     if (PK) {
         if (interior)
-            dsum = fused_tile_iterate_trap<TH, NW, true, MATH>(c, b, lds, bnd2, plan.src, plan.n_iters, plan.do_check != 0,
-                                                               K, xs, ys, false, false);
+            dsum = fused_tile_iterate_trap<TH, NW, true, MATH, LK>(c, b, lds, bnd2, plan.src, plan.n_iters,
+                                                                   plan.do_check != 0, K, xs, ys, false, false);
         else
-            dsum = fused_tile_iterate_trap<TH, NW, false, MATH>(c, b, lds, bnd2, plan.src, plan.n_iters,
-                                                                plan.do_check != 0, K, xs, ys, tp.own_lo != 0,
-                                                                tp.own_hi != 0);
+            dsum = fused_tile_iterate_trap<TH, NW, false, MATH, LK>(c, b, lds, bnd2, plan.src, plan.n_iters,
+                                                                    plan.do_check != 0, K, xs, ys, tp.own_lo != 0,
+                                                                    tp.own_hi != 0);
     } else {
         (void)bnd2;
         if (interior)
@@ -683,6 +694,18 @@ __global__ __launch_bounds__(64 * FT_NW, DFX_FT_WGS) void k_tvl1_step_fused(Tvl1
     }
     if (plan.is_last)
         end_iter_tile(c, b, st, plan, nblk, (int)blockIdx.x, step_id, dsum, lds_red, &lds_flag);
+}
+
+template <bool PK, int MATH>
+__global__ __launch_bounds__(64 * FT_NW, PK ? DFX_FT_WGS_LK : DFX_FT_WGS) void k_tvl1_step_fused(Tvl1LevelCtx c, int step_id,
+                                                                                          int tiles_x, int tiles_y) {
+    step_fused<PK, MATH, PK>(c, step_id, tiles_x, tiles_y);
+}
+
+template <int MATH>
+__global__ __launch_bounds__(64 * FT_NW, DFX_FT_WGS) void k_tvl1_step_fused_nbr_lds(Tvl1LevelCtx c, int step_id,
+                                                                                   int tiles_x, int tiles_y) {
+    step_fused<true, MATH, false>(c, step_id, tiles_x, tiles_y);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -720,8 +743,9 @@ void tvl1_launch_level_begin(hipStream_t s, const Tvl1LevelCtx &c, int first_lev
 int tvl1_fused_max_k() { return FT_TH / 2 - 4; } // owned region stays >= 8 rows tall
 
 // impl: 0 = packed tile function (math = dfx_params.tvl1_math; the scalar forms take the hypot reading from c.k.hyp), 1 = simple one-pixel-per-thread kernel, 2 = scalar tile
-// function.  The grid of the fused kernels is the step's tile count (tvl1_step_blocks).
-void tvl1_launch_step(hipStream_t s, const Tvl1LevelCtx &c, int step_id, int impl, int math) {
+// function.  nbr_lds: impl 0 in its register form (DFX_VAR_TVL1_STEP_NBR_LDS).  The grid of the fused kernels is the step's
+// tile count (tvl1_step_blocks).
+void tvl1_launch_step(hipStream_t s, const Tvl1LevelCtx &c, int step_id, int impl, int math, bool nbr_lds) {
     if (impl == 1) {
         hipLaunchKernelGGL(k_tvl1_step_simple, grid_for(c.w, c.h, c.n_pairs), dim3(256), 0, s, c, step_id);
         return;
@@ -729,7 +753,16 @@ void tvl1_launch_step(hipStream_t s, const Tvl1LevelCtx &c, int step_id, int imp
     const int K = c.loop.fuse_k;
     const Tvl1StepGeom g = tvl1_step_geom(c.w, c.h, 64, FT_TH, K, 0); // classic counts: the in-kernel warp phase
     const dim3 grid(tvl1_step_blocks(c, impl), 1, c.n_pairs), block(64 * FT_NW);
-    if (impl == 2)
+    if (impl == 0 && (nbr_lds || !c.split_warp)) { // the lean form has no in-kernel warp phase
+        if (math == 1)
+            hipLaunchKernelGGL((k_tvl1_step_fused_nbr_lds<1>), grid, block, 0, s, c, step_id, g.ntx, g.nty);
+        else if (math == TVL1_HYP_SQRT)
+            hipLaunchKernelGGL((k_tvl1_step_fused_nbr_lds<TVL1_HYP_SQRT>), grid, block, 0, s, c, step_id, g.ntx, g.nty);
+        else if (math == TVL1_HYP_LIBM)
+            hipLaunchKernelGGL((k_tvl1_step_fused_nbr_lds<TVL1_HYP_LIBM>), grid, block, 0, s, c, step_id, g.ntx, g.nty);
+        else
+            hipLaunchKernelGGL((k_tvl1_step_fused_nbr_lds<0>), grid, block, 0, s, c, step_id, g.ntx, g.nty);
+    } else if (impl == 2)
         hipLaunchKernelGGL((k_tvl1_step_fused<false, 0>), grid, block, 0, s, c, step_id, g.ntx, g.nty);
     else if (math == 1)
         hipLaunchKernelGGL((k_tvl1_step_fused<true, 1>), grid, block, 0, s, c, step_id, g.ntx, g.nty);

@@ -34,6 +34,50 @@
 
 enum { Q_P11 = 0, Q_P21, Q_U1, Q_U2, Q_PLANES };
 
+// The lean form of the tile function (LK = true: the step kernel's default, 128 VGPRs = 4 waves per SIMD).  Same tile,
+// same rows per thread, same arithmetic and error-sum order, but the tile's data lives elsewhere:
+//   * the lane +-1 neighbours (p11 / p21 from the left, u1 / u2 from the right) come from the neighbouring lane's register
+//     by DPP (wave_shr:1 / wave_shl:1; a tile row is exactly one wave) instead of through the four [TH][64] LDS planes.  gfx9
+//     has no DPP on VOP3P: the primal's p - p_left is formed per half (v_subrev_f32 with a DPP source), the dual's
+//     u_right - u from v_mov_b32_dpp values; either way every half is the same IEEE subtraction as before.  Lane 0 (left) and lane 63 (right) receive 0 instead of their own value: in an interior
+//     tile they are halo lanes outside every owned pixel's dependency cone over n_iters <= K iterations, and at the image
+//     border the has_left / has_right selects replace them as before;
+//   * rho_c, grad and 1/grad, constant over the iterations, move into the LDS that frees: float2-interleaved planes
+//     kc[KC_*][role * HP + j][lane], one ds_read_b64 per float2 (wave-private: no barrier); l_t * grad is recomputed in the
+//     loop (the same product, the same bits);
+//   * the vertical neighbours across roles travel through boundary rows for u as they already did for p12 / p22:
+//     bnd[B_*][2 * NW][64].
+// LDS: 3 x [TH/2][64] float2 + 4 x [2 * NW][64] float = 32 KB at TH = 32 (the register form: 36 KB).
+enum { KC_RHOC = 0, KC_GRAD, KC_RGRAD, KC_PLANES };
+enum { B_P12 = 0, B_P22, B_U1, B_U2, B_PLANES };
+
+// the value of lane - 1 (lane 0: 0) / lane + 1 (lane 63: 0) of a wave (the border tiles, where a select follows)
+__device__ __forceinline__ float lane_from_left(float v) {
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x138, 0xf, 0xf, true)); // wave_shr:1
+}
+__device__ __forceinline__ float lane_from_right(float v) {
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x130, 0xf, 0xf, true)); // wave_shl:1
+}
+
+// The interior tiles' primal differences: a - (a of lane - 1) and b - (b of lane - 1) for both halves, one v_subrev_f32 with
+// a DPP source each (lane 0: a - 0).  Inline assembly because the compiler packs the scalar subtractions back into
+// v_pk_add_f32 (SLP), which takes no DPP operand, and then keeps a v_mov_b32_dpp per half.  (The dual's u_right - u stays
+// compiler-generated: its result feeds v_max_f32 / v_min_f32, which would need a canonicalising v_max_f32 per half after
+// inline assembly — 8 VALU more per iteration than the DPP moves cost.)
+// s_nop 1: a DPP instruction reading a VGPR that a VALU instruction wrote needs two wait states in between.
+__device__ __forceinline__ void sub_from_left(f2 a, f2 b, f2 &da, f2 &db) {
+    float r0, r1, r2, r3;
+    asm("s_nop 1\n\t"
+        "v_subrev_f32_dpp %0, %4, %4 wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+        "v_subrev_f32_dpp %1, %5, %5 wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+        "v_subrev_f32_dpp %2, %6, %6 wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+        "v_subrev_f32_dpp %3, %7, %7 wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1"
+        : "=&v"(r0), "=&v"(r1), "=&v"(r2), "=&v"(r3)
+        : "v"(a.x), "v"(a.y), "v"(b.x), "v"(b.y));
+    da = pk_set(r0, r1);
+    db = pk_set(r2, r3);
+}
+
 // The packed tile function in four phases: issue the HBM loads of a tile (raw, into registers) / turn them into the
 // tile state (mask, pack, 1/grad, LDS neighbour planes) / iterate / store the owned region.
 
@@ -91,13 +135,16 @@ __device__ __forceinline__ void tile_issue_loads(const Tvl1LevelCtx &c, int b, i
         }
 }
 
-template <int TH, int NW, bool INTERIOR, int MATH>
+// LK: lds = the KC_PLANES constant planes (as f2 [TH/2][64] each), bnd = B_PLANES boundary planes; kgr / krg / klg / krc
+// of T are left unset (they live in LDS).  !LK: lds = the Q_PLANES neighbour planes, bnd = the p12 / p22 boundary planes.
+template <int TH, int NW, bool INTERIOR, int MATH, bool LK = false>
 __device__ __forceinline__ void tile_consume(const Tvl1LevelCtx &c, int x0, int y0,
                                              const float (&pf)[PF_PLANES][TH / NW / 2][2], TileState<TH / NW / 2> &T,
                                              float (*lds)[TH][64], float (*bnd)[2 * NW][64]) {
     constexpr int RPT = TH / NW, HP = RPT / 2;
     using RM = RowMap<TH, NW>;
     const int lx = threadIdx.x & 63, rg = RM::who();
+    f2 (*kc)[TH / 2][64] = reinterpret_cast<f2 (*)[TH / 2][64]>(lds);
     const int gx = x0 + lx;
     const bool col_in = INTERIOR || (gx >= 0 && gx < c.w);
 #pragma unroll
@@ -131,10 +178,16 @@ __device__ __forceinline__ void tile_consume(const Tvl1LevelCtx &c, int x0, int 
             T.krg[j] = pk_set(T.kgr[j].x > FLT_EPSILON ? -r.x : 0.0f, T.kgr[j].y > FLT_EPSILON ? -r.y : 0.0f);
             T.kgr[j] = c.k.l_t * T.kgr[j];
         }
-        lds[Q_P11][RM::row(rg, j, 0)][lx] = T.p11[j].x;
-        lds[Q_P11][RM::row(rg, j, 1)][lx] = T.p11[j].y;
-        lds[Q_P21][RM::row(rg, j, 0)][lx] = T.p21[j].x;
-        lds[Q_P21][RM::row(rg, j, 1)][lx] = T.p21[j].y;
+        if (LK) {
+            kc[KC_RHOC][rg * HP + j][lx] = T.krc[j];
+            kc[KC_GRAD][rg * HP + j][lx] = T.kgr[j];
+            kc[KC_RGRAD][rg * HP + j][lx] = T.krg[j];
+        } else {
+            lds[Q_P11][RM::row(rg, j, 0)][lx] = T.p11[j].x;
+            lds[Q_P11][RM::row(rg, j, 1)][lx] = T.p11[j].y;
+            lds[Q_P21][RM::row(rg, j, 0)][lx] = T.p21[j].x;
+            lds[Q_P21][RM::row(rg, j, 1)][lx] = T.p21[j].y;
+        }
     }
     // rows read as upper neighbours by other roles: the last upper-half row, the highest lower-half row
     bnd[0][rg][lx] = T.p12[HP - 1].x;
@@ -153,11 +206,13 @@ __device__ __forceinline__ void tile_consume(const Tvl1LevelCtx &c, int x0, int 
 //     a from the edges that means: primal update iff a >= K-d-1, dual update iff a >= K-d.  Role 0 (a = 0 .. HP-1)
 //     skips 6 of its 16 primal and 10 of its 16 dual float2-updates at K = 4: 14 % of the arithmetic of a full step.
 //     Skipped rows keep stale values nobody reads (the store and the error sum only touch rows >= K).
-template <int TH, int NW, bool INTERIOR, bool SKIPS, int MATH>
+// LK: the lean form (DPP lane neighbours, constants from LDS; see the top of this file), lds / bnd as in tile_consume.
+template <int TH, int NW, bool INTERIOR, bool SKIPS, int MATH, bool LK = false>
 __device__ __forceinline__ double tile_iterate_trap(const Tvl1LevelCtx &c, TileState<TH / NW / 2> &T,
                                                     float (*lds)[TH][64], float (*bnd)[2 * NW][64], int n_iters,
                                                     bool do_check, int K, int x0, int y0, int role, bool own_lo,
                                                     bool own_hi) {
+    const f2 (*kc)[TH / 2][64] = reinterpret_cast<const f2 (*)[TH / 2][64]>(lds);
     constexpr int TW = 64;
     constexpr int RPT = TH / NW, HP = RPT / 2;
     using RM = RowMap<TH, NW>;
@@ -194,20 +249,34 @@ __device__ __forceinline__ double tile_iterate_trap(const Tvl1LevelCtx &c, TileS
                 continue;
             }
             const int lya = RM::row(role, j, 0), lyb = RM::row(role, j, 1);
+            const f2 krc = LK ? kc[KC_RHOC][role * HP + j][lx] : T.krc[j];
+            const f2 kgr = LK ? kc[KC_GRAD][role * HP + j][lx] : T.kgr[j];
+            const f2 krg = LK ? kc[KC_RGRAD][role * HP + j][lx] : T.krg[j];
             f2 v1, v2;
             if (MATH != 1)
-                pk_threshold(T.kwx[j], T.kwy[j], T.kgr[j], T.krg[j], T.klg[j], T.krc[j], T.u1[j], T.u2[j], l_t, v1, v2);
+                pk_threshold(T.kwx[j], T.kwy[j], kgr, krg, LK ? l_t * kgr : T.klg[j], krc, T.u1[j], T.u2[j], l_t, v1, v2);
             else
-                pk_threshold_fast(T.kwx[j], T.kwy[j], T.kgr[j], T.krg[j], T.krc[j], T.u1[j], T.u2[j], l_t, v1, v2);
-            const f2 p11l = pk_set(lds[Q_P11][lya][lxl], lds[Q_P11][lyb][lxl]);
-            const f2 p21l = pk_set(lds[Q_P21][lya][lxl], lds[Q_P21][lyb][lxl]);
+                pk_threshold_fast(T.kwx[j], T.kwy[j], kgr, krg, krc, T.u1[j], T.u2[j], l_t, v1, v2);
+            f2 p11l, p21l; // (the interior lean form needs only the differences)
+            if (!LK) {
+                p11l = pk_set(lds[Q_P11][lya][lxl], lds[Q_P11][lyb][lxl]);
+                p21l = pk_set(lds[Q_P21][lya][lxl], lds[Q_P21][lyb][lxl]);
+            } else if (!INTERIOR) {
+                p11l = pk_set(lane_from_left(T.p11[j].x), lane_from_left(T.p11[j].y));
+                p21l = pk_set(lane_from_left(T.p21[j].x), lane_from_left(T.p21[j].y));
+            }
             // upper neighbours: upper half <- float2 j-1, lower half <- float2 j+1
             const f2 p12u = pk_set(j > 0 ? T.p12[j > 0 ? j - 1 : 0].x : p12ux,
                                    j + 1 < HP ? T.p12[j + 1 < HP ? j + 1 : 0].y : p12uy);
             const f2 p22u = pk_set(j > 0 ? T.p22[j > 0 ? j - 1 : 0].x : p22ux,
                                    j + 1 < HP ? T.p22[j + 1 < HP ? j + 1 : 0].y : p22uy);
             f2 div1, div2;
-            if (INTERIOR) {
+            if (INTERIOR && LK) { // p11 - p11l per half: the DPP operand cannot feed a packed instruction
+                f2 d1, d2;
+                sub_from_left(T.p11[j], T.p21[j], d1, d2);
+                div1 = d1 + (T.p12[j] - p12u);
+                div2 = d2 + (T.p22[j] - p22u);
+            } else if (INTERIOR) {
                 div1 = (T.p11[j] - p11l) + (T.p12[j] - p12u);
                 div2 = (T.p21[j] - p21l) + (T.p22[j] - p22u);
             } else {
@@ -223,10 +292,18 @@ __device__ __forceinline__ double tile_iterate_trap(const Tvl1LevelCtx &c, TileS
             }
             T.u1[j] = u1n;
             T.u2[j] = u2n;
-            lds[Q_U1][lya][lx] = u1n.x;
-            lds[Q_U1][lyb][lx] = u1n.y;
-            lds[Q_U2][lya][lx] = u2n.x;
-            lds[Q_U2][lyb][lx] = u2n.y;
+            if (!LK) {
+                lds[Q_U1][lya][lx] = u1n.x;
+                lds[Q_U1][lyb][lx] = u1n.y;
+                lds[Q_U2][lya][lx] = u2n.x;
+                lds[Q_U2][lyb][lx] = u2n.y;
+            }
+        }
+        if (LK) { // rows read as lower neighbours by other roles: the first upper-half row, the highest lower-half row
+            bnd[B_U1][role][lx] = T.u1[0].x;
+            bnd[B_U2][role][lx] = T.u2[0].x;
+            bnd[B_U1][NW + role][lx] = T.u1[HP - 1].y;
+            bnd[B_U2][NW + role][lx] = T.u2[HP - 1].y;
         }
         if (chk) { // rows in ascending order within each half
 #pragma unroll
@@ -242,15 +319,32 @@ __device__ __forceinline__ double tile_iterate_trap(const Tvl1LevelCtx &c, TileS
         }
         __syncthreads();
         // ---- dual update (A.7)
-        const float u1dx = lds[Q_U1][row_xd][lx], u2dx = lds[Q_U2][row_xd][lx];
-        const float u1dy = lds[Q_U1][row_yd][lx], u2dy = lds[Q_U2][row_yd][lx];
+        float u1dx, u2dx, u1dy, u2dy;
+        if (LK) { // row a0 + HP: role + 1's first upper-half row (innermost: its own lower half); row TH - a0: role - 1's
+                  // highest lower-half row (role 0: clamped to its own row TH - 1, halo)
+            u1dx = innermost ? T.u1[HP - 1].y : bnd[B_U1][min(role + 1, NW - 1)][lx];
+            u2dx = innermost ? T.u2[HP - 1].y : bnd[B_U2][min(role + 1, NW - 1)][lx];
+            u1dy = role == 0 ? T.u1[0].y : bnd[B_U1][NW + max(role - 1, 0)][lx];
+            u2dy = role == 0 ? T.u2[0].y : bnd[B_U2][NW + max(role - 1, 0)][lx];
+        } else {
+            u1dx = lds[Q_U1][row_xd][lx];
+            u2dx = lds[Q_U2][row_xd][lx];
+            u1dy = lds[Q_U1][row_yd][lx];
+            u2dy = lds[Q_U2][row_yd][lx];
+        }
 #pragma unroll
         for (int j = 0; j < HP; ++j) {
             if (SKIPS && a0 + j < need)
                 continue;
             const int lya = RM::row(role, j, 0), lyb = RM::row(role, j, 1);
-            f2 u1r = pk_set(lds[Q_U1][lya][lxr], lds[Q_U1][lyb][lxr]);
-            f2 u2r = pk_set(lds[Q_U2][lya][lxr], lds[Q_U2][lyb][lxr]);
+            f2 u1r, u2r; // (the interior lean form needs only the differences)
+            if (!LK) {
+                u1r = pk_set(lds[Q_U1][lya][lxr], lds[Q_U1][lyb][lxr]);
+                u2r = pk_set(lds[Q_U2][lya][lxr], lds[Q_U2][lyb][lxr]);
+            } else if (!INTERIOR) {
+                u1r = pk_set(lane_from_right(T.u1[j].x), lane_from_right(T.u1[j].y));
+                u2r = pk_set(lane_from_right(T.u2[j].x), lane_from_right(T.u2[j].y));
+            }
             // lower neighbours: upper half <- float2 j+1, lower half <- float2 j-1
             f2 u1d = pk_set(j + 1 < HP ? T.u1[j + 1 < HP ? j + 1 : 0].x : u1dx, j > 0 ? T.u1[j > 0 ? j - 1 : 0].y : u1dy);
             f2 u2d = pk_set(j + 1 < HP ? T.u2[j + 1 < HP ? j + 1 : 0].x : u2dx, j > 0 ? T.u2[j > 0 ? j - 1 : 0].y : u2dy);
@@ -265,17 +359,28 @@ __device__ __forceinline__ double tile_iterate_trap(const Tvl1LevelCtx &c, TileS
                 u2d.x = dn_a ? u2d.x : T.u2[j].x;
                 u2d.y = dn_b ? u2d.y : T.u2[j].y;
             }
-            if (MATH != 1) {
-                pk_dual<MATH>(T.p11[j], T.p12[j], u1r - T.u1[j], u1d - T.u1[j], taut, taut_s);
-                pk_dual<MATH>(T.p21[j], T.p22[j], u2r - T.u2[j], u2d - T.u2[j], taut, taut_s);
+            // u_right - u: per half with the DPP source in the interior lean form, packed otherwise — the same bits
+            f2 u1x, u2x;
+            if (LK && INTERIOR) {
+                u1x = pk_set(lane_from_right(T.u1[j].x) - T.u1[j].x, lane_from_right(T.u1[j].y) - T.u1[j].y);
+                u2x = pk_set(lane_from_right(T.u2[j].x) - T.u2[j].x, lane_from_right(T.u2[j].y) - T.u2[j].y);
             } else {
-                pk_dual_fast(T.p11[j], T.p12[j], u1r - T.u1[j], u1d - T.u1[j], taut);
-                pk_dual_fast(T.p21[j], T.p22[j], u2r - T.u2[j], u2d - T.u2[j], taut);
+                u1x = u1r - T.u1[j];
+                u2x = u2r - T.u2[j];
             }
-            lds[Q_P11][lya][lx] = T.p11[j].x;
-            lds[Q_P11][lyb][lx] = T.p11[j].y;
-            lds[Q_P21][lya][lx] = T.p21[j].x;
-            lds[Q_P21][lyb][lx] = T.p21[j].y;
+            if (MATH != 1) {
+                pk_dual<MATH>(T.p11[j], T.p12[j], u1x, u1d - T.u1[j], taut, taut_s);
+                pk_dual<MATH>(T.p21[j], T.p22[j], u2x, u2d - T.u2[j], taut, taut_s);
+            } else {
+                pk_dual_fast(T.p11[j], T.p12[j], u1x, u1d - T.u1[j], taut);
+                pk_dual_fast(T.p21[j], T.p22[j], u2x, u2d - T.u2[j], taut);
+            }
+            if (!LK) {
+                lds[Q_P11][lya][lx] = T.p11[j].x;
+                lds[Q_P11][lyb][lx] = T.p11[j].y;
+                lds[Q_P21][lya][lx] = T.p21[j].x;
+                lds[Q_P21][lyb][lx] = T.p21[j].y;
+            }
         }
         bnd[0][role][lx] = T.p12[HP - 1].x;
         bnd[1][role][lx] = T.p22[HP - 1].x;
