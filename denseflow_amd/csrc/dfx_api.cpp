@@ -860,6 +860,8 @@ int calc_batch_body(dfx_context *c, const uint8_t *const *frames, size_t frame_p
 int calc_batch_impl(dfx_context *c, const uint8_t *const *frames, size_t frame_pitch, const uint8_t *d_frames,
                     size_t d_pitch, size_t d_frame_stride, int n_frames, int step, const OutSpec &out,
                     unsigned long long *ticket = nullptr) {
+    if (c->algo == DFX_ALGO_FRAMES) // every flow entry point funnels through here
+        return dfx_fail(c, DFX_ERR_UNSUPPORTED, "a DFX_ALGO_FRAMES handle computes no flow");
     const int rc = calc_batch_body(c, frames, frame_pitch, d_frames, d_pitch, d_frame_stride, n_frames, step, out, ticket);
     if (rc != DFX_OK) {
         const std::string keep = c->get_err();
@@ -932,7 +934,7 @@ int dfx_create(dfx_handle *out, int device, dfx_algo algo, int width, int height
     *out = nullptr;
     if (width < 1 || height < 1 || width > 32768 || height > 32768)
         return fail_create(DFX_ERR_INVALID, "invalid frame size");
-    if (algo != DFX_ALGO_TVL1 && algo != DFX_ALGO_FARN && algo != DFX_ALGO_BROX)
+    if (algo != DFX_ALGO_TVL1 && algo != DFX_ALGO_FARN && algo != DFX_ALGO_BROX && algo != DFX_ALGO_FRAMES)
         return fail_create(DFX_ERR_INVALID, "invalid algorithm id");
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0)
@@ -976,8 +978,10 @@ int dfx_create(dfx_handle *out, int device, dfx_algo algo, int width, int height
             c->engine = dfx_make_tvl1_engine(c);
         else if (algo == DFX_ALGO_FARN)
             c->engine = dfx_make_farneback_engine(c);
-        else
+        else if (algo == DFX_ALGO_BROX)
             c->engine = dfx_make_brox_engine(c);
+        else
+            c->engine = dfx_make_frames_engine(c);
         return c->engine->create();
     };
     const int rc = init();
@@ -1584,6 +1588,7 @@ void dfx_destroy(dfx_handle h) {
     for (auto &p : h->h_png_bounds)
         dfx_free_host(p);
     free_jpeg(h);
+    dfx_free_colour(h);
     for (auto &e : h->ev_h2d)
         if (e)
             (void)hipEventDestroy(e);

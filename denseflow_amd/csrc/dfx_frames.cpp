@@ -1,0 +1,473 @@
+// dfx_frames.cpp — colour frame extraction behind the C ABI (include/dfx.h): DFX_ALGO_FRAMES handles, the 3-channel
+// resize, the colour JPEG encoder and dfx_extract_frames, which chains them for one buffer of frames.
+//
+// Reference behaviour replaced: DenseFlow::extract_frames_only, /root/reference/src/denseflow_gpu.cpp:82-105 —
+// load_frames_batch(..., to_gray = false) :88, cv::resize of the BGR frame :94-98, imencode(".jpg", frame) :99-101.
+#include <algorithm>
+#include <cstring>
+
+#include "dfx_internal.h"
+#include "jpeg_kernels.h"
+#include "prepare_kernels.h"
+
+namespace {
+
+// A DFX_ALGO_FRAMES handle has no flow engine behind it: this one allocates nothing and refuses every flow request
+// (the ABI's flow entry points stop earlier, in calc_batch_impl).
+class FramesEngine : public AlgoEngine {
+  public:
+    explicit FramesEngine(dfx_context *c) : c_(c) {}
+    int create() override { return DFX_OK; }
+    int batch() const override;
+    int ensure_frame_slots(int) override { return refuse(); }
+    int frame_slots() const override { return 0; }
+    int build_frames(const unsigned char *, long long, long long, int, const int *) override { return refuse(); }
+    int run_pairs(int, const PairDesc *, float *, long long) override { return refuse(); }
+    int account(int) override { return refuse(); }
+
+  private:
+    int refuse() const { return dfx_fail(c_, DFX_ERR_UNSUPPORTED, "a DFX_ALGO_FRAMES handle computes no flow"); }
+    dfx_context *c_;
+};
+
+// Frames per device batch: dfx_params.max_batch, or 32 Mpx of output frames (16 at 1080p: 100 MB of source frames per
+// staging parity, enough blocks — 780 000 — to fill the device many times over).
+int frames_batch(const dfx_context *c) {
+    if (c->prm.max_batch > 0)
+        return c->prm.max_batch;
+    const long long px = (long long)c->W * c->H;
+    return (int)std::max<long long>(1, std::min<long long>(256, (32ll << 20) / px));
+}
+
+int FramesEngine::batch() const { return frames_batch(c_); }
+
+size_t round4(size_t v) { return (v + 3) & ~(size_t)3; }
+
+template <class T> int dev_alloc(dfx_context *c, T *&p, size_t bytes) {
+    HIPCHK(c, hipMalloc((void **)&p, bytes));
+    c->colour.device_bytes += bytes;
+    return DFX_OK;
+}
+
+void free_encoder(dfx_context *c) {
+    auto &j = c->colour;
+    dfx_free_dev(j.d_tab);
+    dfx_free_dev(j.d_dc);
+    dfx_free_dev(j.d_bits);
+    dfx_free_dev(j.d_plane_bits);
+    dfx_free_dev(j.d_plane_base);
+    dfx_free_dev(j.d_hdr);
+    for (int q = 0; q < 2; ++q) {
+        dfx_free_dev(j.d_stream[q]);
+        dfx_free_host(j.h_stream[q]);
+        j.h_capacity[q] = 0;
+        dfx_free_host(j.h_info[q]);
+        j.d_info[q] = nullptr;
+    }
+    j.quality = j.frames = 0;
+    j.capacity = 0;
+}
+
+void free_staging(dfx_context *c) {
+    auto &j = c->colour;
+    for (auto &p : j.d_src)
+        dfx_free_dev(p);
+    dfx_free_dev(j.d_bgr);
+    j.src_slots = j.bgr_slots = 0;
+    j.src_pitch = j.src_frame_bytes = 0;
+}
+
+// Everything of the colour state, sized for batches of `frames` frames at `quality` from sw x sh sources.  Any change
+// re-allocates the lot (a handle is used with one source size and one quality).
+int ensure_colour(dfx_context *c, int frames, int quality, int sw, int sh) {
+    auto &j = c->colour;
+    const bool resize = sw != c->W || sh != c->H;
+    const size_t sp = round4((size_t)sw * 3), fb = sp * (size_t)sh;
+    if (j.quality == quality && frames <= j.frames && frames <= j.src_slots && j.src_frame_bytes == fb && j.src_pitch == sp &&
+        (!resize || frames <= j.bgr_slots))
+        return DFX_OK;
+    (void)dfx_finish_tails(c, 0, -1);
+    HIPCHK(c, hipDeviceSynchronize());
+    free_encoder(c);
+    free_staging(c);
+    j.device_bytes = 0;
+    const size_t mcus = (size_t)((c->W + 15) / 16) * ((c->H + 15) / 16), nblk = mcus * 6;
+    JpegTables t[2];
+    jpeg_build_colour_tables(quality, t);
+    j.header = jpeg_colour_file_header(c->W, c->H, quality);
+    int rc = dev_alloc(c, j.d_tab, sizeof t);
+    if (rc != DFX_OK)
+        return rc;
+    HIPCHK(c, hipMemcpy(j.d_tab, t, sizeof t, hipMemcpyHostToDevice));
+    if ((rc = dev_alloc(c, j.d_dc, (size_t)frames * nblk * sizeof(short))) != DFX_OK ||
+        (rc = dev_alloc(c, j.d_bits, (size_t)frames * nblk * sizeof(unsigned))) != DFX_OK ||
+        (rc = dev_alloc(c, j.d_plane_bits, (size_t)frames * 8)) != DFX_OK ||
+        (rc = dev_alloc(c, j.d_plane_base, (size_t)frames * 8)) != DFX_OK || (rc = dev_alloc(c, j.d_hdr, 16)) != DFX_OK)
+        return rc;
+    // shared stream buffer: 4 bits per pixel on average over the batch (a photographic frame at quality 95 needs 1.5 - 3;
+    // a batch that does not fit is measured and coded again after grow_streams)
+    j.capacity = (((size_t)frames * c->W * c->H / 2 + (64u << 10)) + 255) & ~(size_t)255;
+    for (int p = 0; p < 2; ++p) {
+        if ((rc = dev_alloc(c, j.d_stream[p], j.capacity)) != DFX_OK)
+            return rc;
+        j.h_capacity[p] = j.capacity;
+        HIPCHK(c, hipHostMalloc((void **)&j.h_stream[p], j.h_capacity[p], hipHostMallocDefault));
+        HIPCHK(c, hipHostMalloc((void **)&j.h_info[p], (2 + 2 * (size_t)frames) * 8, hipHostMallocMapped));
+        std::memset(j.h_info[p], 0, (2 + 2 * (size_t)frames) * 8);
+        HIPCHK(c, hipHostGetDevicePointer((void **)&j.d_info[p], j.h_info[p], 0));
+        if ((rc = dev_alloc(c, j.d_src[p], (size_t)frames * fb)) != DFX_OK)
+            return rc;
+    }
+    if (resize && (rc = dev_alloc(c, j.d_bgr, (size_t)frames * round4((size_t)c->W * 3) * c->H)) != DFX_OK)
+        return rc;
+    j.quality = quality;
+    j.frames = j.src_slots = frames;
+    j.bgr_slots = resize ? frames : 0;
+    j.src_pitch = sp;
+    j.src_frame_bytes = fb;
+    return DFX_OK;
+}
+
+// The stream buffers (device + landing, both parities) re-sized to hold `need` bytes; on failure the old ones stay.
+int grow_streams(dfx_context *c, unsigned long long need) {
+    auto &j = c->colour;
+    (void)dfx_finish_tails(c, 0, -1); // a deferred tail may still be reading a landing buffer
+    HIPCHK(c, hipDeviceSynchronize());
+    const size_t cap = (((size_t)need + (size_t)need / 4 + (64u << 10)) + 255) & ~(size_t)255;
+    unsigned *nd[2] = {nullptr, nullptr};
+    unsigned char *nh[2] = {nullptr, nullptr};
+    hipError_t e = hipSuccess;
+    for (int p = 0; p < 2 && e == hipSuccess; ++p) {
+        e = hipMalloc((void **)&nd[p], cap);
+        if (e == hipSuccess)
+            e = hipHostMalloc((void **)&nh[p], cap, hipHostMallocDefault);
+    }
+    if (e != hipSuccess) {
+        for (int p = 0; p < 2; ++p) {
+            if (nd[p])
+                (void)hipFree(nd[p]);
+            if (nh[p])
+                (void)hipHostFree(nh[p]);
+        }
+        (void)hipGetLastError();
+        return dfx_fail(c, DFX_ERR_HIP, "growing the colour JPEG stream buffers failed; the encoder keeps its old buffers");
+    }
+    for (int p = 0; p < 2; ++p) {
+        dfx_free_dev(j.d_stream[p]);
+        dfx_free_host(j.h_stream[p]);
+        j.d_stream[p] = nd[p];
+        j.h_stream[p] = nh[p];
+        j.h_capacity[p] = cap;
+    }
+    j.device_bytes += 2 * (cap - j.capacity);
+    j.capacity = cap;
+    return DFX_OK;
+}
+
+struct BatchFiles { // what the host needs to assemble the files of one device batch
+    int i0 = 0, n = 0, parity = 0;
+    std::vector<unsigned long long> bits, base;
+};
+
+int assemble(dfx_context *c, const std::vector<unsigned char> &header, const unsigned char *landing, const BatchFiles &b,
+             uint8_t *const *jpg, size_t cap, uint32_t *sizes, std::string *err) {
+    for (int j = 0; j < b.n; ++j) {
+        const size_t sz = jpeg_assemble(header, landing + b.base[j], b.bits[j], jpg[b.i0 + j], cap);
+        if (sz == 0) {
+            const char *m = "JPEG: jpg_capacity is too small for an encoded frame";
+            if (err)
+                *err = m;
+            else
+                c->set_err(m);
+            return DFX_ERR_UNSUPPORTED;
+        }
+        sizes[b.i0 + j] = (uint32_t)sz;
+    }
+    return DFX_OK;
+}
+
+// n source-size BGR frames -> n files, in device batches.  Per batch q (parity p = seq & 1):
+//   copy stream : frames -> d_src[p]                                        (batch q + 1 goes up while q computes)
+//   compute     : [resize d_src[p] -> d_bgr] -> encode -> d_stream[p]; the totals land in h_info[p]
+//   d2h stream  : d_stream[p] -> h_stream[p]
+//   host        : header + stuffing of batch q - 1 while batch q computes
+// ticket != nullptr: the last batch's download and assembly finish on a helper thread (dfx_context::Tail).
+int extract_body(dfx_context *c, const uint8_t *const *frames, size_t pitch, int sw, int sh, int n, int quality,
+                 uint8_t *const *jpg, size_t cap, uint32_t *sizes, unsigned long long *ticket) {
+    auto &j = c->colour;
+    const int B = std::min(frames_batch(c), std::max(n, 1));
+    int rc = ensure_colour(c, std::max(B, j.frames), quality, sw, sh);
+    if (rc != DFX_OK)
+        return rc;
+    const bool resize = sw != c->W || sh != c->H;
+    const size_t row = (size_t)sw * 3, out_pitch = round4((size_t)c->W * 3), out_frame = out_pitch * c->H;
+    const int nb = (n + B - 1) / B;
+    auto upload = [&](int q, int p) -> int {
+        // d_src[p] was last read by the compute of batch q - 2, which this thread has waited for; a tail only reads
+        // the landing buffer
+        const int i0 = q * B, m = std::min(B, n - i0);
+        for (int i = 0; i < m; ++i)
+            HIPCHK(c, hipMemcpy2DAsync(j.d_src[p] + (size_t)i * j.src_frame_bytes, j.src_pitch, frames[i0 + i], pitch, row,
+                                       (size_t)sh, hipMemcpyHostToDevice, c->copy_stream));
+        HIPCHK(c, hipEventRecord(c->ev_h2d[p], c->copy_stream));
+        return DFX_OK;
+    };
+    auto encode = [&](int m, int p) -> int {
+        JpegColourCtx jc;
+        jc.bgr = resize ? j.d_bgr : j.d_src[p];
+        jc.frame_stride = (long long)(resize ? out_frame : j.src_frame_bytes);
+        jc.pitch = (int)(resize ? out_pitch : j.src_pitch);
+        jc.w = c->W, jc.h = c->H, jc.mcus_x = (c->W + 15) / 16, jc.mcus_y = (c->H + 15) / 16;
+        jc.n_planes = m;
+        jc.tab = j.d_tab, jc.dc = j.d_dc, jc.bits = j.d_bits;
+        jc.plane_bits = j.d_plane_bits, jc.plane_base = j.d_plane_base;
+        jc.stream = j.d_stream[p], jc.capacity_bytes = j.capacity;
+        jc.info = j.d_info[p], jc.hdr = j.d_hdr;
+        jpeg_colour_launch_encode(c->stream, jc);
+        HIPCHK(c, hipGetLastError());
+        return DFX_OK;
+    };
+    BatchFiles prev, cur;
+    bool have_prev = false;
+    const unsigned long long seq0 = j.seq;
+    rc = upload(0, (int)(seq0 & 1));
+    if (rc != DFX_OK)
+        return rc;
+    for (int q = 0; q < nb; ++q) {
+        const int p = (int)((seq0 + q) & 1), i0 = q * B, m = std::min(B, n - i0);
+        j.seq = seq0 + q + 1;
+        // the landing buffer and the totals of this parity may still be in use by a deferred tail of an earlier call
+        (void)dfx_finish_tails(c, 0, p);
+        HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_h2d[p], 0));
+        if (resize) {
+            prepare_bgr_launch(c->stream, j.d_src[p], (long long)j.src_pitch, (long long)j.src_frame_bytes, sw, sh, m, j.d_bgr,
+                               (long long)out_pitch, (long long)out_frame, c->W, c->H);
+            HIPCHK(c, hipGetLastError());
+        }
+        if ((rc = encode(m, p)) != DFX_OK)
+            return rc;
+        if (q + 1 < nb && (rc = upload(q + 1, p ^ 1)) != DFX_OK)
+            return rc;
+        if (have_prev) { // host work of batch q - 1 beside the kernels of batch q
+            HIPCHK(c, dfx_stream_wait(c, c->d2h_stream));
+            if ((rc = assemble(c, j.header, j.h_stream[prev.parity], prev, jpg, cap, sizes, nullptr)) != DFX_OK)
+                return rc;
+            have_prev = false;
+        }
+        HIPCHK(c, dfx_stream_wait(c, c->stream));
+        const unsigned long long *hi = j.h_info[p];
+        if (hi[1]) { // more than the stream buffer was sized for: grow it to what the scan pass measured, code again
+            if ((rc = grow_streams(c, hi[0])) != DFX_OK)
+                return rc;
+            if ((rc = encode(m, p)) != DFX_OK)
+                return rc;
+            HIPCHK(c, dfx_stream_wait(c, c->stream));
+            if (hi[1])
+                return dfx_fail(c, DFX_ERR_UNSUPPORTED, "JPEG: the frames do not fit the stream buffer (encode them on the host)");
+        }
+        cur.i0 = i0, cur.n = m, cur.parity = p;
+        cur.bits.resize(m), cur.base.resize(m);
+        for (int i = 0; i < m; ++i) {
+            cur.bits[i] = hi[2 + 2 * i];
+            cur.base[i] = hi[2 + 2 * i + 1];
+        }
+        HIPCHK(c, hipMemcpyAsync(j.h_stream[p], j.d_stream[p], (size_t)hi[0], hipMemcpyDeviceToHost, c->d2h_stream));
+        HIPCHK(c, hipEventRecord(c->ev_d2h[p], c->d2h_stream));
+        prev = cur;
+        have_prev = true;
+    }
+    c->stats.kernel_launches += (uint64_t)nb * (resize ? 6 : 5);
+    if (!have_prev)
+        return DFX_OK;
+    // A frame of the last batch that could exceed jpg_capacity with every byte stuffed is assembled here, synchronously,
+    // so that "does not fit" is this call's DFX_ERR_UNSUPPORTED and never a deferred tail's error.
+    bool may_not_fit = false;
+    for (unsigned long long b : prev.bits)
+        may_not_fit = may_not_fit || j.header.size() + 2 * (size_t)((b >> 3) + 1) + 2 > cap;
+    if (ticket && !may_not_fit) {
+        std::unique_ptr<dfx_context::Tail> t(new dfx_context::Tail());
+        t->ticket = c->next_ticket++;
+        t->parity = prev.parity;
+        dfx_context::Tail *tp = t.get();
+        const BatchFiles last = prev;
+        hipEvent_t ev = c->ev_d2h[prev.parity];
+        const unsigned char *landing = j.h_stream[prev.parity];
+        const std::vector<unsigned char> header = j.header;
+        std::vector<uint8_t *> dst(jpg, jpg + n); // the caller's pointer array need not outlive the submit call
+        const int dev = c->device;
+        std::mutex *mtx = &c->tails_mtx;
+        std::condition_variable *cv = &c->tails_cv;
+        t->worker = std::thread([=]() {
+            (void)hipSetDevice(dev);
+            const hipError_t e = hipEventSynchronize(ev);
+            int wrc = DFX_OK;
+            std::string werr;
+            if (e != hipSuccess) {
+                wrc = DFX_ERR_HIP;
+                werr = std::string("deferred download failed: ") + hipGetErrorString(e);
+            } else {
+                wrc = assemble(nullptr, header, landing, last, dst.data(), cap, sizes, &werr);
+            }
+            {
+                std::lock_guard<std::mutex> lock(*mtx);
+                tp->rc = wrc;
+                tp->err = werr;
+                tp->done = true;
+            }
+            cv->notify_all();
+        });
+        *ticket = t->ticket;
+        std::lock_guard<std::mutex> lock(c->tails_mtx);
+        c->tails.push_back(std::move(t));
+        return DFX_OK;
+    }
+    HIPCHK(c, dfx_stream_wait(c, c->d2h_stream));
+    return assemble(c, j.header, j.h_stream[prev.parity], prev, jpg, cap, sizes, nullptr);
+}
+
+int extract_entry(dfx_handle h, const uint8_t *const *frames, size_t pitch, int sw, int sh, int n, int quality,
+                  uint8_t *const *jpg, size_t cap, uint32_t *sizes, uint64_t *ticket) {
+    if (!h)
+        return DFX_ERR_INVALID;
+    if (ticket)
+        *ticket = 0;
+    else
+        (void)dfx_finish_tails(h, 0, -1);
+    if (n < 0)
+        return dfx_fail(h, DFX_ERR_INVALID, "n must be >= 0");
+    if (n == 0)
+        return DFX_OK;
+    if (!frames || !jpg || !sizes)
+        return dfx_fail(h, DFX_ERR_INVALID, "NULL frame, JPEG buffer or size array");
+    if (sw < 1 || sh < 1 || sw > 32768 || sh > 32768)
+        return dfx_fail(h, DFX_ERR_INVALID, "invalid source frame size");
+    if (pitch < (size_t)sw * 3)
+        return dfx_fail(h, DFX_ERR_INVALID, "pitch smaller than a row");
+    if (quality < 1 || quality > 100)
+        return dfx_fail(h, DFX_ERR_INVALID, "JPEG quality must be 1..100");
+    HIPCHK(h, hipSetDevice(h->device));
+    unsigned long long t = 0;
+    const int rc = extract_body(h, frames, pitch, sw, sh, n, quality, jpg, cap, sizes, ticket ? &t : nullptr);
+    if (rc != DFX_OK) { // copies into caller-owned buffers may be in flight: drain before handing the error back
+        const std::string keep = h->get_err();
+        (void)hipStreamSynchronize(h->copy_stream);
+        (void)hipStreamSynchronize(h->stream);
+        (void)hipStreamSynchronize(h->d2h_stream);
+        (void)dfx_finish_tails(h, 0, -1);
+        h->set_err(keep);
+    } else if (ticket) {
+        *ticket = t;
+    }
+    return rc;
+}
+
+} // namespace
+
+AlgoEngine *dfx_make_frames_engine(dfx_context *c) { return new FramesEngine(c); }
+
+void dfx_free_colour(dfx_context *c) {
+    free_encoder(c);
+    free_staging(c);
+    c->colour.device_bytes = 0;
+}
+
+extern "C" {
+
+int dfx_encode_jpeg_bgr(dfx_handle h, const uint8_t *const *frames, size_t pitch, int n, int quality, uint8_t *const *jpg,
+                        size_t jpg_capacity, uint32_t *sizes) {
+    if (!h)
+        return DFX_ERR_INVALID;
+    return extract_entry(h, frames, pitch, h->W, h->H, n, quality, jpg, jpg_capacity, sizes, nullptr);
+}
+
+int dfx_extract_frames(dfx_handle h, const uint8_t *const *frames, size_t pitch, int src_width, int src_height, int n,
+                       int quality, uint8_t *const *jpg, size_t jpg_capacity, uint32_t *sizes) {
+    return extract_entry(h, frames, pitch, src_width, src_height, n, quality, jpg, jpg_capacity, sizes, nullptr);
+}
+
+int dfx_submit_extract_frames(dfx_handle h, const uint8_t *const *frames, size_t pitch, int src_width, int src_height,
+                              int n, int quality, uint8_t *const *jpg, size_t jpg_capacity, uint32_t *sizes,
+                              uint64_t *ticket) {
+    if (!ticket)
+        return h ? dfx_fail(h, DFX_ERR_INVALID, "ticket is NULL") : DFX_ERR_INVALID;
+    return extract_entry(h, frames, pitch, src_width, src_height, n, quality, jpg, jpg_capacity, sizes, ticket);
+}
+
+size_t dfx_jpeg_capacity_bgr(dfx_handle h) {
+    if (!h)
+        return 0;
+    return (size_t)h->W * h->H * 3 + 4096;
+}
+
+size_t dfx_frames_device_bytes(dfx_handle h) { return h ? h->colour.device_bytes : 0; }
+
+int dfx_prepare_frames_bgr_device(dfx_handle h, const uint8_t *d_src, size_t src_pitch, size_t src_frame_stride,
+                                  int src_width, int src_height, int n, uint8_t *d_dst, size_t dst_pitch,
+                                  size_t dst_frame_stride) {
+    if (!h)
+        return DFX_ERR_INVALID;
+    (void)dfx_finish_tails(h, 0, -1);
+    if (n < 0)
+        return dfx_fail(h, DFX_ERR_INVALID, "n must be >= 0");
+    if (n == 0)
+        return DFX_OK;
+    if (!d_src || !d_dst)
+        return dfx_fail(h, DFX_ERR_INVALID, "NULL device frames");
+    if (src_width < 1 || src_height < 1 || src_width > 32768 || src_height > 32768)
+        return dfx_fail(h, DFX_ERR_INVALID, "invalid source frame size");
+    if (src_pitch < (size_t)src_width * 3 || src_frame_stride < src_pitch * (size_t)src_height ||
+        dst_pitch < (size_t)h->W * 3 || dst_frame_stride < dst_pitch * (size_t)h->H)
+        return dfx_fail(h, DFX_ERR_INVALID, "pitch/stride smaller than a frame");
+    HIPCHK(h, hipSetDevice(h->device));
+    prepare_bgr_launch(h->stream, d_src, (long long)src_pitch, (long long)src_frame_stride, src_width, src_height, n, d_dst,
+                       (long long)dst_pitch, (long long)dst_frame_stride, h->W, h->H);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return DFX_OK;
+}
+
+int dfx_prepare_frames_bgr(dfx_handle h, const uint8_t *const *src, size_t src_pitch, int src_width, int src_height, int n,
+                           uint8_t *const *dst, size_t dst_pitch) {
+    if (!h)
+        return DFX_ERR_INVALID;
+    (void)dfx_finish_tails(h, 0, -1);
+    if (n < 0)
+        return dfx_fail(h, DFX_ERR_INVALID, "n must be >= 0");
+    if (n == 0)
+        return DFX_OK;
+    if (!src || !dst)
+        return dfx_fail(h, DFX_ERR_INVALID, "NULL frame arrays");
+    if (src_width < 1 || src_height < 1 || src_width > 32768 || src_height > 32768)
+        return dfx_fail(h, DFX_ERR_INVALID, "invalid source frame size");
+    const size_t rb = (size_t)src_width * 3, sp = round4(rb), fb = sp * src_height;
+    const size_t ob = (size_t)h->W * 3, op = round4(ob), of = op * h->H;
+    if (src_pitch < rb || dst_pitch < ob)
+        return dfx_fail(h, DFX_ERR_INVALID, "pitch smaller than a row");
+    HIPCHK(h, hipSetDevice(h->device));
+    unsigned char *d_in = nullptr, *d_out = nullptr;
+    const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)n, ((size_t)256 << 20) / std::max(fb, of)));
+    auto run = [&]() -> int {
+        HIPCHK(h, hipMalloc((void **)&d_in, (size_t)chunk * fb));
+        HIPCHK(h, hipMalloc((void **)&d_out, (size_t)chunk * of));
+        for (int i0 = 0; i0 < n; i0 += chunk) {
+            const int m = std::min(chunk, n - i0);
+            for (int i = 0; i < m; ++i)
+                HIPCHK(h, hipMemcpy2DAsync(d_in + (size_t)i * fb, sp, src[i0 + i], src_pitch, rb, (size_t)src_height,
+                                           hipMemcpyHostToDevice, h->stream));
+            prepare_bgr_launch(h->stream, d_in, (long long)sp, (long long)fb, src_width, src_height, m, d_out, (long long)op,
+                               (long long)of, h->W, h->H);
+            HIPCHK(h, hipGetLastError());
+            for (int i = 0; i < m; ++i)
+                HIPCHK(h, hipMemcpy2DAsync(dst[i0 + i], dst_pitch, d_out + (size_t)i * of, op, ob, (size_t)h->H,
+                                           hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(h, hipStreamSynchronize(h->stream));
+        }
+        return DFX_OK;
+    };
+    const int rc = run();
+    dfx_free_dev(d_in);
+    dfx_free_dev(d_out);
+    return rc;
+}
+
+} // extern "C"

@@ -119,6 +119,30 @@ struct dfx_context {
         size_t capacity = 0;
         std::vector<unsigned char> header;
     } jpeg;
+    // colour frame extraction (dfx_frames.cpp: dfx_extract_frames / dfx_encode_jpeg_bgr): the colour encoder's tables and
+    // per-block temporaries (one set, compute stream only); per staging parity the source-size BGR frames, the shared
+    // stream buffer, its page-locked landing buffer and the totals the device reports; the resized frames (one set:
+    // written and read on the compute stream).  Row pitches are multiples of 4 (jpeg_colour_kernels.hip reads dwords).
+    struct ColourState {
+        int quality = 0, frames = 0; // what the encoder buffers are sized for
+        struct JpegTables *d_tab = nullptr; // [2]: luminance, chrominance
+        short *d_dc = nullptr;
+        unsigned *d_bits = nullptr;
+        unsigned long long *d_plane_bits = nullptr, *d_plane_base = nullptr, *d_hdr = nullptr;
+        unsigned *d_stream[2] = {nullptr, nullptr};
+        unsigned char *h_stream[2] = {nullptr, nullptr};
+        size_t h_capacity[2] = {0, 0};
+        unsigned long long *h_info[2] = {nullptr, nullptr}, *d_info[2] = {nullptr, nullptr}; // mapped page-locked
+        size_t capacity = 0;
+        std::vector<unsigned char> header;
+        unsigned char *d_src[2] = {nullptr, nullptr}; // src_slots source-size frames per parity
+        int src_slots = 0;
+        size_t src_pitch = 0, src_frame_bytes = 0;
+        unsigned char *d_bgr = nullptr; // bgr_slots frames of W x H (only when the source size differs)
+        int bgr_slots = 0;
+        unsigned long long seq = 0;   // device batches are numbered across calls: parity = seq & 1
+        size_t device_bytes = 0;      // device memory held by this state
+    } colour;
     DfxHelper helper;              // host-side work beside the calling thread (dfx_helper.h): one thread per handle
     std::vector<int> h_slots;      // slot id of each new frame of the current batch
     std::vector<PairDesc> h_pairs; // descriptors of the current batch
@@ -208,3 +232,5 @@ template <class T> inline void dfx_free_host(T *&p) {
 AlgoEngine *dfx_make_tvl1_engine(dfx_context *c);
 AlgoEngine *dfx_make_farneback_engine(dfx_context *c);
 AlgoEngine *dfx_make_brox_engine(dfx_context *c);
+AlgoEngine *dfx_make_frames_engine(dfx_context *c); // DFX_ALGO_FRAMES: no flow state at all (dfx_frames.cpp)
+void dfx_free_colour(dfx_context *c);               // dfx_destroy: the buffers of dfx_context::colour

@@ -44,6 +44,25 @@ void jpeg_build_tables(int quality, JpegTables &t, unsigned char q_out[64]) {
         t.nat2zig[kDfxJpegZigzag[k]] = (unsigned char)k;
 }
 
+void jpeg_build_colour_tables(int quality, JpegTables t[2]) {
+    unsigned char q[64];
+    jpeg_build_tables(quality, t[0], q);
+    t[1] = t[0]; // nat2zig
+    dfx_jpeg_quantiser_chroma(quality, q);
+    for (int i = 0; i < 64; ++i) {
+        t[1].div[i] = 8u * q[i];
+        t[1].magic[i] = dfx_jpeg_divide_magic(t[1].div[i]);
+    }
+    build_huff(kDfxJpegDcBitsC, kDfxJpegDcVal, t[1].dc_code, t[1].dc_len, 12);
+    build_huff(kDfxJpegAcBitsC, kDfxJpegAcValC, t[1].ac_code, t[1].ac_len, 256);
+}
+
+std::vector<unsigned char> jpeg_colour_file_header(int w, int h, int quality) {
+    unsigned char buf[DFX_JPEG_COLOUR_HEADER_MAX];
+    const int n = dfx_jpeg_colour_header(w, h, quality, buf);
+    return std::vector<unsigned char>(buf, buf + n);
+}
+
 std::vector<unsigned char> jpeg_file_header(int w, int h, const unsigned char q[64]) {
     std::vector<unsigned char> out;
     const unsigned char soi_app0[] = {0xFF, 0xD8, 0xFF, 0xE0, 0, 16, 'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0};

@@ -46,8 +46,32 @@ struct JpegCtx {
 // Enqueue the whole encode of a batch on stream s: count pass, scans, layout, zero-fill, emit pass.
 void jpeg_launch_encode(hipStream_t s, const JpegCtx &c);
 
+// The colour form (jpeg_colour_kernels.hip): n_planes BGR frames -> one YCbCr 4:2:0 interleaved stream each, what
+// cv::imencode(".jpg", bgr) codes (reference src/denseflow_gpu.cpp:82-105, the -s=0 mode).  A frame's blocks are numbered
+// in MCU order (Y00 Y01 Y10 Y11 Cb Cr per 16 x 16 MCU, MCUs row-major); the other fields mean what they mean in JpegCtx,
+// with "plane" = frame.  The rows are read as dwords: the first frame is 4-byte aligned, pitch and frame_stride are
+// multiples of 4.
+struct JpegColourCtx {
+    const unsigned char *bgr; // frame f: bgr + f * frame_stride, rows of w interleaved B G R pixels, pitch bytes apart
+    long long frame_stride;
+    int pitch, w, h, mcus_x, mcus_y;
+    int n_planes;
+    const JpegTables *tab; // [0] luminance, [1] chrominance
+    short *dc;             // [n_planes][mcus_x * mcus_y * 6]
+    unsigned *bits;
+    unsigned long long *plane_bits, *plane_base;
+    unsigned *stream;
+    unsigned long long capacity_bytes;
+    unsigned long long *info, *hdr;
+};
+void jpeg_colour_launch_encode(hipStream_t s, const JpegColourCtx &c);
+
 // ---- host side (jpeg_host.cpp) ---------------------------------------------------------------------------------------
 void jpeg_build_tables(int quality, JpegTables &t, unsigned char q_out[64]);
+// The table pair of a colour file: t[0] luminance (the gray encoder's), t[1] chrominance (Annex K.2 / K.3.3 tables 2).
+void jpeg_build_colour_tables(int quality, JpegTables t[2]);
+// The file header up to and including SOS of a w x h colour image (include/dfx_jpeg_tables.h: dfx_jpeg_colour_header).
+std::vector<unsigned char> jpeg_colour_file_header(int w, int h, int quality);
 // The file header up to and including SOS for a w x h gray image with quantiser q (what imencodeJpeg writes).
 std::vector<unsigned char> jpeg_file_header(int w, int h, const unsigned char q[64]);
 // header + byte-stuffed entropy-coded segment (`bits` bits at src, last byte padded with ones) + EOI into dst.

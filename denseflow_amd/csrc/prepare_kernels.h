@@ -10,3 +10,9 @@ int prepare_mode(int sw, int sh, int dw, int dh);
 void prepare_launch(hipStream_t s, const unsigned char *d_src, long long src_pitch, long long src_frame_stride, int sw,
                     int sh, int channels, int n, unsigned char *d_dst, long long dst_pitch, long long dst_frame_stride,
                     int dw, int dh);
+
+// n BGR frames (sw x sh, interleaved) -> n BGR frames of dw x dh: cv::resize(INTER_LINEAR) of every channel on its own.
+// The buffers are device allocations (their first byte 4-byte aligned): rows are read as aligned dwords.
+void prepare_bgr_launch(hipStream_t s, const unsigned char *d_src, long long src_pitch, long long src_frame_stride, int sw,
+                        int sh, int n, unsigned char *d_dst, long long dst_pitch, long long dst_frame_stride, int dw,
+                        int dh);

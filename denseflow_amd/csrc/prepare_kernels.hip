@@ -83,6 +83,79 @@ __global__ __launch_bounds__(256) void k_prepare_frames(const unsigned char *src
     D[(long long)dy * dst_pitch + dx] = (unsigned char)out;
 }
 
+// ---- the 3-channel form: cv::resize(bgr, resized, size) of the reference's colour frame extraction
+// (/root/reference/src/denseflow_gpu.cpp:82-105, -s=0).  cv::resize treats the channels independently, so every channel
+// goes through exactly the arithmetic above.  A row of interleaved BGR is 3 bytes per pixel: a pixel is fetched as the
+// aligned dword(s) that hold it (one, or two when it straddles a dword boundary), not byte by byte.  The first dword
+// always contains a byte of the pixel and the second is only touched when the pixel reaches into it, so no load leaves
+// the row's own dwords.  One thread produces four destination pixels = 12 bytes, stored as three dwords where the
+// destination row allows it.
+__device__ __forceinline__ unsigned load_bgr(const unsigned char *row, int x) {
+    const unsigned long long a = (unsigned long long)(row + 3 * (long long)x);
+    const unsigned *p = reinterpret_cast<const unsigned *>(a & ~3ull);
+    const unsigned sh = (unsigned)(a & 3ull) * 8u;
+    unsigned v = p[0] >> sh;
+    if (sh > 8u)
+        v |= p[1] << (32u - sh);
+    return v & 0xFFFFFFu;
+}
+
+__global__ __launch_bounds__(256) void k_prepare_bgr(const unsigned char *src, long long src_pitch, long long src_frame_stride,
+                                                      int sw, int sh, unsigned char *dst, long long dst_pitch,
+                                                      long long dst_frame_stride, int dw, int dh, double scale_x,
+                                                      double scale_y, int mode) {
+    const int gx = blockIdx.x * 64 + (threadIdx.x & 63); // group of four destination pixels
+    const int dy = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (gx * 4 >= dw || dy >= dh)
+        return;
+    const unsigned char *S = src + (long long)blockIdx.z * src_frame_stride;
+    unsigned char *D = dst + (long long)blockIdx.z * dst_frame_stride + (long long)dy * dst_pitch + 12ll * gx;
+    unsigned out[4] = {0u, 0u, 0u, 0u}; // packed B | G << 8 | R << 16
+    int sy0 = 0, sy1 = 0, b0 = 0, b1 = 0;
+    if (mode == 2)
+        linear_coeff_y(dy, scale_y, sh, sy0, sy1, b0, b1);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int dx = gx * 4 + i;
+        if (dx >= dw)
+            break;
+        if (mode == 0) {
+            out[i] = load_bgr(S + (long long)dy * src_pitch, dx);
+        } else if (mode == 1) {
+            const unsigned char *r0 = S + (long long)(2 * dy) * src_pitch, *r1 = r0 + src_pitch;
+            const unsigned p00 = load_bgr(r0, 2 * dx), p01 = load_bgr(r0, 2 * dx + 1), p10 = load_bgr(r1, 2 * dx),
+                           p11 = load_bgr(r1, 2 * dx + 1);
+#pragma unroll
+            for (int c = 0; c < 24; c += 8)
+                out[i] |= ((((p00 >> c) & 255u) + ((p01 >> c) & 255u) + ((p10 >> c) & 255u) + ((p11 >> c) & 255u) + 2u) >> 2) << c;
+        } else {
+            int sx, a0, a1;
+            linear_coeff_x(dx, scale_x, sw, sx, a0, a1);
+            const int sx1 = min(sx + 1, sw - 1); // weight 0 whenever this clamps
+            const unsigned char *r0 = S + (long long)sy0 * src_pitch, *r1 = S + (long long)sy1 * src_pitch;
+            const unsigned p00 = load_bgr(r0, sx), p01 = load_bgr(r0, sx1), p10 = load_bgr(r1, sx), p11 = load_bgr(r1, sx1);
+#pragma unroll
+            for (int c = 0; c < 24; c += 8) {
+                const int h0 = (int)((p00 >> c) & 255u) * a0 + (int)((p01 >> c) & 255u) * a1; // HResizeLinear, int
+                const int h1 = (int)((p10 >> c) & 255u) * a0 + (int)((p11 >> c) & 255u) * a1;
+                out[i] |= (unsigned)((((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2) >> 2) << c;
+            }
+        }
+    }
+    if (gx * 4 + 4 <= dw && ((unsigned long long)D & 3ull) == 0) {
+        unsigned *W = reinterpret_cast<unsigned *>(D);
+        W[0] = out[0] | (out[1] << 24);
+        W[1] = (out[1] >> 8) | (out[2] << 16);
+        W[2] = (out[2] >> 16) | (out[3] << 8);
+    } else {
+        for (int i = 0; i < 4 && gx * 4 + i < dw; ++i) {
+            D[3 * i] = (unsigned char)out[i];
+            D[3 * i + 1] = (unsigned char)(out[i] >> 8);
+            D[3 * i + 2] = (unsigned char)(out[i] >> 16);
+        }
+    }
+}
+
 } // namespace
 
 int prepare_mode(int sw, int sh, int dw, int dh) {
@@ -103,4 +176,15 @@ void prepare_launch(hipStream_t s, const unsigned char *d_src, long long src_pit
     const dim3 grid((dw + 63) / 64, (dh + 3) / 4, n);
     hipLaunchKernelGGL(k_prepare_frames, grid, dim3(256), 0, s, d_src, src_pitch, src_frame_stride, sw, sh, channels,
                        d_dst, dst_pitch, dst_frame_stride, dw, dh, scale_x, scale_y, prepare_mode(sw, sh, dw, dh));
+}
+
+void prepare_bgr_launch(hipStream_t s, const unsigned char *d_src, long long src_pitch, long long src_frame_stride, int sw,
+                        int sh, int n, unsigned char *d_dst, long long dst_pitch, long long dst_frame_stride, int dw,
+                        int dh) {
+    if (n <= 0)
+        return;
+    const double scale_x = 1.0 / ((double)dw / (double)sw), scale_y = 1.0 / ((double)dh / (double)sh);
+    const dim3 grid(((dw + 3) / 4 + 63) / 64, (dh + 3) / 4, n);
+    hipLaunchKernelGGL(k_prepare_bgr, grid, dim3(256), 0, s, d_src, src_pitch, src_frame_stride, sw, sh, d_dst, dst_pitch,
+                       dst_frame_stride, dw, dh, scale_x, scale_y, prepare_mode(sw, sh, dw, dh));
 }

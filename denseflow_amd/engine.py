@@ -23,7 +23,7 @@ _CSRC = os.path.join(_HERE, "csrc")
 DFX_MAX_LEVELS = 32
 DFX_MAX_WARPS = 16
 
-ALGO_TVL1, ALGO_FARN, ALGO_BROX = 0, 1, 2
+ALGO_TVL1, ALGO_FARN, ALGO_BROX, ALGO_FRAMES = 0, 1, 2, 3
 OK, ERR_INVALID, ERR_NO_DEVICE, ERR_HIP, ERR_UNSUPPORTED, ERR_NV_DISABLED, ERR_UNKNOWN_ALGO = range(7)
 
 
@@ -211,6 +211,21 @@ def load_library():
     L.dfx_prepare_frames.restype = i
     L.dfx_prepare_frames_device.argtypes = [vp, vp, sz, sz, i, i, i, i, vp, sz, sz]
     L.dfx_prepare_frames_device.restype = i
+    L.dfx_prepare_frames_bgr.argtypes = [vp, C.POINTER(vp), sz, i, i, i, C.POINTER(vp), sz]
+    L.dfx_prepare_frames_bgr.restype = i
+    L.dfx_prepare_frames_bgr_device.argtypes = [vp, vp, sz, sz, i, i, i, vp, sz, sz]
+    L.dfx_prepare_frames_bgr_device.restype = i
+    L.dfx_encode_jpeg_bgr.argtypes = [vp, C.POINTER(vp), sz, i, i, C.POINTER(vp), sz, u32p]
+    L.dfx_encode_jpeg_bgr.restype = i
+    L.dfx_jpeg_capacity_bgr.argtypes = [vp]
+    L.dfx_jpeg_capacity_bgr.restype = sz
+    L.dfx_extract_frames.argtypes = [vp, C.POINTER(vp), sz, i, i, i, i, C.POINTER(vp), sz, u32p]
+    L.dfx_extract_frames.restype = i
+    L.dfx_submit_extract_frames.argtypes = [vp, C.POINTER(vp), sz, i, i, i, i, C.POINTER(vp), sz, u32p,
+                                            C.POINTER(C.c_uint64)]
+    L.dfx_submit_extract_frames.restype = i
+    L.dfx_frames_device_bytes.argtypes = [vp]
+    L.dfx_frames_device_bytes.restype = sz
     L.dfx_get_stats.argtypes = [vp, C.POINTER(DfxStats)]
     L.dfx_get_stats.restype = i
     L.dfx_reset_stats.argtypes = [vp]
@@ -267,7 +282,8 @@ class FlowEngine:
         self._h = C.c_void_p()
         self.width, self.height = int(width), int(height)
         self.algorithm = algorithm
-        algo = algo_from_name(algorithm)
+        # "frames": a handle without flow state, for the colour frame extraction (no -a=<name> maps to it)
+        algo = ALGO_FRAMES if algorithm == "frames" else algo_from_name(algorithm)
         if knobs:
             if params is None:
                 params = default_params()
@@ -544,6 +560,64 @@ class FlowEngine:
         self._check(self._L.dfx_encode_jpeg(self._h, (C.c_void_p * n)(*[p.ctypes.data for p in ps]), self.width, n,
                                             int(quality), (C.c_void_p * n)(*[b.ctypes.data for b in bufs]), cap, sizes))
         return [bufs[i][:sizes[i]].tobytes() for i in range(n)]
+
+    # -- colour frame extraction (reference: extract_frames_only, src/denseflow_gpu.cpp:82-105) ------------
+    def _bgr(self, frames):
+        fs = [np.ascontiguousarray(f, dtype=np.uint8) for f in frames]
+        if fs and (any(f.shape != fs[0].shape for f in fs) or len(fs[0].shape) != 3 or fs[0].shape[2] != 3):
+            raise ValueError("frames must share one (h, w, 3) shape")
+        return fs
+
+    def prepare_frames_bgr(self, frames):
+        """cv::resize(INTER_LINEAR) of (h, w, 3) uint8 BGR frames to the engine's size, every channel on its own."""
+        src = self._bgr(frames)
+        n = len(src)
+        out = [np.empty((self.height, self.width, 3), np.uint8) for _ in range(n)]
+        if n == 0:
+            return out
+        sh, sw = src[0].shape[:2]
+        sp = (C.c_void_p * n)(*[f.ctypes.data for f in src])
+        op = (C.c_void_p * n)(*[f.ctypes.data for f in out])
+        self._check(self._L.dfx_prepare_frames_bgr(self._h, sp, sw * 3, sw, sh, n, op, self.width * 3))
+        return out
+
+    def prepare_frames_bgr_device(self, d_src_ptr: int, src_pitch: int, src_frame_stride: int, src_width: int,
+                                  src_height: int, n: int, d_dst_ptr: int, dst_pitch: int, dst_frame_stride: int):
+        self._check(self._L.dfx_prepare_frames_bgr_device(self._h, d_src_ptr, src_pitch, src_frame_stride, int(src_width),
+                                                          int(src_height), int(n), d_dst_ptr, dst_pitch, dst_frame_stride))
+
+    def encode_jpeg_bgr(self, frames, quality: int = 95):
+        """imencode(".jpg", bgr) of (H, W, 3) uint8 BGR frames on the device (YCbCr 4:2:0): a list of `bytes`."""
+        fs = self._bgr(frames)
+        if fs and fs[0].shape[:2] != (self.height, self.width):
+            raise ValueError("frame shape does not match the engine")
+        return self.extract_frames(fs, quality)
+
+    def extract_frames(self, frames, quality: int = 95, submit: bool = False):
+        """The -s=0 mode for one buffer of (h, w, 3) uint8 BGR source frames: resize to the engine's size and encode,
+        all on the device.  Returns a list of `bytes`.  submit=True goes through dfx_submit_extract_frames + dfx_wait."""
+        fs = self._bgr(frames)
+        n = len(fs)
+        if n == 0:
+            return []
+        sh, sw = fs[0].shape[:2]
+        cap = int(self._L.dfx_jpeg_capacity_bgr(self._h))
+        bufs = [np.empty(cap, np.uint8) for _ in range(n)]
+        sizes = (C.c_uint32 * n)()
+        fp = (C.c_void_p * n)(*[f.ctypes.data for f in fs])
+        bp = (C.c_void_p * n)(*[b.ctypes.data for b in bufs])
+        if submit:
+            t = C.c_uint64(0)
+            self._check(self._L.dfx_submit_extract_frames(self._h, fp, sw * 3, sw, sh, n, int(quality), bp, cap, sizes,
+                                                          C.byref(t)))
+            self._check(self._L.dfx_wait(self._h, t.value))
+        else:
+            self._check(self._L.dfx_extract_frames(self._h, fp, sw * 3, sw, sh, n, int(quality), bp, cap, sizes))
+        return [bufs[i][:sizes[i]].tobytes() for i in range(n)]
+
+    def frames_device_bytes(self) -> int:
+        """Device memory held by the colour extraction state of this handle."""
+        return int(self._L.dfx_frames_device_bytes(self._h))
 
     def calc_optflows_u8_device(self, d_frames_ptr: int, pitch: int, frame_stride: int, n_frames: int, step: int,
                                 lower: float, upper: float, d_img_x_ptr: int, d_img_y_ptr: int, img_pitch: int,

@@ -183,6 +183,8 @@ class DenseFlow {
     void encode_save(string save_type, bool verbose = true);
     int extract_frames_video(VideoCapture &video_stream, vector<path> &frames_path, bool use_frames, bool do_resize,
                              const Size &size, path output_dir, bool verbose);
+    // -s=0 of a colour source (a folder of .ppm frames): BGR frames, resize + JPEG on the device (dfx_extract_frames)
+    int extract_frames_colour(vector<path> &frames_path, bool do_resize, const Size &size, path output_dir);
     friend struct DenseFlowTestAccess;
 
   public:

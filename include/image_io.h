@@ -27,9 +27,11 @@ class VideoCapture {
 };
 
 bool imreadGray(const string &file, Mat &gray);          // .pgm (P5) / .ppm (P6, BGR2GRAY fixed-point weights)
-void resizeLinear(const Mat &src, Mat &dst, Size size);  // bilinear, half-pixel centres (cv::resize default)
+bool imreadColor(const string &file, Mat &bgr);          // .ppm (P6) -> BGR, as cv::imread; false for anything else
+void resizeLinear(const Mat &src, Mat &dst, Size size);  // bilinear, half-pixel centres (cv::resize default), 1 or 3 channels
 
-bool imencodeJpeg(const Mat &gray, vector<uchar> &out, int quality = 95); // baseline, 8-bit gray
+// baseline JPEG: 8-bit gray (one component), or BGR as YCbCr 4:2:0 — what cv::imencode(".jpg") writes for either
+bool imencodeJpeg(const Mat &img, vector<uchar> &out, int quality = 95);
 void imencodeJpegForcePortable(bool on); // testing aid: bypass the AVX2 transform
 bool imencodePng(const Mat &img, vector<uchar> &out);                     // 8-bit gray or BGR, stored deflate
 

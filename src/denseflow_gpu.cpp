@@ -892,15 +892,121 @@ int DenseFlow::extract_frames_video(VideoCapture &video_stream, vector<path> &fr
     return video_frame_idx;
 }
 
+// The colour entry points of libdfx are resolved weakly: a build of this shell against an ABI without them (the CPU
+// pipeline tests' fake) still links, and the mode then runs on the host twins (resizeLinear, imencodeJpeg).
+#pragma weak dfx_submit_extract_frames
+#pragma weak dfx_prepare_frames_bgr
+#pragma weak dfx_jpeg_capacity_bgr
+
+// Colour frame extraction (reference :82-105 for a BGR source): buffers of frames go through one DFX_ALGO_FRAMES handle
+// per output size — resize and JPEG on the device, one submission per buffer — and the next buffer is read while the
+// device works.  DF_HOST_RESIZE / DF_HOST_JPEG move either stage to its host twin, as for the flow outputs; both
+// together need no device at all.
+int DenseFlow::extract_frames_colour(vector<path> &frames_path, bool do_resize, const Size &size, path output_dir) {
+    const bool have_abi = dfx_submit_extract_frames && dfx_prepare_frames_bgr && dfx_jpeg_capacity_bgr;
+    const bool host_resize = !have_abi || !device_resize, host_jpeg = !have_abi || std::getenv("DF_HOST_JPEG");
+    const bool need_device = !host_jpeg || (do_resize && !host_resize);
+    if (need_device && (!dfx_ || dfx_size_.width != size.width || dfx_size_.height != size.height)) {
+        if (dfx_)
+            dfx_destroy(dfx_);
+        dfx_ = nullptr;
+        const int rc = dfx_create(&dfx_, device, DFX_ALGO_FRAMES, size.width, size.height, nullptr);
+        if (rc != DFX_OK)
+            throw std::runtime_error(string("dfx_create failed: ") + dfx_last_error(nullptr));
+        dfx_size_ = size;
+    }
+    const size_t frame_bytes = (size_t)src_w_ * src_h_ * 3;
+    const int per_buffer = (int)std::max<size_t>(1, std::min<size_t>((size_t)batch_maxsize, ((size_t)256 << 20) / frame_bytes));
+    auto read_buffer = [&](vector<Mat> &frames) {
+        frames.clear();
+        while ((int)frames.size() < per_buffer && !frames_path.empty()) {
+            Mat f;
+            if (!imreadColor(frames_path.front().string(), f) || f.cols != src_w_ || f.rows != src_h_)
+                throw std::runtime_error("cannot read frame " + frames_path.front().string());
+            frames_path.erase(frames_path.begin());
+            if (do_resize && host_resize) {
+                Mat r;
+                resizeLinear(f, r, size);
+                f = r;
+            }
+            frames.push_back(f);
+        }
+    };
+    struct InFlight {
+        uint64_t ticket = 0;
+        vector<vector<uchar>> files;
+        vector<uint32_t> sizes;
+        int n = 0;
+    };
+    auto submit = [&](vector<Mat> &frames, InFlight &fl) {
+        const int n = (int)frames.size();
+        fl.n = n;
+        fl.files.assign(n, vector<uchar>());
+        fl.sizes.assign(n, 0);
+        fl.ticket = 0;
+        if (host_jpeg) {
+            if (do_resize && !host_resize) { // the device resizes, the host encodes
+                vector<const uint8_t *> src(n);
+                vector<uint8_t *> dst(n);
+                vector<Mat> resized(n);
+                for (int i = 0; i < n; ++i) {
+                    resized[i].create(size, CV_8UC3);
+                    src[i] = frames[i].data();
+                    dst[i] = resized[i].data();
+                }
+                if (dfx_prepare_frames_bgr(dfx_, src.data(), frames[0].step, src_w_, src_h_, n, dst.data(), resized[0].step) != DFX_OK)
+                    throw std::runtime_error(string("dfx_prepare_frames_bgr failed: ") + dfx_last_error(dfx_));
+                frames = resized;
+            }
+            parallelFor(n, encode_threads, [&](int i) { imencodeJpeg(frames[i], fl.files[i]); });
+            return;
+        }
+        const size_t cap = dfx_jpeg_capacity_bgr(dfx_);
+        vector<const uint8_t *> src(n);
+        vector<uint8_t *> dst(n);
+        for (int i = 0; i < n; ++i) {
+            fl.files[i].resize(cap);
+            src[i] = frames[i].data();
+            dst[i] = fl.files[i].data();
+        }
+        if (dfx_submit_extract_frames(dfx_, src.data(), frames[0].step, frames[0].cols, frames[0].rows, n, 95, dst.data(), cap,
+                                      fl.sizes.data(), &fl.ticket) != DFX_OK)
+            throw std::runtime_error(string("dfx_submit_extract_frames failed: ") + dfx_last_error(dfx_));
+    };
+    int video_frame_idx = 0;
+    auto collect = [&](InFlight &fl) {
+        if (!host_jpeg) {
+            if (dfx_wait(dfx_, fl.ticket) != DFX_OK)
+                throw std::runtime_error(string("dfx_wait failed: ") + dfx_last_error(dfx_));
+            for (int i = 0; i < fl.n; ++i)
+                fl.files[i].resize(fl.sizes[i]);
+        }
+        writeImages(std::move(fl.files), (output_dir / "img").string(), video_frame_idx);
+        video_frame_idx += fl.n;
+    };
+    vector<Mat> frames;
+    InFlight fl;
+    read_buffer(frames);
+    while (!frames.empty()) {
+        submit(frames, fl); // the frames have been consumed when this returns
+        read_buffer(frames); // the next buffer, while the last device batch of this one finishes
+        collect(fl);
+    }
+    return video_frame_idx;
+}
+
 void DenseFlow::extract_frames_only(bool use_frames, bool verbose) {
-    // Deliberate limitation, stated loudly: the reference's -s=0 mode writes COLOUR frames (it reads BGR,
-    // src/denseflow_gpu.cpp:100-117); this decoder-free build has a gray-only JPEG encoder and reads the Y plane of
-    // .y4m clips / converts .ppm to gray, so the extracted img_%05d.jpg are single-channel.
+    // The reference's -s=0 mode writes COLOUR frames (it reads BGR, src/denseflow_gpu.cpp:100-117).  A colour source — a
+    // folder of .ppm frames — is extracted in colour (extract_frames_colour).  Stated loudly for the others: this
+    // decoder-free build reads the Y plane of .y4m clips (the BGR of a clip with chroma would be swscale's conversion in
+    // the reference, which nothing here can pin) and .pgm frames, and their img_%05d.jpg are single-channel.
     static std::once_flag warned;
-    std::call_once(warned, [] {
-        cout << "note: -s=0 in this build writes GRAY frames (Y plane / BGR2GRAY); the reference writes colour frames"
-             << endl;
-    });
+    auto warn_gray = [] {
+        std::call_once(warned, [] {
+            cout << "note: -s=0 in this build writes GRAY frames (Y plane / BGR2GRAY); the reference writes colour frames"
+                 << endl;
+        });
+    };
     for (size_t i = 0; i < video_paths.size(); i++) {
         VideoCapture video_stream;
         vector<path> frames_path;
@@ -917,7 +1023,13 @@ void DenseFlow::extract_frames_only(bool use_frames, bool verbose) {
         Size size;
         int frames_num;
         const bool do_resize = get_new_size(video_stream, frames_path, use_frames, size, frames_num);
-        frames_num = extract_frames_video(video_stream, frames_path, use_frames, do_resize, size, output_dirs[i], verbose);
+        Mat probe;
+        if (use_frames && imreadColor(frames_path[0].string(), probe)) {
+            frames_num = extract_frames_colour(frames_path, do_resize, size, output_dirs[i]);
+        } else {
+            warn_gray();
+            frames_num = extract_frames_video(video_stream, frames_path, use_frames, do_resize, size, output_dirs[i], verbose);
+        }
         total_frames += frames_num;
         if (verbose)
             cout << "extracted frames of video " << video_paths[i] << ", " << frames_num << " frames" << endl;

@@ -135,17 +135,42 @@ bool imreadGray(const string &file, Mat &gray) {
     return true;
 }
 
-// cv::resize(src, dst, size) for CV_8UC1 with the default INTER_LINEAR, in OpenCV's 8-bit integer arithmetic
+// A .ppm (P6) frame as the BGR image cv::imread gives (reference src/denseflow_gpu.cpp:100-117 reads colour frames for
+// -s=0).  false for anything else, a .pgm included: a gray source stays on the gray path.
+bool imreadColor(const string &file, Mat &bgr) {
+    FILE *fp = fopen(file.c_str(), "rb");
+    if (!fp)
+        return false;
+    std::shared_ptr<FILE> guard(fp, fclose);
+    char magic[3] = {0, 0, 0};
+    if (fread(magic, 1, 2, fp) != 2 || magic[0] != 'P' || magic[1] != '6')
+        return false;
+    int w, h, maxv;
+    if (!pnm_token(fp, w) || !pnm_token(fp, h) || !pnm_token(fp, maxv) || maxv != 255 || w <= 0 || h <= 0 || w > 32768 ||
+        h > 32768)
+        return false;
+    bgr.create(Size(w, h), CV_8UC3);
+    uchar *d = bgr.data();
+    const size_t n = (size_t)w * h;
+    if (fread(d, 1, n * 3, fp) != n * 3)
+        return false;
+    for (size_t i = 0; i < n; ++i)
+        std::swap(d[3 * i], d[3 * i + 2]);
+    return true;
+}
+
+// cv::resize(src, dst, size) for CV_8UC1 / CV_8UC3 (every channel on its own, as cv::resize does) with the default INTER_LINEAR, in OpenCV's 8-bit integer arithmetic
 // (the same arithmetic as the device path, denseflow_amd/csrc/prepare_kernels.hip): source coordinate
 // (float)((d + 0.5)*scale - 0.5); 11-bit fixed-point weights; along x an out-of-range index is clamped and its
 // fraction zeroed, along y the two row indices are clamped; an exact 2x2 decimation is a rounded 2x2 mean
 // (cv::resize executes that INTER_LINEAR request as INTER_AREA).
 void resizeLinear(const Mat &src, Mat &dst, Size size) {
-    dst.create(size, CV_8UC1);
+    const int cn = src.channels();
+    dst.create(size, src.type());
     const int sw = src.cols, sh = src.rows, dw = size.width, dh = size.height;
     if (sw == dw && sh == dh) {
         for (int y = 0; y < dh; ++y)
-            std::memcpy(dst.ptr<uchar>(y), src.ptr<uchar>(y), dw);
+            std::memcpy(dst.ptr<uchar>(y), src.ptr<uchar>(y), (size_t)dw * cn);
         return;
     }
     if (sw == 2 * dw && sh == 2 * dh) {
@@ -153,7 +178,9 @@ void resizeLinear(const Mat &src, Mat &dst, Size size) {
             const uchar *r0 = src.ptr<uchar>(2 * y), *r1 = src.ptr<uchar>(2 * y + 1);
             uchar *d = dst.ptr<uchar>(y);
             for (int x = 0; x < dw; ++x)
-                d[x] = (uchar)((r0[2 * x] + r0[2 * x + 1] + r1[2 * x] + r1[2 * x + 1] + 2) >> 2);
+                for (int c = 0; c < cn; ++c)
+                    d[x * cn + c] = (uchar)((r0[2 * x * cn + c] + r0[(2 * x + 1) * cn + c] + r1[2 * x * cn + c] +
+                                             r1[(2 * x + 1) * cn + c] + 2) >> 2);
         }
         return;
     }
@@ -180,9 +207,11 @@ void resizeLinear(const Mat &src, Mat &dst, Size size) {
         const uchar *r1 = src.ptr<uchar>(std::min(std::max(s + 1, 0), sh - 1));
         uchar *d = dst.ptr<uchar>(y);
         for (int x = 0; x < dw; ++x) {
-            const int x0 = xo[x], x1 = std::min(x0 + 1, sw - 1);
-            const int h0 = r0[x0] * a0[x] + r0[x1] * a1[x], h1 = r1[x0] * a0[x] + r1[x1] * a1[x];
-            d[x] = (uchar)((((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2) >> 2);
+            const int x0 = xo[x] * cn, x1 = std::min(xo[x] + 1, sw - 1) * cn;
+            for (int c = 0; c < cn; ++c) {
+                const int h0 = r0[x0 + c] * a0[x] + r0[x1 + c] * a1[x], h1 = r1[x0 + c] * a0[x] + r1[x1 + c] * a1[x];
+                d[x * cn + c] = (uchar)((((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2) >> 2);
+            }
         }
     }
 }
@@ -330,11 +359,65 @@ inline void fdct_quant(const uchar *src, size_t pitch, int valid_w, int valid_h,
 
 inline int bit_length(int a) { return a ? 32 - __builtin_clz((unsigned)a) : 0; }
 
+struct CodeTables {
+    HuffTable dc, ac, dc_c, ac_c; // Annex K luminance pair, chrominance pair
+    uchar nat2zig[64];            // position of natural-order coefficient i in the zig-zag scan
+    CodeTables() {
+        dc.build(kDcBits, kDcVal);
+        ac.build(kAcBits, kAcVal);
+        dc_c.build(kDfxJpegDcBitsC, kDcVal);
+        ac_c.build(kDfxJpegAcBitsC, kDfxJpegAcValC);
+        for (int k = 0; k < 64; ++k)
+            nat2zig[kZigzag[k]] = (uchar)k;
+    }
+};
+
+// Huffman coding of one quantised block (natural order): DC difference against the component's predictor, AC run lengths.
+inline void put_block(BitWriter &bw, const int *coef, int &prev_dc, const HuffTable &dc, const HuffTable &ac,
+                      const uchar *nat2zig) {
+    const int diff = coef[0] - prev_dc;
+    prev_dc = coef[0];
+    const int nb = bit_length(diff < 0 ? -diff : diff);
+    bw.put(dc.code[nb], dc.len[nb]);
+    if (nb)
+        bw.put((unsigned)(diff < 0 ? diff - 1 : diff), nb);
+    // AC run lengths over the zig-zag scan: visit only the non-zero coefficients
+    unsigned long long nz = 0; // bit k: zig-zag position k holds a non-zero coefficient
+    for (int i = 1; i < 64; ++i)
+        nz |= (unsigned long long)(coef[i] != 0) << nat2zig[i];
+    int last = 0;
+    while (nz) {
+        const int k = __builtin_ctzll(nz);
+        nz &= nz - 1;
+        int run = k - last - 1;
+        last = k;
+        while (run > 15) {
+            bw.put(ac.code[0xF0], ac.len[0xF0]);
+            run -= 16;
+        }
+        const int v = coef[kZigzag[k]];
+        const int n = bit_length(v < 0 ? -v : v);
+        const int sym = (run << 4) | n;
+        bw.put(((unsigned)ac.code[sym] << n) | ((unsigned)(v < 0 ? v - 1 : v) & ((1u << n) - 1)), ac.len[sym] + n);
+    }
+    if (last != 63)
+        bw.put(ac.code[0x00], ac.len[0x00]);
+}
+
+const CodeTables &code_tables() {
+    static const CodeTables T; // thread-safe one-time initialisation: encoders run in parallel
+    return T;
+}
+
+bool imencodeJpegColour(const Mat &bgr, vector<uchar> &out, int quality);
+
 } // namespace
 
 void imencodeJpegForcePortable(bool on) { g_force_portable = on; }
 
 bool imencodeJpeg(const Mat &gray, vector<uchar> &out, int quality) {
+    if (!gray.empty() && gray.type() == CV_8UC3)
+        return imencodeJpegColour(gray, out, quality);
     if (gray.empty() || gray.type() != CV_8UC1)
         return false;
     uchar q[64];
@@ -344,17 +427,7 @@ bool imencodeJpeg(const Mat &gray, vector<uchar> &out, int quality) {
         Q.div[i] = 8u * q[i];
         Q.magic[i] = dfx_jpeg_divide_magic(Q.div[i]);
     }
-    struct Tables {
-        HuffTable dc, ac;
-        uchar nat2zig[64];  // position of natural-order coefficient i in the zig-zag scan
-        Tables() {
-            dc.build(kDcBits, kDcVal);
-            ac.build(kAcBits, kAcVal);
-            for (int k = 0; k < 64; ++k)
-                nat2zig[kZigzag[k]] = (uchar)k;
-        }
-    };
-    static const Tables T; // thread-safe one-time initialisation: encoders run in parallel
+    const CodeTables &T = code_tables();
     const HuffTable &dc = T.dc, &ac = T.ac;
     const int W = gray.cols, H = gray.rows;
     out.clear();
@@ -384,34 +457,7 @@ bool imencodeJpeg(const Mat &gray, vector<uchar> &out, int quality) {
         for (int bx = 0; bx < W; bx += 8) {
             alignas(32) int coef[64];
             fdct_quant(gray.ptr<uchar>(by) + bx, gray.step, W - bx, H - by, Q, coef);
-            // DC difference
-            const int diff = coef[0] - prev_dc;
-            prev_dc = coef[0];
-            const int nb = bit_length(diff < 0 ? -diff : diff);
-            bw.put(dc.code[nb], dc.len[nb]);
-            if (nb)
-                bw.put((unsigned)(diff < 0 ? diff - 1 : diff), nb);
-            // AC run lengths over the zig-zag scan: visit only the non-zero coefficients
-            unsigned long long nz = 0; // bit k: zig-zag position k holds a non-zero coefficient
-            for (int i = 1; i < 64; ++i)
-                nz |= (unsigned long long)(coef[i] != 0) << T.nat2zig[i];
-            int last = 0;
-            while (nz) {
-                const int k = __builtin_ctzll(nz);
-                nz &= nz - 1;
-                int run = k - last - 1;
-                last = k;
-                while (run > 15) {
-                    bw.put(ac.code[0xF0], ac.len[0xF0]);
-                    run -= 16;
-                }
-                const int v = coef[kZigzag[k]];
-                const int n = bit_length(v < 0 ? -v : v);
-                const int sym = (run << 4) | n;
-                bw.put(((unsigned)ac.code[sym] << n) | ((unsigned)(v < 0 ? v - 1 : v) & ((1u << n) - 1)), ac.len[sym] + n);
-            }
-            if (last != 63)
-                bw.put(ac.code[0x00], ac.len[0x00]);
+            put_block(bw, coef, prev_dc, dc, ac, T.nat2zig);
         }
     }
     bw.flush();
@@ -419,6 +465,82 @@ bool imencodeJpeg(const Mat &gray, vector<uchar> &out, int quality) {
     out.push_back(0xFF), out.push_back(0xD9);
     return true;
 }
+
+// cv::imencode(".jpg", bgr) at its defaults: YCbCr 4:2:0, one interleaved scan (reference src/denseflow_gpu.cpp:82-105, the
+// -s=0 mode).  libjpeg's pipeline restated: jccolor.c's fixed-point conversion, jcsample.c's h2v2_downsample of Cb / Cr
+// with its edge rules — the source's right column replicated up to the padded width BEFORE downsampling, an odd last row
+// replicated to a row pair, the downsampled rows replicated AFTER downsampling to a full MCU row — and jccoefct.c's dummy
+// blocks: a Y block that lies wholly outside the image has no AC and the DC of the block before it in the MCU, so it
+// codes as a zero difference + EOB.  Pinned against libjpeg-turbo (tests/test_jpeg_colour_pin.py).
+namespace {
+bool imencodeJpegColour(const Mat &bgr, vector<uchar> &out, int quality) {
+    const int W = bgr.cols, H = bgr.rows;
+    const int mx = (W + 15) / 16, my = (H + 15) / 16, cwp = mx * 8, ch = (H + 1) / 2;
+    QuantTable Q[2];
+    for (int t = 0; t < 2; ++t) {
+        uchar q[64];
+        dfx_jpeg_quantiser_from(t ? kDfxJpegChromaQ : kDfxJpegLumaQ, quality, q);
+        for (int i = 0; i < 64; ++i) {
+            Q[t].div[i] = 8u * q[i];
+            Q[t].magic[i] = dfx_jpeg_divide_magic(Q[t].div[i]);
+        }
+    }
+    const CodeTables &T = code_tables();
+    // planes: Y at the image size (fdct_quant replicates the ragged edge), Cb / Cr at the padded chroma width
+    vector<uchar> yp((size_t)W * H), cbp((size_t)cwp * ch), crp((size_t)cwp * ch);
+    for (int y = 0; y < H; ++y) {
+        const uchar *r = bgr.ptr<uchar>(y);
+        for (int x = 0; x < W; ++x)
+            yp[(size_t)y * W + x] = (uchar)DFX_JPEG_YCC_Y(r[3 * x + 2], r[3 * x + 1], r[3 * x]);
+    }
+    for (int cy = 0; cy < ch; ++cy) {
+        const uchar *r0 = bgr.ptr<uchar>(2 * cy), *r1 = bgr.ptr<uchar>(std::min(2 * cy + 1, H - 1));
+        for (int cx = 0; cx < cwp; ++cx) {
+            const int x0 = 3 * std::min(2 * cx, W - 1), x1 = 3 * std::min(2 * cx + 1, W - 1), bias = 1 + (cx & 1);
+            const uchar *px[4] = {r0 + x0, r0 + x1, r1 + x0, r1 + x1};
+            int cb = bias, cr = bias;
+            for (const uchar *p : px) {
+                cb += DFX_JPEG_YCC_CB(p[2], p[1], p[0]);
+                cr += DFX_JPEG_YCC_CR(p[2], p[1], p[0]);
+            }
+            cbp[(size_t)cy * cwp + cx] = (uchar)(cb >> 2);
+            crp[(size_t)cy * cwp + cx] = (uchar)(cr >> 2);
+        }
+    }
+    uchar header[DFX_JPEG_COLOUR_HEADER_MAX];
+    out.assign(header, header + dfx_jpeg_colour_header(W, H, quality, header));
+    static thread_local vector<uchar> scratch;
+    const size_t blocks = (size_t)mx * my * 6;
+    if (scratch.size() < blocks * 432 + 16)
+        scratch.resize(blocks * 432 + 16);
+    BitWriter bw(scratch.data());
+    int pred[3] = {0, 0, 0};
+    for (int m_y = 0; m_y < my; ++m_y)
+        for (int m_x = 0; m_x < mx; ++m_x) {
+            alignas(32) int coef[64];
+            for (int k = 0; k < 4; ++k) {
+                const int bx = (2 * m_x + (k & 1)) * 8, by = (2 * m_y + (k >> 1)) * 8;
+                if (bx < W && by < H) {
+                    fdct_quant(yp.data() + (size_t)by * W + bx, (size_t)W, W - bx, H - by, Q[0], coef);
+                } else { // dummy block: the previous Y block's DC, no AC
+                    coef[0] = pred[0];
+                    for (int i = 1; i < 64; ++i)
+                        coef[i] = 0;
+                }
+                put_block(bw, coef, pred[0], T.dc, T.ac, T.nat2zig);
+            }
+            const uchar *cp[2] = {cbp.data(), crp.data()};
+            for (int c = 0; c < 2; ++c) {
+                fdct_quant(cp[c] + (size_t)(m_y * 8) * cwp + m_x * 8, (size_t)cwp, 8, ch - m_y * 8, Q[1], coef);
+                put_block(bw, coef, pred[1 + c], T.dc_c, T.ac_c, T.nat2zig);
+            }
+        }
+    bw.flush();
+    out.insert(out.end(), scratch.data(), bw.p);
+    out.push_back(0xFF), out.push_back(0xD9);
+    return true;
+}
+} // namespace
 
 // ------------------------------------------------------------------------------------------------
 // PNG writer: 8-bit gray or BGR (stored as RGB) — the file cv::imencode(".png") writes (reference src/common.cpp:70).
