@@ -13,7 +13,7 @@
 namespace {
 
 // A DFX_ALGO_FRAMES handle has no flow engine behind it: this one allocates nothing and refuses every flow request
-// (the ABI's flow entry points stop earlier, in calc_batch_impl).
+// (the ABI's flow entry points stop earlier, in dfx_run_flowbuffer).
 class FramesEngine : public AlgoEngine {
   public:
     explicit FramesEngine(dfx_context *c) : c_(c) {}
@@ -49,25 +49,6 @@ template <class T> int dev_alloc(dfx_context *c, T *&p, size_t bytes) {
     return DFX_OK;
 }
 
-void free_encoder(dfx_context *c) {
-    auto &j = c->colour;
-    dfx_free_dev(j.d_tab);
-    dfx_free_dev(j.d_dc);
-    dfx_free_dev(j.d_bits);
-    dfx_free_dev(j.d_plane_bits);
-    dfx_free_dev(j.d_plane_base);
-    dfx_free_dev(j.d_hdr);
-    for (int q = 0; q < 2; ++q) {
-        dfx_free_dev(j.d_stream[q]);
-        dfx_free_host(j.h_stream[q]);
-        j.h_capacity[q] = 0;
-        dfx_free_host(j.h_info[q]);
-        j.d_info[q] = nullptr;
-    }
-    j.quality = j.frames = 0;
-    j.capacity = 0;
-}
-
 void free_staging(dfx_context *c) {
     auto &j = c->colour;
     for (auto &p : j.d_src)
@@ -83,107 +64,49 @@ int ensure_colour(dfx_context *c, int frames, int quality, int sw, int sh) {
     auto &j = c->colour;
     const bool resize = sw != c->W || sh != c->H;
     const size_t sp = round4((size_t)sw * 3), fb = sp * (size_t)sh;
-    if (j.quality == quality && frames <= j.frames && frames <= j.src_slots && j.src_frame_bytes == fb && j.src_pitch == sp &&
+    if (j.quality == quality && frames <= j.slots && frames <= j.src_slots && j.src_frame_bytes == fb && j.src_pitch == sp &&
         (!resize || frames <= j.bgr_slots))
         return DFX_OK;
-    (void)dfx_finish_tails(c, 0, -1);
-    HIPCHK(c, hipDeviceSynchronize());
-    free_encoder(c);
-    free_staging(c);
-    j.device_bytes = 0;
-    const size_t mcus = (size_t)((c->W + 15) / 16) * ((c->H + 15) / 16), nblk = mcus * 6;
-    JpegTables t[2];
-    jpeg_build_colour_tables(quality, t);
-    j.header = jpeg_colour_file_header(c->W, c->H, quality);
-    int rc = dev_alloc(c, j.d_tab, sizeof t);
-    if (rc != DFX_OK)
-        return rc;
-    HIPCHK(c, hipMemcpy(j.d_tab, t, sizeof t, hipMemcpyHostToDevice));
-    if ((rc = dev_alloc(c, j.d_dc, (size_t)frames * nblk * sizeof(short))) != DFX_OK ||
-        (rc = dev_alloc(c, j.d_bits, (size_t)frames * nblk * sizeof(unsigned))) != DFX_OK ||
-        (rc = dev_alloc(c, j.d_plane_bits, (size_t)frames * 8)) != DFX_OK ||
-        (rc = dev_alloc(c, j.d_plane_base, (size_t)frames * 8)) != DFX_OK || (rc = dev_alloc(c, j.d_hdr, 16)) != DFX_OK)
-        return rc;
-    // shared stream buffer: 4 bits per pixel on average over the batch (a photographic frame at quality 95 needs 1.5 - 3;
-    // a batch that does not fit is measured and coded again after grow_streams)
-    j.capacity = (((size_t)frames * c->W * c->H / 2 + (64u << 10)) + 255) & ~(size_t)255;
-    for (int p = 0; p < 2; ++p) {
-        if ((rc = dev_alloc(c, j.d_stream[p], j.capacity)) != DFX_OK)
+    return dfx_regrow(c, j.slots, frames, [&]() -> int {
+        dfx_jpeg_free(c->colour);
+        free_staging(c);
+        j.device_bytes = 0;
+        const size_t mcus = (size_t)((c->W + 15) / 16) * ((c->H + 15) / 16), nblk = mcus * 6;
+        JpegTables t[2];
+        jpeg_build_colour_tables(quality, t);
+        j.header = jpeg_colour_file_header(c->W, c->H, quality);
+        int rc = dev_alloc(c, j.d_tab, sizeof t);
+        if (rc != DFX_OK)
             return rc;
-        j.h_capacity[p] = j.capacity;
-        HIPCHK(c, hipHostMalloc((void **)&j.h_stream[p], j.h_capacity[p], hipHostMallocDefault));
-        HIPCHK(c, hipHostMalloc((void **)&j.h_info[p], (2 + 2 * (size_t)frames) * 8, hipHostMallocMapped));
-        std::memset(j.h_info[p], 0, (2 + 2 * (size_t)frames) * 8);
-        HIPCHK(c, hipHostGetDevicePointer((void **)&j.d_info[p], j.h_info[p], 0));
-        if ((rc = dev_alloc(c, j.d_src[p], (size_t)frames * fb)) != DFX_OK)
+        HIPCHK(c, hipMemcpy(j.d_tab, t, sizeof t, hipMemcpyHostToDevice));
+        if ((rc = dev_alloc(c, j.d_dc, (size_t)frames * nblk * sizeof(short))) != DFX_OK ||
+            (rc = dev_alloc(c, j.d_bits, (size_t)frames * nblk * sizeof(unsigned))) != DFX_OK ||
+            (rc = dev_alloc(c, j.d_plane_bits, (size_t)frames * 8)) != DFX_OK ||
+            (rc = dev_alloc(c, j.d_plane_base, (size_t)frames * 8)) != DFX_OK || (rc = dev_alloc(c, j.d_hdr, 16)) != DFX_OK)
             return rc;
-    }
-    if (resize && (rc = dev_alloc(c, j.d_bgr, (size_t)frames * round4((size_t)c->W * 3) * c->H)) != DFX_OK)
-        return rc;
-    j.quality = quality;
-    j.frames = j.src_slots = frames;
-    j.bgr_slots = resize ? frames : 0;
-    j.src_pitch = sp;
-    j.src_frame_bytes = fb;
-    return DFX_OK;
-}
-
-// The stream buffers (device + landing, both parities) re-sized to hold `need` bytes; on failure the old ones stay.
-int grow_streams(dfx_context *c, unsigned long long need) {
-    auto &j = c->colour;
-    (void)dfx_finish_tails(c, 0, -1); // a deferred tail may still be reading a landing buffer
-    HIPCHK(c, hipDeviceSynchronize());
-    const size_t cap = (((size_t)need + (size_t)need / 4 + (64u << 10)) + 255) & ~(size_t)255;
-    unsigned *nd[2] = {nullptr, nullptr};
-    unsigned char *nh[2] = {nullptr, nullptr};
-    hipError_t e = hipSuccess;
-    for (int p = 0; p < 2 && e == hipSuccess; ++p) {
-        e = hipMalloc((void **)&nd[p], cap);
-        if (e == hipSuccess)
-            e = hipHostMalloc((void **)&nh[p], cap, hipHostMallocDefault);
-    }
-    if (e != hipSuccess) {
+        // shared stream buffer: 4 bits per pixel on average over the batch (a photographic frame at quality 95 needs 1.5 - 3;
+        // a batch that does not fit is measured and coded again after dfx_jpeg_grow)
+        j.capacity = (((size_t)frames * c->W * c->H / 2 + (64u << 10)) + 255) & ~(size_t)255;
         for (int p = 0; p < 2; ++p) {
-            if (nd[p])
-                (void)hipFree(nd[p]);
-            if (nh[p])
-                (void)hipHostFree(nh[p]);
+            if ((rc = dev_alloc(c, j.d_stream[p], j.capacity)) != DFX_OK)
+                return rc;
+            j.h_capacity[p] = j.capacity;
+            HIPCHK(c, hipHostMalloc((void **)&j.h_stream[p], j.h_capacity[p], hipHostMallocDefault));
+            HIPCHK(c, hipHostMalloc((void **)&j.h_info[p], (2 + 2 * (size_t)frames) * 8, hipHostMallocMapped));
+            std::memset(j.h_info[p], 0, (2 + 2 * (size_t)frames) * 8);
+            HIPCHK(c, hipHostGetDevicePointer((void **)&j.d_info[p], j.h_info[p], 0));
+            if ((rc = dev_alloc(c, j.d_src[p], (size_t)frames * fb)) != DFX_OK)
+                return rc;
         }
-        (void)hipGetLastError();
-        return dfx_fail(c, DFX_ERR_HIP, "growing the colour JPEG stream buffers failed; the encoder keeps its old buffers");
-    }
-    for (int p = 0; p < 2; ++p) {
-        dfx_free_dev(j.d_stream[p]);
-        dfx_free_host(j.h_stream[p]);
-        j.d_stream[p] = nd[p];
-        j.h_stream[p] = nh[p];
-        j.h_capacity[p] = cap;
-    }
-    j.device_bytes += 2 * (cap - j.capacity);
-    j.capacity = cap;
-    return DFX_OK;
-}
-
-struct BatchFiles { // what the host needs to assemble the files of one device batch
-    int i0 = 0, n = 0, parity = 0;
-    std::vector<unsigned long long> bits, base;
-};
-
-int assemble(dfx_context *c, const std::vector<unsigned char> &header, const unsigned char *landing, const BatchFiles &b,
-             uint8_t *const *jpg, size_t cap, uint32_t *sizes, std::string *err) {
-    for (int j = 0; j < b.n; ++j) {
-        const size_t sz = jpeg_assemble(header, landing + b.base[j], b.bits[j], jpg[b.i0 + j], cap);
-        if (sz == 0) {
-            const char *m = "JPEG: jpg_capacity is too small for an encoded frame";
-            if (err)
-                *err = m;
-            else
-                c->set_err(m);
-            return DFX_ERR_UNSUPPORTED;
-        }
-        sizes[b.i0 + j] = (uint32_t)sz;
-    }
-    return DFX_OK;
+        if (resize && (rc = dev_alloc(c, j.d_bgr, (size_t)frames * round4((size_t)c->W * 3) * c->H)) != DFX_OK)
+            return rc;
+        j.quality = quality;
+        j.src_slots = frames;
+        j.bgr_slots = resize ? frames : 0;
+        j.src_pitch = sp;
+        j.src_frame_bytes = fb;
+        return DFX_OK;
+    });
 }
 
 // n source-size BGR frames -> n files, in device batches.  Per batch q (parity p = seq & 1):
@@ -193,10 +116,10 @@ int assemble(dfx_context *c, const std::vector<unsigned char> &header, const uns
 //   host        : header + stuffing of batch q - 1 while batch q computes
 // ticket != nullptr: the last batch's download and assembly finish on a helper thread (dfx_context::Tail).
 int extract_body(dfx_context *c, const uint8_t *const *frames, size_t pitch, int sw, int sh, int n, int quality,
-                 uint8_t *const *jpg, size_t cap, uint32_t *sizes, unsigned long long *ticket) {
+                 uint8_t *const *jpg, size_t cap, uint32_t *sizes, uint64_t *ticket) {
     auto &j = c->colour;
     const int B = std::min(frames_batch(c), std::max(n, 1));
-    int rc = ensure_colour(c, std::max(B, j.frames), quality, sw, sh);
+    int rc = ensure_colour(c, std::max(B, j.slots), quality, sw, sh);
     if (rc != DFX_OK)
         return rc;
     const bool resize = sw != c->W || sh != c->H;
@@ -227,8 +150,22 @@ int extract_body(dfx_context *c, const uint8_t *const *frames, size_t pitch, int
         HIPCHK(c, hipGetLastError());
         return DFX_OK;
     };
-    BatchFiles prev, cur;
+    // the files of batch [i0, i0 + coded.planes.size()) out of the landing buffer of parity p
+    auto files_of = [&](int i0, int p, const DfxJpegCoded &coded) {
+        DfxHandover h;
+        h.header = j.header, h.landing = j.h_stream[p], h.coded = coded.planes;
+        h.capacity = cap;
+        h.too_small = "JPEG: jpg_capacity is too small for an encoded frame";
+        for (size_t i = 0; i < coded.planes.size(); ++i) {
+            h.jpg.push_back(jpg[i0 + i]);
+            h.size.push_back(sizes + i0 + i);
+        }
+        return h;
+    };
+    DfxHandover prev; // the batch whose download is in flight
     bool have_prev = false;
+    int prev_parity = 0;
+    std::string err;
     const unsigned long long seq0 = j.seq;
     rc = upload(0, (int)(seq0 & 1));
     if (rc != DFX_OK)
@@ -250,79 +187,35 @@ int extract_body(dfx_context *c, const uint8_t *const *frames, size_t pitch, int
             return rc;
         if (have_prev) { // host work of batch q - 1 beside the kernels of batch q
             HIPCHK(c, dfx_stream_wait(c, c->d2h_stream));
-            if ((rc = assemble(c, j.header, j.h_stream[prev.parity], prev, jpg, cap, sizes, nullptr)) != DFX_OK)
-                return rc;
+            if ((rc = dfx_hand_over(prev, &err)) != DFX_OK)
+                return dfx_fail(c, rc, err);
             have_prev = false;
         }
-        HIPCHK(c, dfx_stream_wait(c, c->stream));
-        const unsigned long long *hi = j.h_info[p];
-        if (hi[1]) { // more than the stream buffer was sized for: grow it to what the scan pass measured, code again
-            if ((rc = grow_streams(c, hi[0])) != DFX_OK)
-                return rc;
-            if ((rc = encode(m, p)) != DFX_OK)
-                return rc;
-            HIPCHK(c, dfx_stream_wait(c, c->stream));
-            if (hi[1])
-                return dfx_fail(c, DFX_ERR_UNSUPPORTED, "JPEG: the frames do not fit the stream buffer (encode them on the host)");
-        }
-        cur.i0 = i0, cur.n = m, cur.parity = p;
-        cur.bits.resize(m), cur.base.resize(m);
-        for (int i = 0; i < m; ++i) {
-            cur.bits[i] = hi[2 + 2 * i];
-            cur.base[i] = hi[2 + 2 * i + 1];
-        }
-        HIPCHK(c, hipMemcpyAsync(j.h_stream[p], j.d_stream[p], (size_t)hi[0], hipMemcpyDeviceToHost, c->d2h_stream));
+        DfxJpegCoded coded;
+        size_t grown = 0;
+        rc = dfx_jpeg_settle(c, j, p, m, /*idle=*/false, "colour JPEG",
+                             "JPEG: the frames do not fit the stream buffer (encode them on the host)",
+                             [&] { return encode(m, p); }, &coded, &grown);
+        j.device_bytes += grown;
+        if (rc != DFX_OK)
+            return rc;
+        HIPCHK(c, hipMemcpyAsync(j.h_stream[p], j.d_stream[p], (size_t)coded.total, hipMemcpyDeviceToHost, c->d2h_stream));
         HIPCHK(c, hipEventRecord(c->ev_d2h[p], c->d2h_stream));
-        prev = cur;
+        prev = files_of(i0, p, coded);
+        prev_parity = p;
         have_prev = true;
     }
     c->stats.kernel_launches += (uint64_t)nb * (resize ? 6 : 5);
     if (!have_prev)
         return DFX_OK;
-    // A frame of the last batch that could exceed jpg_capacity with every byte stuffed is assembled here, synchronously,
-    // so that "does not fit" is this call's DFX_ERR_UNSUPPORTED and never a deferred tail's error.
-    bool may_not_fit = false;
-    for (unsigned long long b : prev.bits)
-        may_not_fit = may_not_fit || j.header.size() + 2 * (size_t)((b >> 3) + 1) + 2 > cap;
-    if (ticket && !may_not_fit) {
-        std::unique_ptr<dfx_context::Tail> t(new dfx_context::Tail());
-        t->ticket = c->next_ticket++;
-        t->parity = prev.parity;
-        dfx_context::Tail *tp = t.get();
-        const BatchFiles last = prev;
-        hipEvent_t ev = c->ev_d2h[prev.parity];
-        const unsigned char *landing = j.h_stream[prev.parity];
-        const std::vector<unsigned char> header = j.header;
-        std::vector<uint8_t *> dst(jpg, jpg + n); // the caller's pointer array need not outlive the submit call
-        const int dev = c->device;
-        std::mutex *mtx = &c->tails_mtx;
-        std::condition_variable *cv = &c->tails_cv;
-        t->worker = std::thread([=]() {
-            (void)hipSetDevice(dev);
-            const hipError_t e = hipEventSynchronize(ev);
-            int wrc = DFX_OK;
-            std::string werr;
-            if (e != hipSuccess) {
-                wrc = DFX_ERR_HIP;
-                werr = std::string("deferred download failed: ") + hipGetErrorString(e);
-            } else {
-                wrc = assemble(nullptr, header, landing, last, dst.data(), cap, sizes, &werr);
-            }
-            {
-                std::lock_guard<std::mutex> lock(*mtx);
-                tp->rc = wrc;
-                tp->err = werr;
-                tp->done = true;
-            }
-            cv->notify_all();
-        });
-        *ticket = t->ticket;
-        std::lock_guard<std::mutex> lock(c->tails_mtx);
-        c->tails.push_back(std::move(t));
+    if (ticket && !dfx_may_not_fit(prev)) {
+        *ticket = dfx_defer_tail(c, prev_parity, c->ev_d2h[prev_parity],
+                                 [h = std::move(prev)](std::string *e) { return dfx_hand_over(h, e); });
         return DFX_OK;
     }
     HIPCHK(c, dfx_stream_wait(c, c->d2h_stream));
-    return assemble(c, j.header, j.h_stream[prev.parity], prev, jpg, cap, sizes, nullptr);
+    rc = dfx_hand_over(prev, &err);
+    return rc == DFX_OK ? rc : dfx_fail(c, rc, err);
 }
 
 int extract_entry(dfx_handle h, const uint8_t *const *frames, size_t pitch, int sw, int sh, int n, int quality,
@@ -346,17 +239,11 @@ int extract_entry(dfx_handle h, const uint8_t *const *frames, size_t pitch, int 
     if (quality < 1 || quality > 100)
         return dfx_fail(h, DFX_ERR_INVALID, "JPEG quality must be 1..100");
     HIPCHK(h, hipSetDevice(h->device));
-    unsigned long long t = 0;
-    const int rc = extract_body(h, frames, pitch, sw, sh, n, quality, jpg, cap, sizes, ticket ? &t : nullptr);
-    if (rc != DFX_OK) { // copies into caller-owned buffers may be in flight: drain before handing the error back
-        const std::string keep = h->get_err();
-        (void)hipStreamSynchronize(h->copy_stream);
-        (void)hipStreamSynchronize(h->stream);
-        (void)hipStreamSynchronize(h->d2h_stream);
-        (void)dfx_finish_tails(h, 0, -1);
-        h->set_err(keep);
-    } else if (ticket) {
-        *ticket = t;
+    const int rc = extract_body(h, frames, pitch, sw, sh, n, quality, jpg, cap, sizes, ticket);
+    if (rc != DFX_OK) { // copies into caller-owned buffers may be in flight
+        dfx_drain_after_error(h);
+        if (ticket)
+            *ticket = 0;
     }
     return rc;
 }
@@ -366,7 +253,7 @@ int extract_entry(dfx_handle h, const uint8_t *const *frames, size_t pitch, int 
 AlgoEngine *dfx_make_frames_engine(dfx_context *c) { return new FramesEngine(c); }
 
 void dfx_free_colour(dfx_context *c) {
-    free_encoder(c);
+    dfx_jpeg_free(c->colour);
     free_staging(c);
     c->colour.device_bytes = 0;
 }

@@ -1,7 +1,7 @@
 // dfx_helper.h — the ONE helper thread of a handle (no HIP in this header: tests/helper_tsan.cpp runs it under
 // ThreadSanitizer on the CPU).
 //
-// The host-pointer path of calc_batch_body hands the host-side work of batch k-1 / k+1 (rows from the bounce buffer to the
+// The host-pointer path of dfx_pipeline.cpp hands the host-side work of batch k-1 / k+1 (rows from the bounce buffer to the
 // caller's buffers, JPEG files assembled, the next batch's frames gathered and sent up) to another thread while the
 // calling thread drives batch k.  Rounds 3-4 created a std::thread per batch for that (ADVICE r3 / VERDICT r4 #8: ~20 us
 // of clone + join per batch, and a thread id per batch in every trace); this is one persistent thread per handle, created

@@ -1,5 +1,7 @@
-// dfx_internal.h — host-side plumbing shared by the C ABI (dfx_api.cpp) and the per-algorithm
-// engines (tvl1_engine.cpp, farneback_engine.cpp).  Nothing here crosses the C ABI.
+// dfx_internal.h — host-side plumbing shared by the C ABI (dfx_api.cpp: argument checks and entry points), the two
+// device-to-caller pipelines (dfx_pipeline.cpp: FlowBuffers; dfx_frames.cpp: colour frames), what they share
+// (dfx_streams.cpp: deferred tails, JPEG stream state) and the per-algorithm engines (*_engine.cpp).  Nothing here
+// crosses the C ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -8,6 +10,7 @@
 #include <condition_variable>
 #include <cstdio>
 #include <deque>
+#include <functional>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -16,9 +19,10 @@
 
 #include "../../include/dfx.h"
 #include "dfx_device.h"
+#include "dfx_handover.h"
 #include "dfx_helper.h"
 
-// An algorithm engine owns every device buffer of one handle.  The common driver (dfx_api.cpp)
+// An algorithm engine owns every device buffer of one handle.  The common driver (dfx_pipeline.cpp)
 // walks a FlowBuffer in batches of `batch()` pairs, keeps the per-frame derived data (pyramids,
 // polynomial expansions) in a ring of frame slots so each frame is prepared once, and calls:
 //     build_frames  - prepare `n` new frames (u8 pixels already on the device) into the given slots
@@ -47,6 +51,24 @@ class AlgoEngine {
         (void)max_pairs, (void)iters, (void)checks;
         return -DFX_ERR_UNSUPPORTED;
     }
+};
+
+// The stream state of a device JPEG encoder, gray (dfx_context::jpeg) or colour (dfx_context::colour): tables and
+// per-block temporaries, and per staging parity the shared stream buffer, its page-locked landing buffer and the totals
+// the device reports (dfx_streams.cpp).
+struct JpegStreams {
+    int quality = 0, slots = 0; // what the buffers below are sized for (slots: pairs of a flow batch / colour frames)
+    struct JpegTables *d_tab = nullptr;
+    short *d_dc = nullptr;
+    unsigned *d_bits = nullptr;
+    unsigned long long *d_plane_bits = nullptr, *d_plane_base = nullptr;
+    unsigned long long *d_hdr = nullptr; // device copy of (total, overflow): the emit pass must not poll host memory
+    unsigned *d_stream[2] = {nullptr, nullptr};
+    unsigned char *h_stream[2] = {nullptr, nullptr};
+    size_t h_capacity[2] = {0, 0}; // page-locked landing buffers (gray: sized to what batches need, dfx_jpeg_ensure_landing)
+    unsigned long long *h_info[2] = {nullptr, nullptr}, *d_info[2] = {nullptr, nullptr}; // mapped page-locked
+    size_t capacity = 0;
+    std::vector<unsigned char> header;
 };
 
 struct dfx_context {
@@ -105,36 +127,12 @@ struct dfx_context {
     int png_slots = 0;
     // device JPEG encoder (jpeg_kernels.hip): tables + per-block temporaries (one set, compute stream only), and per
     // staging parity the shared stream buffer, its page-locked landing buffer and the totals the device reports
-    struct JpegState {
-        int quality = 0, pairs = 0; // what the buffers below are sized for
-        struct JpegTables *d_tab = nullptr;
-        short *d_dc = nullptr;
-        unsigned *d_bits = nullptr;
-        unsigned long long *d_plane_bits = nullptr, *d_plane_base = nullptr;
-        unsigned *d_stream[2] = {nullptr, nullptr};
-        unsigned char *h_stream[2] = {nullptr, nullptr};
-        size_t h_capacity[2] = {0, 0}; // page-locked landing buffers: sized to what batches actually need (ensure_jpeg_landing)
-        unsigned long long *h_info[2] = {nullptr, nullptr}, *d_info[2] = {nullptr, nullptr}; // mapped page-locked
-        unsigned long long *d_hdr = nullptr; // device copy of (total, overflow): the emit pass must not poll host memory
-        size_t capacity = 0;
-        std::vector<unsigned char> header;
-    } jpeg;
-    // colour frame extraction (dfx_frames.cpp: dfx_extract_frames / dfx_encode_jpeg_bgr): the colour encoder's tables and
-    // per-block temporaries (one set, compute stream only); per staging parity the source-size BGR frames, the shared
-    // stream buffer, its page-locked landing buffer and the totals the device reports; the resized frames (one set:
-    // written and read on the compute stream).  Row pitches are multiples of 4 (jpeg_colour_kernels.hip reads dwords).
-    struct ColourState {
-        int quality = 0, frames = 0; // what the encoder buffers are sized for
-        struct JpegTables *d_tab = nullptr; // [2]: luminance, chrominance
-        short *d_dc = nullptr;
-        unsigned *d_bits = nullptr;
-        unsigned long long *d_plane_bits = nullptr, *d_plane_base = nullptr, *d_hdr = nullptr;
-        unsigned *d_stream[2] = {nullptr, nullptr};
-        unsigned char *h_stream[2] = {nullptr, nullptr};
-        size_t h_capacity[2] = {0, 0};
-        unsigned long long *h_info[2] = {nullptr, nullptr}, *d_info[2] = {nullptr, nullptr}; // mapped page-locked
-        size_t capacity = 0;
-        std::vector<unsigned char> header;
+    JpegStreams jpeg;
+    // colour frame extraction (dfx_frames.cpp: dfx_extract_frames / dfx_encode_jpeg_bgr): the colour encoder's stream state
+    // (d_tab is [2]: luminance, chrominance; a slot is a frame); per staging parity the source-size BGR frames; the
+    // resized frames (one set: written and read on the compute stream).  Row pitches are multiples of 4
+    // (jpeg_colour_kernels.hip reads dwords).
+    struct ColourState : JpegStreams {
         unsigned char *d_src[2] = {nullptr, nullptr}; // src_slots source-size frames per parity
         int src_slots = 0;
         size_t src_pitch = 0, src_frame_bytes = 0;
@@ -182,6 +180,14 @@ struct dfx_context {
 // (housekeeping inside other entry points): errors stay recorded for the dfx_wait of their ticket.
 int dfx_finish_tails(dfx_context *c, unsigned long long up_to, int parity, bool report = false);
 
+// The deferred tail of a dfx_submit_* call: a worker waits for `event` (the last download of staging parity `parity`),
+// runs `work` (which owns copies of all it touches; it returns a status and fills the error text) and publishes the
+// outcome.  Returns the tail's ticket.
+unsigned long long dfx_defer_tail(dfx_context *c, int parity, hipEvent_t event, std::function<int(std::string *)> work);
+// An error return may leave asynchronous copies in flight that target caller-owned (often pool-recycled) buffers: drain
+// every stream and every deferred tail before handing the error back.  The error text survives.
+void dfx_drain_after_error(dfx_context *c);
+
 #define HIPCHK(ctx, call)                                                                                       \
     do {                                                                                                        \
         hipError_t e_ = (call);                                                                                 \
@@ -228,6 +234,35 @@ template <class T> inline void dfx_free_host(T *&p) {
         p = nullptr;
     }
 }
+
+// Grow a set of buffers that is sized for `count` slots to `need`: nothing may use the old ones (deferred tails, device
+// work), and `alloc` — which frees them and allocates the new ones — may fail half-way.
+template <class N, class F> inline int dfx_regrow(dfx_context *c, N &count, N need, F alloc) {
+    (void)dfx_finish_tails(c, 0, -1);
+    HIPCHK(c, hipDeviceSynchronize());
+    count = 0; // a failed allocation below must not leave the old size standing
+    const int rc = alloc();
+    if (rc == DFX_OK)
+        count = need;
+    return rc;
+}
+
+// ---- JPEG stream state (dfx_streams.cpp) ----
+void dfx_jpeg_free(JpegStreams &j);
+// Both stream buffers and both landing buffers re-sized to hold `need` bytes, all or nothing: a failure leaves the
+// encoder as it was.  *delta (optional) receives the change in device bytes.  `noun` names the encoder in the error.
+int dfx_jpeg_grow(dfx_context *c, JpegStreams &j, unsigned long long need, const char *noun, size_t *delta = nullptr);
+// The landing buffer of parity q holds at least `need` bytes.  Nothing reads or writes h_stream[q] when this is called.
+int dfx_jpeg_ensure_landing(dfx_context *c, JpegStreams &j, int q, size_t need);
+struct DfxJpegCoded { // what the device reports for one coded batch
+    unsigned long long total = 0;     // bytes of the batch's streams in d_stream[parity]
+    std::vector<DfxCodedPlane> planes;
+};
+// After the encode of `n` planes has been launched on the compute stream into parity q: wait for it (idle = true: the
+// caller already has), and if the streams did not fit the shared buffer, grow it to what the scan pass measured, `launch`
+// the encode once more and wait again.  Still no fit: DFX_ERR_UNSUPPORTED with `no_fit` as the text.
+int dfx_jpeg_settle(dfx_context *c, JpegStreams &j, int q, int n, bool idle, const char *noun, const char *no_fit,
+                    const std::function<int()> &launch, DfxJpegCoded *out, size_t *delta = nullptr);
 
 AlgoEngine *dfx_make_tvl1_engine(dfx_context *c);
 AlgoEngine *dfx_make_farneback_engine(dfx_context *c);

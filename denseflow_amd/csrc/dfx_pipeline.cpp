@@ -1,0 +1,556 @@
+// dfx_pipeline.cpp — the FlowBuffer driver that is common to every algorithm: staging, the upload / compute / download
+// schedule over device batches, the bounded / PNG / JPEG output stages and the hand-over to the caller's buffers.
+//
+// Reference behaviour mirrored: DenseFlow::calc_optflows_imp, /root/reference/src/denseflow_gpu.cpp
+// :282-370 — pair selection :315-316, per-pair upload/calc/download :317-339, M = max(N-|step|,0)
+// flows per FlowBuffer :307-308.
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
+
+#include "dfx_pipeline.h"
+#include "dfx_plan.h"
+#include "jpeg_kernels.h"
+#include "prepare_kernels.h"
+#include "quantize_kernels.h"
+
+namespace {
+
+// both buffers of a staging pair, freed and allocated anew (device memory, or page-locked host memory)
+template <class T> int realloc_pair(dfx_context *c, T *(&pair)[2], size_t bytes, bool host = false) {
+    for (auto &p : pair) {
+        if (host) {
+            dfx_free_host(p);
+            HIPCHK(c, hipHostMalloc((void **)&p, bytes, hipHostMallocDefault));
+        } else {
+            dfx_free_dev(p);
+            HIPCHK(c, hipMalloc((void **)&p, bytes));
+        }
+    }
+    return DFX_OK;
+}
+
+int ensure_src_staging(dfx_context *c, int need) {
+    const size_t fb = c->in_row_bytes() * c->in_h();
+    if (need <= c->src_slots && fb == c->src_frame_bytes)
+        return DFX_OK;
+    return dfx_regrow(c, c->src_slots, need, [&]() -> int {
+        c->src_frame_bytes = 0;
+        const int rc = realloc_pair(c, c->d_src, (size_t)need * fb);
+        if (rc == DFX_OK)
+            c->src_frame_bytes = fb;
+        return rc;
+    });
+}
+
+int ensure_bounce(dfx_context *c, size_t in_bytes, size_t out_bytes) {
+    int rc = DFX_OK;
+    if (in_bytes > c->h_in_bytes)
+        rc = dfx_regrow(c, c->h_in_bytes, in_bytes, [&] { return realloc_pair(c, c->h_in, in_bytes, true); });
+    if (rc == DFX_OK && out_bytes > c->h_out_bytes)
+        rc = dfx_regrow(c, c->h_out_bytes, out_bytes, [&] { return realloc_pair(c, c->h_out, out_bytes, true); });
+    return rc;
+}
+
+int ensure_staging(dfx_context *c, int u8_need, int flow_need) {
+    const size_t plane = (size_t)c->W * c->H;
+    int rc = DFX_OK;
+    if (u8_need > c->u8_slots)
+        rc = dfx_regrow(c, c->u8_slots, u8_need, [&] { return realloc_pair(c, c->d_u8, (size_t)u8_need * plane); });
+    if (rc == DFX_OK && flow_need > c->flow_slots)
+        rc = dfx_regrow(c, c->flow_slots, flow_need,
+                        [&] { return realloc_pair(c, c->d_flow_out, (size_t)flow_need * plane * 2 * sizeof(float)); });
+    return rc;
+}
+
+// One frame / plane between host and device.  Dense rows (pitch == row bytes on both sides) go as ONE linear copy:
+// a 2-D copy of a small frame costs several times the linear one, and a FlowBuffer of 224x224 frames is hundreds
+// of them.
+inline hipError_t copy_rows_async(void *dst, size_t dpitch, const void *src, size_t spitch, size_t row_bytes,
+                                  size_t rows, hipMemcpyKind kind, hipStream_t s) {
+    if (dpitch == row_bytes && spitch == row_bytes)
+        return hipMemcpyAsync(dst, src, row_bytes * rows, kind, s);
+    return hipMemcpy2DAsync(dst, dpitch, src, spitch, row_bytes, rows, kind, s);
+}
+
+// One FlowBuffer on its way through the device, for host- and device-resident frames.
+//   host mode  : in.frames[i] host pointers, results to host pointers.  Copies run on their own streams through two
+//                staging sets: the frames of batch i+1 go up and the flows of batch i-1 come down while batch i computes
+//                (the reference uploads, computes and downloads one pair at a time with a blocking download, :317-339).
+//   device mode: in.d_frames / out.d_* contiguous device arrays, no copies at all.
+// The handle's helper thread runs host-side work of the neighbouring batches and reads this object: the destructor
+// finishes its job on every path out.
+struct FlowRun {
+    dfx_context *c;
+    const InSpec &in;
+    const OutSpec &out;
+    const int step;
+    AlgoEngine *E = nullptr;
+    DfxPairs pairs;
+    std::vector<DfxBatchPlan> plan;
+    unsigned long long seq0 = 0; // batches are numbered across calls (q = seq0 + k): see par()
+    int F = 0;                   // frame slots of the engine: frame id f lives in slot f % F
+    bool host_mode = false, prep = false, bounce_in = false, bounce = false;
+    size_t plane = 0;
+    std::vector<DfxJpegCoded> coded; // JPEG mode: what the device reported for each batch
+
+    FlowRun(dfx_context *ctx, const InSpec &i, const OutSpec &o, int s) : c(ctx), in(i), out(o), step(s) {}
+    ~FlowRun() { (void)c->helper.finish(); }
+    // batch k uses staging set / bounce buffer / events of this parity
+    int par(size_t k) const { return (int)((seq0 + k) & 1ull); }
+    int prepare(const std::vector<int> &seg);
+    int run(uint64_t *ticket);
+    int upload(size_t k);
+    int download(size_t k);
+    DfxHandover describe(size_t k) const;
+    int hand_over(size_t k);
+    int overlap_copies(size_t k);
+    int compute(size_t k);
+    int launch_jpeg(size_t k);
+    int finish(uint64_t *ticket);
+};
+
+// Pairs, engine frame slots, staging, the bounce decision and the batch plan.  Leaves plan empty for M = 0.
+int FlowRun::prepare(const std::vector<int> &seg) {
+    pairs = dfx_build_pairs(seg, step); // dfx_plan.h: pure host logic, CPU-tested
+    const int M = pairs.size();
+    if (M == 0)
+        return DFX_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    E = c->engine;
+    int B = E->batch();
+    const int F_need = std::max(dfx_frames_needed(pairs, B), std::min(B, M) + std::abs(step));
+    int rc = E->ensure_frame_slots(F_need);
+    host_mode = in.frames != nullptr;
+    // float flows land in the caller's device array, or in a staging set when they are copied to the host
+    // or only feed the bounding kernel
+    prep = c->prepares(); // inputs are source-format frames: convert / resize them on the device first
+    if (rc == DFX_OK)
+        rc = ensure_staging(c, (host_mode || prep) ? F_need : 0, (host_mode || out.quantized) ? B : 0);
+    if (rc == DFX_OK && prep && host_mode)
+        rc = ensure_src_staging(c, F_need);
+    if (rc == DFX_OK && out.quantized && host_mode)
+        rc = dfx_ensure_img_staging(c, B);
+    if (rc == DFX_OK && out.jpeg)
+        rc = dfx_ensure_jpeg(c, B, out.quality);
+    if (rc == DFX_OK && out.png)
+        rc = dfx_ensure_png(c, B);
+    if (rc != DFX_OK)
+        return rc;
+    plane = (size_t)c->W * c->H;
+    // Small frames: an asynchronous copy costs ~10 us of driver time whatever its size, and a 300-frame clip of
+    // 224x224 frames is ~900 of them (a third of the batch's compute time).  Such FlowBuffers go through page-locked
+    // bounce buffers instead: the host gathers / scatters the frames with memcpy and the copy stream moves one block
+    // per batch and direction.
+    const size_t in_fb = c->in_row_bytes() * c->in_h();
+    const size_t out_pb = out.quantized ? 2 * plane : plane * 8; // bytes per pair leaving the device
+    // Decided per direction: a 224x224 frame is 50 KB (gathered), but its float flow is 401 KB — one direct copy per
+    // flow (~10 us of driver time) is cheaper than a second pass of host memcpy over 120 MB per clip.
+    bounce_in = host_mode && in_fb <= (256u << 10) && (size_t)F_need * in_fb <= (256u << 20);
+    bounce = !out.jpeg && bounce_in && out_pb <= (256u << 10) && (size_t)B * out_pb <= (256u << 20); // results
+    if (bounce_in) {
+        rc = ensure_bounce(c, (size_t)F_need * in_fb, bounce ? (size_t)B * out_pb : 0);
+        if (rc != DFX_OK)
+            return rc;
+    } else if (host_mode && M <= B && M >= 32) {
+        // Large frames, and the whole FlowBuffer would be one batch: nothing could overlap its copies.  Two balanced
+        // batches put the second upload and the first download under the compute (the engine's batch is sized for
+        // the device-resident path, where a bigger batch is simply better: 336 / 362 pairs/s at 32 / 128 for TVL1).
+        B = (M + 1) / 2;
+    }
+    F = E->frame_slots();
+    c->h_slots.resize(F);
+    c->h_pairs.resize(B);
+    // Frames [lo of its first pair, hi of its last pair] must be resident for a batch; earlier batches already prepared
+    // the ids below their own end.  Frame id f lives in slot f % F; F >= that range, so a batch never evicts what it needs.
+    plan = dfx_plan_batches(pairs, B);
+    seq0 = c->batch_seq;
+    c->batch_seq += plan.size();
+    coded.resize(out.jpeg ? plan.size() : 0);
+    return DFX_OK;
+}
+
+int FlowRun::upload(size_t k) { // host frames of batch k -> staging set par(k) (upload stream)
+    const DfxBatchPlan &p = plan[k];
+    const int q = par(k);
+    const size_t rb = c->in_row_bytes(), fb = rb * c->in_h();
+    unsigned char *dst = prep ? c->d_src[q] : c->d_u8[q];
+    // the staging set was last read by the frame preparation of batch q-2 (compute stream)
+    if (seq0 + k >= 2)
+        HIPCHK(c, hipStreamWaitEvent(c->copy_stream, c->ev_compute[q], 0));
+    if (bounce_in) {
+        if (seq0 + k >= 2) // the copy that last read this bounce buffer (batch q-2) has long finished; make it formal
+            HIPCHK(c, hipEventSynchronize(c->ev_h2d[q]));
+        unsigned char *hb = c->h_in[q];
+        for (int j = 0; j < p.n_new; ++j)
+            dfx_copy_rows(hb + (size_t)j * fb, rb, in.frames[p.first_new + j], in.frame_pitch, rb, c->in_h());
+        if (p.n_new > 0)
+            HIPCHK(c, hipMemcpyAsync(dst, hb, (size_t)p.n_new * fb, hipMemcpyHostToDevice, c->copy_stream));
+    } else {
+        for (int j = 0; j < p.n_new; ++j)
+            HIPCHK(c, copy_rows_async(dst + (size_t)j * fb, rb, in.frames[p.first_new + j], in.frame_pitch, rb, c->in_h(),
+                                      hipMemcpyHostToDevice, c->copy_stream));
+    }
+    HIPCHK(c, hipEventRecord(c->ev_h2d[q], c->copy_stream));
+    return DFX_OK;
+}
+
+int FlowRun::download(size_t k) { // results of batch k: staging set par(k) -> host (download stream)
+    const DfxBatchPlan &p = plan[k];
+    const int q = par(k);
+    HIPCHK(c, hipStreamWaitEvent(c->d2h_stream, c->ev_compute[q], 0));
+    if (out.jpeg || bounce) {
+        // one block (JPEG: the entropy-coded segments; bounce: one per plane kind) that hand_over(k) turns into the caller's
+        // files / rows later.  A deferred tail of an earlier FlowBuffer may still be reading this landing / bounce buffer.
+        const int trc = dfx_finish_tails(c, 0, q);
+        if (trc != DFX_OK)
+            return trc;
+    }
+    if (out.jpeg) {
+        if (coded[k].total > 0) {
+            const int grc = dfx_jpeg_ensure_landing(c, c->jpeg, q, (size_t)coded[k].total);
+            if (grc != DFX_OK)
+                return grc;
+            HIPCHK(c, hipMemcpyAsync(c->jpeg.h_stream[q], c->jpeg.d_stream[q], (size_t)coded[k].total,
+                                     hipMemcpyDeviceToHost, c->d2h_stream));
+        }
+    } else if (bounce) {
+        unsigned char *hb = c->h_out[q];
+        if (out.quantized) {
+            HIPCHK(c, hipMemcpyAsync(hb, c->d_img[q], (size_t)p.nb * plane, hipMemcpyDeviceToHost, c->d2h_stream));
+            HIPCHK(c, hipMemcpyAsync(hb + (size_t)p.nb * plane, c->d_img[q] + (size_t)c->img_slots * plane,
+                                     (size_t)p.nb * plane, hipMemcpyDeviceToHost, c->d2h_stream));
+        } else {
+            HIPCHK(c, hipMemcpyAsync(hb, c->d_flow_out[q], (size_t)p.nb * plane * 8, hipMemcpyDeviceToHost,
+                                     c->d2h_stream));
+        }
+    } else {
+        for (int j = 0; j < p.nb; ++j) {
+            if (out.quantized) {
+                const unsigned char *sx = c->d_img[q] + (size_t)j * plane;
+                const unsigned char *sy = c->d_img[q] + ((size_t)c->img_slots + j) * plane;
+                HIPCHK(c, copy_rows_async(out.img_x[p.i0 + j], out.img_pitch, sx, c->W, c->W, c->H,
+                                          hipMemcpyDeviceToHost, c->d2h_stream));
+                HIPCHK(c, copy_rows_async(out.img_y[p.i0 + j], out.img_pitch, sy, c->W, c->W, c->H,
+                                          hipMemcpyDeviceToHost, c->d2h_stream));
+            } else {
+                HIPCHK(c, copy_rows_async(out.flows[p.i0 + j], out.out_pitch, c->d_flow_out[q] + (size_t)j * plane * 2,
+                                          (size_t)c->W * 8, (size_t)c->W * 8, c->H, hipMemcpyDeviceToHost,
+                                          c->d2h_stream));
+            }
+        }
+    }
+    HIPCHK(c, hipEventRecord(c->ev_d2h[q], c->d2h_stream));
+    return DFX_OK;
+}
+
+// What is left to do on the host for batch k once its download has arrived (nothing for direct copies).  Valid from
+// download(k) on: that call settles which landing buffer the batch uses.
+DfxHandover FlowRun::describe(size_t k) const {
+    const DfxBatchPlan &p = plan[k];
+    DfxHandover h;
+    if (out.jpeg) { // header + byte-stuffed segment + EOI for every plane of the batch: its x planes, then its y planes
+        h.header = c->jpeg.header;
+        h.landing = c->jpeg.h_stream[par(k)];
+        h.coded = coded[k].planes;
+        h.capacity = out.jpg_capacity;
+        h.too_small = "JPEG: jpg_capacity is too small for an encoded plane (encode this FlowBuffer's 8-bit planes on the host)";
+        for (int j = 0; j < 2 * p.nb; ++j) {
+            const bool is_y = j >= p.nb;
+            const int i = p.i0 + (is_y ? j - p.nb : j);
+            h.jpg.push_back(is_y ? out.jpg_y[i] : out.jpg_x[i]);
+            h.size.push_back((is_y ? out.size_y : out.size_x) + i);
+        }
+    } else if (bounce) {
+        h.block = c->h_out[par(k)];
+        h.two_planes = out.quantized;
+        h.W = c->W, h.H = c->H;
+        h.pitch = out.quantized ? out.img_pitch : out.out_pitch;
+        for (int j = 0; j < p.nb; ++j) {
+            if (out.quantized) {
+                h.dst_a.push_back(out.img_x[p.i0 + j]);
+                h.dst_b.push_back(out.img_y[p.i0 + j]);
+            } else {
+                h.dst_a.push_back(out.flows[p.i0 + j]);
+            }
+        }
+    }
+    return h;
+}
+
+int FlowRun::hand_over(size_t k) { // results of batch k -> the caller's buffers, on the calling or the helper thread
+    HIPCHK(c, hipEventSynchronize(c->ev_d2h[par(k)]));
+    std::string err;
+    const int rc = dfx_hand_over(describe(k), &err);
+    return rc == DFX_OK ? rc : dfx_fail(c, rc, err);
+}
+
+// Host mode, before batch k computes: flows of batch k-1 down (download stream, after its compute), frames of batch k+1
+// up (upload stream, after the frame preparation of batch k-1, which last read that staging set).
+int FlowRun::overlap_copies(size_t k) {
+    int rc = k >= 1 ? download(k - 1) : DFX_OK;
+    if (rc != DFX_OK)
+        return rc;
+    // Host work that can run beside this thread driving batch k (the TVL1 engine polls the device inside
+    // run_pairs), on a helper thread: hand the results of batch k-1 over (rows to the caller's buffers / JPEG
+    // files assembled; its download was enqueued just above and is a fraction of a batch's compute time), and — for
+    // small frames — gather the frames of batch k+1 into the page-locked bounce buffer and send them up: 2048
+    // frames of 224 x 224 are 100 MB of host memcpy, 6 % of their batch's compute time when the GPU waits for it.
+    const bool hand = (bounce || out.jpeg) && k >= 1;
+    const bool up_next = k + 1 < plan.size();
+    if (up_next && !bounce_in) { // large frames: a few asynchronous copies to enqueue, nothing to gather
+        rc = upload(k + 1);
+        if (rc != DFX_OK)
+            return rc;
+    }
+    if (hand || (up_next && bounce_in)) {
+        c->helper.start([this, k, hand, up_next] {
+            (void)hipSetDevice(c->device);
+            int r = hand ? hand_over(k - 1) : DFX_OK;
+            if (r == DFX_OK && up_next && bounce_in)
+                r = upload(k + 1);
+            return r;
+        });
+    }
+    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_h2d[par(k)], 0));
+    if (seq0 + k >= 2) // flow staging set par(k) must have been drained by the download of batch q-2
+        HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_d2h[par(k)], 0));
+    return DFX_OK;
+}
+
+int FlowRun::launch_jpeg(size_t k) { // imencode(".jpg") of both planes of every flow, on the device (src/common.cpp:56-57)
+    const int rc = dfx_launch_jpeg(c, par(k), 2 * plan[k].nb, plan[k].nb, c->img_slots);
+    if (rc == DFX_OK)
+        c->stats.kernel_launches += 5;
+    return rc;
+}
+
+int FlowRun::compute(size_t k) { // batch k on the compute stream, up to its statistics and (JPEG) its coded sizes
+    const DfxBatchPlan &p = plan[k];
+    const int q = par(k);
+    int rc;
+    HIPCHK(c, hipEventRecord(c->ev_t0, c->stream));
+    for (int j = 0; j < p.n_new; ++j)
+        c->h_slots[j] = (int)((p.first_new + j) % F);
+    if (p.n_new > 0) {
+        // the new frames: in staging set q (host mode: uploaded there) or in the caller's device array
+        const unsigned char *src = host_mode ? (prep ? c->d_src[q] : c->d_u8[q])
+                                             : in.d_frames + (size_t)p.first_new * in.d_frame_stride;
+        long long pitch = host_mode ? (long long)c->in_row_bytes() : (long long)in.d_pitch;
+        long long stride = !host_mode ? (long long)in.d_frame_stride : prep ? (long long)c->src_frame_bytes : (long long)plane;
+        if (prep) { // cvtColor + cv::resize of load_frames_batch (src/denseflow_gpu.cpp:163, :169), on the device
+            prepare_launch(c->stream, src, pitch, stride, c->src_w, c->src_h, c->src_ch, p.n_new, c->d_u8[q], c->W,
+                           (long long)plane, c->W, c->H);
+            HIPCHK(c, hipGetLastError());
+            c->stats.kernel_launches += 1;
+            src = c->d_u8[q], pitch = c->W, stride = (long long)plane;
+        }
+        rc = E->build_frames(src, stride, pitch, p.n_new, c->h_slots.data());
+        if (rc != DFX_OK)
+            return rc;
+    }
+    // pair i of a clip: a = (step>0 ? i : i-step), b = (step>0 ? i+step : i)   (src/denseflow_gpu.cpp:315-316)
+    for (int j = 0; j < p.nb; ++j) {
+        const int i = p.i0 + j;
+        c->h_pairs[j].frame_a = dfx_pair_a(pairs, i, step) % F;
+        c->h_pairs[j].frame_b = dfx_pair_b(pairs, i, step) % F;
+    }
+    const bool staged = host_mode || out.quantized;
+    float *dst = staged ? c->d_flow_out[q] : out.d_flows + (size_t)p.i0 * out.d_flow_stride;
+    const long long dst_stride = staged ? (long long)plane * 2 : (long long)out.d_flow_stride;
+    rc = E->run_pairs(p.nb, c->h_pairs.data(), dst, dst_stride);
+    if (rc != DFX_OK)
+        return rc;
+    if (out.quantized) {
+        // the bounded planes of this batch: staging set q (host mode), or the caller's device arrays from pair i0 on
+        unsigned char *x = host_mode ? c->d_img[q] : out.d_img_x + (size_t)p.i0 * out.d_img_stride;
+        unsigned char *y = host_mode ? c->d_img[q] + (size_t)c->img_slots * plane : out.d_img_y + (size_t)p.i0 * out.d_img_stride;
+        const long long pitch = host_mode ? c->W : (long long)out.img_pitch;
+        const long long stride = host_mode ? (long long)plane : (long long)out.d_img_stride;
+        if (out.png) { // convertFlowToPngImage's bounds and planes on the device (src/common.cpp:18-46)
+            double *bounds = host_mode ? c->d_png_bounds[q] : out.d_bounds + 2 * (size_t)p.i0;
+            quant_launch_flow_to_png_planes(c->stream, dst, dst_stride, p.nb, c->W, c->H, c->d_png_scratch, bounds, x, y,
+                                            pitch, stride);
+        } else { // convertFlowToImage on the device (src/common.cpp:4-16)
+            quant_launch_flow_to_u8(c->stream, dst, dst_stride, p.nb, c->W, c->H, out.lo, out.hi, x, y, pitch, stride);
+        }
+        HIPCHK(c, hipGetLastError());
+        c->stats.kernel_launches += out.png ? 4 : 1;
+    }
+    if (out.jpeg) {
+        rc = launch_jpeg(k);
+        if (rc != DFX_OK)
+            return rc;
+    }
+    HIPCHK(c, hipEventRecord(c->ev_t1, c->stream));
+    HIPCHK(c, hipEventRecord(c->ev_compute[q], c->stream));
+    HIPCHK(c, dfx_stream_wait(c, c->stream)); // the engines' statistics read-backs are complete
+    float ms = 0.f;
+    HIPCHK(c, hipEventElapsedTime(&ms, c->ev_t0, c->ev_t1));
+    c->stats.device_ms += ms;
+    rc = E->account(p.nb);
+    if (rc != DFX_OK)
+        return rc;
+    rc = c->helper.finish(); // batch k-1 is in the caller's buffers
+    if (rc != DFX_OK)
+        return rc;
+    if (out.png && host_mode) // the stream is idle: this batch's bounds are in the mapped block
+        std::memcpy(out.bounds + 2 * (size_t)p.i0, c->h_png_bounds[q], (size_t)p.nb * 2 * sizeof(double));
+    if (out.jpeg) // a batch that is coded again is coded from its bounded planes in staging set q: no flow is recomputed
+        rc = dfx_jpeg_settle(c, c->jpeg, q, 2 * p.nb, /*idle=*/true, "JPEG",
+                             "JPEG: the batch's streams do not fit the stream buffer (use the 8-bit plane output and encode on "
+                             "the host)",
+                             [&]() -> int {
+                                 const int lrc = launch_jpeg(k);
+                                 if (lrc == DFX_OK)
+                                     HIPCHK(c, hipEventRecord(c->ev_compute[q], c->stream));
+                                 return lrc;
+                             },
+                             &coded[k]);
+    return rc;
+}
+
+// The last batch's download, and its hand-over: now, or (ticket) on a deferred tail, so that the caller can issue the
+// next FlowBuffer while it runs (its uploads run on the other copy stream).
+int FlowRun::finish(uint64_t *ticket) {
+    const size_t last = plan.size() - 1;
+    const int rc = download(last);
+    if (rc != DFX_OK)
+        return rc;
+    if (ticket) {
+        DfxHandover h = describe(last);
+        if (!dfx_may_not_fit(h)) {
+            *ticket = dfx_defer_tail(c, par(last), c->ev_d2h[par(last)],
+                                     [h = std::move(h)](std::string *err) { return dfx_hand_over(h, err); });
+            return DFX_OK;
+        }
+    }
+    HIPCHK(c, dfx_stream_wait(c, c->d2h_stream));
+    return (bounce || out.jpeg) ? hand_over(last) : DFX_OK;
+}
+
+int FlowRun::run(uint64_t *ticket) {
+    int rc = host_mode ? upload(0) : DFX_OK;
+    for (size_t k = 0; rc == DFX_OK && k < plan.size(); ++k) {
+        if (host_mode)
+            rc = overlap_copies(k);
+        if (rc == DFX_OK)
+            rc = compute(k);
+    }
+    if (rc == DFX_OK && host_mode)
+        rc = finish(ticket);
+    return rc;
+}
+
+int flowbuffer_body(dfx_context *c, const InSpec &in, int n_frames, int step, const OutSpec &out, uint64_t *ticket) {
+    // dfx_next_segments applies to this call only, whatever becomes of it
+    std::vector<int> seg;
+    seg.swap(c->next_segments);
+    if (ticket)
+        *ticket = 0;
+    else
+        (void)dfx_finish_tails(c, 0, -1); // synchronous entry points never run beside a deferred tail
+    if (n_frames < 0 || step == 0 || step < -(1 << 30) || step > (1 << 30)) // (|INT_MIN| is not an int)
+        return dfx_fail(c, DFX_ERR_INVALID, "n_frames must be >= 0 and step non-zero");
+    // The FlowBuffer's pairs as (frame a, frame b), frame ids counted over the whole buffer.  One clip: pair i is
+    // (i, i + step) for step > 0, (i - step, i) otherwise, M = max(N - |step|, 0) of them (src/denseflow_gpu.cpp:307-316).
+    // Several clips joined (dfx_next_segments): the same rule inside every clip, no pair across a clip boundary.
+    if (seg.empty())
+        seg.push_back(n_frames);
+    long long total = 0;
+    for (int n : seg) {
+        if (n < 0)
+            return dfx_fail(c, DFX_ERR_INVALID, "dfx_next_segments: negative clip length");
+        total += n;
+    }
+    if (total != n_frames)
+        return dfx_fail(c, DFX_ERR_INVALID, "dfx_next_segments: the clip lengths do not add up to n_frames");
+    FlowRun run(c, in, out, step);
+    const int rc = run.prepare(seg);
+    return rc == DFX_OK && !run.plan.empty() ? run.run(ticket) : rc;
+}
+
+} // namespace
+
+int dfx_run_flowbuffer(dfx_context *c, const InSpec &in, int n_frames, int step, const OutSpec &out, uint64_t *ticket) {
+    if (c->algo == DFX_ALGO_FRAMES) // every flow entry point funnels through here
+        return dfx_fail(c, DFX_ERR_UNSUPPORTED, "a DFX_ALGO_FRAMES handle computes no flow");
+    const int rc = flowbuffer_body(c, in, n_frames, step, out, ticket);
+    if (rc != DFX_OK)
+        dfx_drain_after_error(c);
+    return rc;
+}
+
+int dfx_ensure_img_staging(dfx_context *c, int need) {
+    if (need <= c->img_slots)
+        return DFX_OK;
+    return dfx_regrow(c, c->img_slots, need, [&] { return realloc_pair(c, c->d_img, (size_t)need * 2 * c->W * c->H); });
+}
+
+int dfx_ensure_png(dfx_context *c, int need) {
+    if (need <= c->png_slots)
+        return DFX_OK;
+    return dfx_regrow(c, c->png_slots, need, [&]() -> int {
+        dfx_free_dev(c->d_png_scratch);
+        HIPCHK(c, hipMalloc(&c->d_png_scratch, quant_png_scratch_bytes(need)));
+        for (int p = 0; p < 2; ++p) {
+            dfx_free_host(c->h_png_bounds[p]);
+            HIPCHK(c, hipHostMalloc((void **)&c->h_png_bounds[p], (size_t)need * 2 * sizeof(double), hipHostMallocMapped));
+            HIPCHK(c, hipHostGetDevicePointer((void **)&c->d_png_bounds[p], c->h_png_bounds[p], 0));
+        }
+        return DFX_OK;
+    });
+}
+
+// The shared stream buffer holds 4 bits per pixel on average over the batch (flow planes need ~0.5; a batch that does
+// not fit is measured, and coded again after dfx_jpeg_grow).
+int dfx_ensure_jpeg(dfx_context *c, int pairs, int quality) {
+    auto &j = c->jpeg;
+    if (j.quality == quality && pairs <= j.slots)
+        return DFX_OK;
+    return dfx_regrow(c, j.slots, pairs, [&]() -> int {
+        dfx_jpeg_free(j);
+        const size_t planes = 2 * (size_t)pairs, nblk = (size_t)((c->W + 7) / 8) * ((c->H + 7) / 8);
+        JpegTables t;
+        unsigned char q[64];
+        jpeg_build_tables(quality, t, q);
+        j.header = jpeg_file_header(c->W, c->H, q);
+        HIPCHK(c, hipMalloc(&j.d_tab, sizeof(JpegTables)));
+        HIPCHK(c, hipMemcpy(j.d_tab, &t, sizeof t, hipMemcpyHostToDevice));
+        HIPCHK(c, hipMalloc(&j.d_dc, planes * nblk * sizeof(short)));
+        HIPCHK(c, hipMalloc(&j.d_bits, planes * nblk * sizeof(unsigned)));
+        HIPCHK(c, hipMalloc(&j.d_plane_bits, planes * 8));
+        HIPCHK(c, hipMalloc(&j.d_plane_base, planes * 8));
+        HIPCHK(c, hipMalloc(&j.d_hdr, 16));
+        j.capacity = ((planes * (size_t)c->W * c->H / 2 + (64u << 10)) + 255) & ~(size_t)255;
+        for (int p = 0; p < 2; ++p) {
+            HIPCHK(c, hipMalloc(&j.d_stream[p], j.capacity));
+            // The page-locked landing buffer starts at 1 bit per pixel (flow planes code to ~0.3-0.5) and grows to what a batch
+            // really needs (dfx_jpeg_ensure_landing): pinning 4 bits per pixel twice was ~0.1 s of a 1080p handle's first call
+            // (profiles/round5/e2e/) for bytes that never arrive.
+            j.h_capacity[p] = (j.capacity / 4 + 255) & ~(size_t)255;
+            HIPCHK(c, hipHostMalloc(&j.h_stream[p], j.h_capacity[p], hipHostMallocDefault));
+            HIPCHK(c, hipHostMalloc(&j.h_info[p], (2 + 2 * planes) * 8, hipHostMallocMapped));
+            std::memset(j.h_info[p], 0, (2 + 2 * planes) * 8);
+            HIPCHK(c, hipHostGetDevicePointer((void **)&j.d_info[p], j.h_info[p], 0));
+        }
+        j.quality = quality;
+        return DFX_OK;
+    });
+}
+
+int dfx_launch_jpeg(dfx_context *c, int q, int n_planes, int n_x, int y_first) {
+    const auto &j = c->jpeg;
+    JpegCtx jc;
+    jc.planes = c->d_img[q];
+    jc.plane_stride = (long long)c->W * c->H;
+    jc.pitch = c->W, jc.w = c->W, jc.h = c->H, jc.bw = (c->W + 7) / 8, jc.bh = (c->H + 7) / 8;
+    jc.n_planes = n_planes, jc.n_x = n_x, jc.y_first = y_first;
+    jc.tab = j.d_tab, jc.dc = j.d_dc, jc.bits = j.d_bits;
+    jc.plane_bits = j.d_plane_bits, jc.plane_base = j.d_plane_base;
+    jc.stream = j.d_stream[q], jc.capacity_bytes = j.capacity;
+    jc.info = j.d_info[q], jc.hdr = j.d_hdr;
+    jpeg_launch_encode(c->stream, jc);
+    HIPCHK(c, hipGetLastError());
+    return DFX_OK;
+}

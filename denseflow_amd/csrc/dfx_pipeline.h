@@ -1,0 +1,60 @@
+// dfx_pipeline.h — what the C ABI's entry points (dfx_api.cpp) hand to the FlowBuffer driver (dfx_pipeline.cpp).
+#pragma once
+
+#include "dfx_internal.h"
+
+// Where the frames of a FlowBuffer are: host pointers (host mode) or one device array (device mode).
+struct InSpec {
+    const uint8_t *const *frames = nullptr; // host mode: one pointer per frame, frame_pitch bytes per row
+    size_t frame_pitch = 0;
+    const uint8_t *d_frames = nullptr; // device mode: frame i at d_frames + i * d_frame_stride, d_pitch bytes per row
+    size_t d_pitch = 0, d_frame_stride = 0;
+    static InSpec host(const uint8_t *const *frames, size_t frame_pitch) {
+        InSpec in;
+        in.frames = frames, in.frame_pitch = frame_pitch;
+        return in;
+    }
+    static InSpec device(const uint8_t *d_frames, size_t pitch, size_t frame_stride) {
+        InSpec in;
+        in.d_frames = d_frames, in.d_pitch = pitch, in.d_frame_stride = frame_stride;
+        return in;
+    }
+};
+
+// Where the flows of a FlowBuffer go: float (u, v) fields or planes bounded to 8 bits on the device.
+struct OutSpec {
+    bool quantized = false;
+    double lo = 0, hi = 0;
+    // float output
+    float *const *flows = nullptr; // host mode: one pointer per flow, out_pitch bytes per row
+    size_t out_pitch = 0;
+    float *d_flows = nullptr; // device mode: flow i dense at d_flows + i*d_flow_stride
+    size_t d_flow_stride = 0;
+    // 8-bit output
+    uint8_t *const *img_x = nullptr, *const *img_y = nullptr; // host mode: one pointer per plane
+    size_t img_pitch = 0;                                     // bytes per row (host and device mode)
+    uint8_t *d_img_x = nullptr, *d_img_y = nullptr;           // device mode: plane i at + i*d_img_stride
+    size_t d_img_stride = 0;
+    // the -st=png scheme (implies quantized; lo / hi unused): planes scaled by the reference's per-flow adaptive bounds,
+    // which go to bounds[2 * i] = {bound_x, bound_y} (host mode: filled when the call returns) or d_bounds (device mode)
+    bool png = false;
+    double *bounds = nullptr, *d_bounds = nullptr;
+    // JPEG output (host mode; implies quantized): one file per plane into jpg_x[i] / jpg_y[i] (jpg_capacity bytes each)
+    bool jpeg = false;
+    int quality = 95;
+    uint8_t *const *jpg_x = nullptr, *const *jpg_y = nullptr;
+    size_t jpg_capacity = 0;
+    uint32_t *size_x = nullptr, *size_y = nullptr;
+};
+
+// One FlowBuffer through the handle's engine.  ticket != nullptr (dfx_submit_*): the call returns when the device work is
+// done and every batch but the last has been handed over; dfx_wait(*ticket) awaits the rest.  Consumes dfx_next_segments;
+// after an error nothing is in flight.
+int dfx_run_flowbuffer(dfx_context *c, const InSpec &in, int n_frames, int step, const OutSpec &out, uint64_t *ticket);
+
+// staging that the single-stage entry points of dfx_api.cpp share with the driver
+int dfx_ensure_img_staging(dfx_context *c, int need);      // d_img: `need` x planes, then the y planes, per parity
+int dfx_ensure_png(dfx_context *c, int need);              // scratch and mapped bounds of the -st=png scheme
+int dfx_ensure_jpeg(dfx_context *c, int pairs, int quality); // dfx_context::jpeg for batches of `pairs` pairs
+// The encode of planes already in c->d_img[q] (x planes from index 0, y planes from y_first) into c->jpeg's parity q
+int dfx_launch_jpeg(dfx_context *c, int q, int n_planes, int n_x, int y_first);

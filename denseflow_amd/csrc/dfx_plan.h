@@ -1,5 +1,5 @@
 // dfx_plan.h — the host-side plan of one FlowBuffer: which frame pairs it holds, how they are cut into device batches and
-// which frames every batch has to bring in.  Pure C++ (no HIP): compiled into dfx_api.cpp and, for the CPU suite, into
+// which frames every batch has to bring in.  Pure C++ (no HIP): compiled into dfx_pipeline.cpp and, for the CPU suite, into
 // tests/plan_harness.cpp (tests/test_plan_logic.py checks it against the reference's pair rule and its invariants).
 //
 // Reference: DenseFlow::calc_optflows_imp, /root/reference/src/denseflow_gpu.cpp:307-316 — for a FlowBuffer of N frames

@@ -1,5 +1,5 @@
 // tests/plan_harness.cpp — TEST INFRASTRUCTURE: C wrappers around denseflow_amd/csrc/dfx_plan.h (the pure host logic of
-// a FlowBuffer's batching, the header dfx_api.cpp compiles) so that tests/test_plan_logic.py can drive it on the CPU.
+// a FlowBuffer's batching, the header dfx_pipeline.cpp compiles) so that tests/test_plan_logic.py can drive it on the CPU.
 #include "../denseflow_amd/csrc/dfx_plan.h"
 #include "../denseflow_amd/csrc/farneback_plan.h"
 

@@ -1,4 +1,4 @@
-"""CPU test of the FlowBuffer plan (denseflow_amd/csrc/dfx_plan.h, the header dfx_api.cpp compiles): the pairs of a
+"""CPU test of the FlowBuffer plan (denseflow_amd/csrc/dfx_plan.h, the header dfx_pipeline.cpp compiles): the pairs of a
 FlowBuffer are the reference's (/root/reference/src/denseflow_gpu.cpp:307-316: M = max(N - |step|, 0); flow i is
 (i, i + step) for step > 0, (i - step, i) otherwise) inside every clip and never across a clip boundary; the device batches
 cover every pair once, bring every needed frame in exactly once and in order, and never need more frame slots than
