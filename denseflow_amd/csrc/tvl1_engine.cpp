@@ -309,6 +309,7 @@ int Tvl1Engine::run_pairs(int nb, const PairDesc *h_pairs, float *d_out, long lo
     HIPCHK(c, hipMemcpyAsync(d_pairs, h_pairs_pinned, sizeof(PairDesc) * nb, hipMemcpyHostToDevice, c->stream));
     const int impl = c->prm.impl, math = c->prm.tvl1_math;
     const bool nbr_lds = (c->prm.variant & DFX_VAR_TVL1_STEP_NBR_LDS) != 0;
+    const bool head_regs = (c->prm.variant & DFX_VAR_TVL1_HEAD_NBR_LDS) != 0;
     const float up = (float)(1.0 / c->prm.tvl1_scale_step);
     const int hard_limit = loop.warps * (loop.iterations + 2) + 64;
 
@@ -325,7 +326,7 @@ int Tvl1Engine::run_pairs(int nb, const PairDesc *h_pairs, float *d_out, long lo
             for (int g = 0;; ++g) {
                 for (int i = 0; i < G; ++i) {
                     if (warp_head)
-                        tvl1_launch_warp_head(c->stream, x, step_id, math);
+                        tvl1_launch_warp_head(c->stream, x, step_id, math, head_regs);
                     else if (split_warp)
                         tvl1_launch_warp(c->stream, x, step_id);
                     tvl1_launch_step(c->stream, x, step_id++, impl, math, nbr_lds);

@@ -17,7 +17,8 @@ void tvl1_launch_centered_gradient(hipStream_t s, const float *frame_I, float *f
 void tvl1_launch_level_begin(hipStream_t s, const Tvl1LevelCtx &c, int first_level);
 void tvl1_launch_warp(hipStream_t s, const Tvl1LevelCtx &c, int step_id); // dedicated backward-warp kernel of a step
 // the warp AND the head of the loop it starts (tvl1_head_kernels.hip), in place of tvl1_launch_warp
-void tvl1_launch_warp_head(hipStream_t s, const Tvl1LevelCtx &c, int step_id, int math);
+// (regs: its register form of round 6, DFX_VAR_TVL1_HEAD_NBR_LDS)
+void tvl1_launch_warp_head(hipStream_t s, const Tvl1LevelCtx &c, int step_id, int math, bool regs);
 int tvl1_head_blocks(const Tvl1LevelCtx &c); // workgroups per pair of that launch
 void tvl1_launch_step(hipStream_t s, const Tvl1LevelCtx &c, int step_id, int impl, int math, bool nbr_lds);
 int tvl1_step_blocks(const Tvl1LevelCtx &c, int impl); // workgroups per pair of a step launch

@@ -74,6 +74,7 @@ VAR_TVL1_NO_HEAD = 0x40
 VAR_BROX_SOR_PROGRESS = 0x80
 VAR_BROX_SOR_PER_TILE = 0x100
 VAR_TVL1_STEP_NBR_LDS = 0x200  # TVL1 step kernel in its register form (3 waves per SIMD), not the lean one (4)
+VAR_TVL1_HEAD_NBR_LDS = 0x400  # TVL1 warp-and-head kernel in its register form (3 waves per SIMD), not the lean one (4)
 
 
 class DfxStats(C.Structure):
