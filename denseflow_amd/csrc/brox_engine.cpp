@@ -12,16 +12,15 @@
 
 namespace {
 
-struct BLevel {
-    int w, h, pitch;
-    long long off;
-};
+using BLevel = DfxPlanLevel; // engine_plan.h
 
 class BroxEngine final : public AlgoEngine {
   public:
     explicit BroxEngine(dfx_context *ctx) : c(ctx) {}
     ~BroxEngine() override { destroy(); }
     int create() override;
+    int set_size(int W, int H) override;
+    size_t device_bytes() const override;
     int batch() const override { return B; }
     int ensure_frame_slots(int need) override;
     int frame_slots() const override { return n_frame_slots; }
@@ -32,8 +31,13 @@ class BroxEngine final : public AlgoEngine {
 
   private:
     void destroy();
+    int grow_frame_slots(int need, long long elems);
     BroxLevelCtx level_ctx(int l, int nb) const;
     dfx_context *c;
+    // what the buffers hold, in bytes (they only grow: set_size re-plans the engine inside them); slot_ids: entries of
+    // d_frame_slots / h_slots_pinned; pair_cap: pairs d_pairs / h_pairs_pinned hold
+    size_t frames_cap = 0, planes_cap = 0, sink_cap = 0;
+    int slot_ids = 0, pair_cap = 0;
     std::vector<BLevel> lv;
     long long pyr_elems = 0, frame_elems = 0;
     int n_frame_slots = 0;
@@ -76,57 +80,92 @@ int BroxEngine::create() {
         HIPCHK(c, hipGetDevice(&dev));
         HIPCHK(c, hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
     }
-    // pyramid sizes: scale accumulated in float, ceilf, until a side is <= 15 px or outer_iterations levels
-    {
-        float scale = 1.0f;
-        int pw = c->W, ph = c->H;
-        long long off = 0;
-        lv.push_back(BLevel{c->W, c->H, dfx_round_up(c->W, 64), 0});
-        off += (long long)lv[0].pitch * c->H;
-        while (pw > 15 && ph > 15 && (int)lv.size() < p.brox_outer_iterations && lv.size() < 128) {
-            scale *= p.brox_scale_factor;
-            const int w = (int)std::ceil((float)c->W * scale), h = (int)std::ceil((float)c->H * scale);
-            lv.push_back(BLevel{w, h, dfx_round_up(w, 64), off});
-            off += (long long)lv.back().pitch * h;
-            pw = w;
-            ph = h;
-        }
-        pyr_elems = off;
-        frame_elems = off * BROX_FP_COUNT;
-    }
-    plane_stride = (long long)lv[0].pitch * c->H;
-    slot_stride = plane_stride * BROX_PL_COUNT;
-    B = p.max_batch;
-    if (B <= 0) {
-        const long long px0 = (long long)c->W * c->H;
-        B = (int)std::max<long long>(1, std::min<long long>(DFX_MAX_BATCH, (256LL << 20) / std::max<long long>(px0, 1)));
-    }
-    size_t free_b = 0, total_b = 0;
-    HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
-    const size_t per_pair = (size_t)slot_stride * 4 + (size_t)frame_elems * 4 + (size_t)c->W * c->H * 9;
-    while (B > 1 && per_pair * (size_t)(B + 2) > free_b / 2)
-        B /= 2;
-    HIPCHK(c, hipMalloc(&d_planes, (size_t)slot_stride * B * sizeof(float)));
-    HIPCHK(c, hipMalloc(&d_pairs, sizeof(PairDesc) * B));
-    HIPCHK(c, hipMalloc(&d_sor_sink, sizeof(float) * 16 * (size_t)std::max(n_cu, 1)));
-    HIPCHK(c, hipHostMalloc(&h_pairs_pinned, sizeof(PairDesc) * B, hipHostMallocDefault));
+    // The streaming SOR runs max(n_cu / 8, 1) * 8 persistent workgroups at the most (brox_kernels.hip), whatever the frame
+    // size, and each of them owns 16 floats of the sink: sized once, for that many and no fewer than one per CU.
+    const int wgs = std::max(std::max(n_cu / 8, 1) * 8, std::max(n_cu, 1));
+    HIPCHK(c, hipMalloc(&d_sor_sink, sizeof(float) * 16 * (size_t)wgs));
+    sink_cap = sizeof(float) * 16 * (size_t)wgs;
     HIPCHK(c, hipEventCreateWithFlags(&ev[0], dfx_event_flags(c, true)));
     HIPCHK(c, hipEventCreateWithFlags(&ev[1], dfx_event_flags(c, true)));
-    return ensure_frame_slots(B + 1);
+    return set_size(c->W, c->H);
+}
+
+size_t BroxEngine::device_bytes() const {
+    return frames_cap + planes_cap + sink_cap + sizeof(int) * (size_t)slot_ids + sizeof(PairDesc) * (size_t)pair_cap;
+}
+
+// Plan (engine_plan.h: host arithmetic) + ensure capacity.  Nothing of the engine changes before the last allocation has
+// succeeded; the buffers a failed attempt has already grown stay grown.
+int BroxEngine::set_size(int W, int H) {
+    BroxPlan pl;
+    brox_plan(pl, W, H, c->prm, BROX_FP_COUNT, BROX_PL_COUNT);
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
+    int nB = dfx_plan_fit_batch(pl.batch, pl.per_pair, free_b + device_bytes());
+    const size_t slot_bytes = (size_t)pl.slot_stride * sizeof(float);
+    if (dfx_grow_buf(c, d_planes, planes_cap, slot_bytes * nB) != DFX_OK) {
+        if (planes_cap == 0)
+            B = 0; // not even the array it had came back: no FlowBuffer runs until a dfx_set_size succeeds
+        if (planes_cap < slot_bytes)
+            return DFX_ERR_HIP;
+        nB = (int)std::min<size_t>(planes_cap / slot_bytes, (size_t)nB); // what the allocation it had holds
+    }
+    if (nB > pair_cap) {
+        PairDesc *nd = nullptr, *nh = nullptr;
+        if (hipMalloc(&nd, sizeof(PairDesc) * nB) != hipSuccess ||
+            hipHostMalloc(&nh, sizeof(PairDesc) * nB, hipHostMallocDefault) != hipSuccess) {
+            (void)hipGetLastError();
+            dfx_free_dev(nd);
+            return dfx_fail(c, DFX_ERR_HIP, "brox: allocating the pair descriptors failed");
+        }
+        dfx_free_dev(d_pairs);
+        dfx_free_host(h_pairs_pinned);
+        d_pairs = nd, h_pairs_pinned = nh;
+        pair_cap = nB;
+    }
+    const int rc = grow_frame_slots(nB + 1, pl.frame_elems);
+    if (rc != DFX_OK) { // the engine goes on at its old size, on the frame slots the buffer still holds
+        n_frame_slots = std::min(n_frame_slots, std::min(dfx_slots_in(frames_cap, (size_t)frame_elems * sizeof(float)), slot_ids));
+        return rc;
+    }
+    lv = pl.lv;
+    pyr_elems = pl.pyr_elems;
+    frame_elems = pl.frame_elems;
+    plane_stride = pl.plane_stride;
+    slot_stride = pl.slot_stride;
+    B = nB;
+    n_frame_slots = std::min(dfx_slots_in(frames_cap, (size_t)frame_elems * sizeof(float)), slot_ids);
+    batch_launches = 0;
+    return DFX_OK;
+}
+
+int BroxEngine::grow_frame_slots(int need, long long elems) {
+    const int rc = dfx_grow_buf(c, d_frames, frames_cap, (size_t)need * elems * sizeof(float));
+    if (rc != DFX_OK)
+        return rc;
+    if (need > slot_ids) {
+        int *nd = nullptr, *nh = nullptr;
+        if (hipMalloc(&nd, sizeof(int) * need) != hipSuccess ||
+            hipHostMalloc(&nh, sizeof(int) * need, hipHostMallocDefault) != hipSuccess) {
+            (void)hipGetLastError();
+            dfx_free_dev(nd);
+            return dfx_fail(c, DFX_ERR_HIP, "brox: allocating the frame-slot tables failed");
+        }
+        dfx_free_dev(d_frame_slots);
+        dfx_free_host(h_slots_pinned);
+        d_frame_slots = nd, h_slots_pinned = nh;
+        slot_ids = need;
+    }
+    return DFX_OK;
 }
 
 int BroxEngine::ensure_frame_slots(int need) {
     if (need <= n_frame_slots)
         return DFX_OK;
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    dfx_free_dev(d_frames);
-    dfx_free_dev(d_frame_slots);
-    dfx_free_host(h_slots_pinned);
-    HIPCHK(c, hipMalloc(&d_frames, (size_t)need * frame_elems * sizeof(float)));
-    HIPCHK(c, hipMalloc(&d_frame_slots, sizeof(int) * need));
-    HIPCHK(c, hipHostMalloc(&h_slots_pinned, sizeof(int) * need, hipHostMallocDefault));
-    n_frame_slots = need;
-    return DFX_OK;
+    const int rc = grow_frame_slots(need, frame_elems);
+    n_frame_slots = std::min(dfx_slots_in(frames_cap, (size_t)frame_elems * sizeof(float)), slot_ids);
+    return rc;
 }
 
 int BroxEngine::build_frames(const unsigned char *d_src, long long src_frame_stride, long long src_pitch, int n,

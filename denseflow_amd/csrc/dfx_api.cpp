@@ -6,6 +6,7 @@
 #include <cstring>
 
 #include "dfx_pipeline.h"
+#include "jpeg_kernels.h"
 #include "prepare_kernels.h"
 #include "quantize_kernels.h"
 
@@ -166,6 +167,43 @@ int dfx_create(dfx_handle *out, int device, dfx_algo algo, int width, int height
     return DFX_OK;
 }
 
+int dfx_set_size(dfx_handle h, int width, int height) {
+    if (!h)
+        return DFX_ERR_INVALID;
+    if (width < 1 || height < 1 || width > 32768 || height > 32768) // refused: nothing of the handle changes
+        return dfx_fail(h, DFX_ERR_INVALID, "invalid frame size");
+    // everything outstanding first: deferred tails hold sizes and buffers of the current geometry
+    (void)dfx_finish_tails(h, 0, -1);
+    h->clear_segments();
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->copy_stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->d2h_stream));
+    // the current size again takes the same path: the engine is re-planned and its control state restarts
+    const int rc = h->engine->set_size(width, height); // plan + ensure capacity; a failure leaves the engine as it was
+    if (rc != DFX_OK)
+        return rc;
+    h->W = width;
+    h->H = height;
+    dfx_pipeline_resized(h);
+    dfx_colour_resized(h);
+    h->src_w = h->src_h = 0;
+    h->src_ch = 1;
+    return DFX_OK;
+}
+
+size_t dfx_device_bytes(dfx_handle h) {
+    if (!h)
+        return 0;
+    const auto &j = h->jpeg;
+    size_t n = h->engine ? h->engine->device_bytes() : 0;
+    n += 2 * (h->u8_bytes + h->flow_bytes + h->src_bytes + h->img_bytes);
+    n += h->d_png_scratch ? quant_png_scratch_bytes(h->png_slots) : 0;
+    n += (j.d_tab ? sizeof(JpegTables) : 0) + j.blocks_cap * (sizeof(short) + sizeof(unsigned)) + j.planes_cap * 16 +
+         (j.d_hdr ? 16 : 0) + 2 * j.capacity;
+    return n + h->colour.device_bytes;
+}
+
 namespace {
 // dfx_next_segments applies to the NEXT calc / submit call only, whether that call succeeds or not (include/dfx.h).  The
 // list is consumed inside dfx_run_flowbuffer, which a call rejected by its wrapper's argument checks never reaches: every
@@ -175,13 +213,20 @@ struct SegmentsScope {
     explicit SegmentsScope(dfx_context *ctx) : c(ctx) {}
     ~SegmentsScope() {
         if (c)
-            c->next_segments.clear();
+            c->clear_segments();
     }
     void hand_over() { c = nullptr; } // another entry point takes over (dfx_calc -> dfx_calc_batch)
 };
 // |step| for the wrappers' early size computations; INT_MIN (whose negation is not an int) saturates, and the body
 // rejects it with every other out-of-range step.
 inline int abs_step(int step) { return step == INT_MIN ? INT_MAX : std::abs(step); }
+// frame_pitch of a host-pointer call: checked against the handle's input rows, unless a dfx_next_segments_src declaration
+// is pending (every clip then has its own pitch, checked when it was declared, and the call's is ignored)
+inline bool pitch_too_small(dfx_handle h, size_t frame_pitch) {
+    return h->next_seg_fmt.empty() && frame_pitch < h->in_row_bytes();
+}
+// the device-resident forms have one format for the whole array
+inline bool src_segments_pending(dfx_handle h) { return !h->next_seg_fmt.empty(); }
 } // namespace
 
 int dfx_calc(dfx_handle h, const uint8_t *a, size_t a_pitch, const uint8_t *b, size_t b_pitch, float *flow_uv,
@@ -229,7 +274,7 @@ int float_entry(dfx_handle h, const uint8_t *const *frames, size_t frame_pitch, 
     const int M = std::max(n_frames - abs_step(step), 0);
     if (M > 0 && (!frames || !flows_uv))
         return dfx_fail(h, DFX_ERR_INVALID, "NULL frames or flows array");
-    if (M > 0 && (frame_pitch < h->in_row_bytes() || out_pitch < (size_t)h->W * 8))
+    if (M > 0 && (pitch_too_small(h, frame_pitch) || out_pitch < (size_t)h->W * 8))
         return dfx_fail(h, DFX_ERR_INVALID, "pitch smaller than a row");
     OutSpec out;
     out.flows = flows_uv;
@@ -245,7 +290,7 @@ int u8_entry(dfx_handle h, const uint8_t *const *frames, size_t frame_pitch, int
     const int M = std::max(n_frames - abs_step(step), 0);
     if (M > 0 && (!frames || !img_x || !img_y))
         return dfx_fail(h, DFX_ERR_INVALID, "NULL frames or image plane array");
-    if (M > 0 && (frame_pitch < h->in_row_bytes() || img_pitch < (size_t)h->W))
+    if (M > 0 && (pitch_too_small(h, frame_pitch) || img_pitch < (size_t)h->W))
         return dfx_fail(h, DFX_ERR_INVALID, "pitch smaller than a row");
     OutSpec out;
     out.quantized = true;
@@ -263,7 +308,7 @@ int png_entry(dfx_handle h, const uint8_t *const *frames, size_t frame_pitch, in
     const int M = std::max(n_frames - abs_step(step), 0);
     if (M > 0 && (!frames || !img_x || !img_y || !bounds_xy))
         return dfx_fail(h, DFX_ERR_INVALID, "NULL frames, image plane array or bounds array");
-    if (M > 0 && (frame_pitch < h->in_row_bytes() || img_pitch < (size_t)h->W))
+    if (M > 0 && (pitch_too_small(h, frame_pitch) || img_pitch < (size_t)h->W))
         return dfx_fail(h, DFX_ERR_INVALID, "pitch smaller than a row");
     OutSpec out;
     out.quantized = out.png = true;
@@ -280,7 +325,7 @@ int jpeg_entry(dfx_handle h, const uint8_t *const *frames, size_t frame_pitch, i
     const int M = std::max(n_frames - abs_step(step), 0);
     if (M > 0 && (!frames || !jpg_x || !jpg_y || !size_x || !size_y))
         return dfx_fail(h, DFX_ERR_INVALID, "NULL frames, JPEG buffer or size array");
-    if (M > 0 && frame_pitch < h->in_row_bytes())
+    if (M > 0 && pitch_too_small(h, frame_pitch))
         return dfx_fail(h, DFX_ERR_INVALID, "pitch smaller than a row");
     if (quality < 1 || quality > 100)
         return dfx_fail(h, DFX_ERR_INVALID, "JPEG quality must be 1..100");
@@ -357,6 +402,8 @@ int dfx_calc_batch_device(dfx_handle h, const uint8_t *d_frames, size_t pitch, s
     if (!h)
         return DFX_ERR_INVALID;
     SegmentsScope seg_scope(h);
+    if (src_segments_pending(h))
+        return dfx_fail(h, DFX_ERR_UNSUPPORTED, "dfx_next_segments_src applies to host-pointer calls only");
     const int M = std::max(n_frames - abs_step(step), 0);
     if (M > 0 && (!d_frames || !d_flows))
         return dfx_fail(h, DFX_ERR_INVALID, "NULL device frames or flows");
@@ -375,6 +422,8 @@ int dfx_calc_batch_png_device(dfx_handle h, const uint8_t *d_frames, size_t pitc
     if (!h)
         return DFX_ERR_INVALID;
     SegmentsScope seg_scope(h);
+    if (src_segments_pending(h))
+        return dfx_fail(h, DFX_ERR_UNSUPPORTED, "dfx_next_segments_src applies to host-pointer calls only");
     const int M = std::max(n_frames - abs_step(step), 0);
     if (M > 0 && (!d_frames || !d_img_x || !d_img_y || !d_bounds_xy))
         return dfx_fail(h, DFX_ERR_INVALID, "NULL device frames, image planes or bounds");
@@ -405,13 +454,16 @@ int dfx_encode_jpeg(dfx_handle h, const uint8_t *const *planes, size_t pitch, in
         return dfx_fail(h, DFX_ERR_INVALID, "JPEG quality must be 1..100");
     HIPCHK(h, hipSetDevice(h->device));
     const int B = h->engine->batch();
+    if (B < 1)
+        return dfx_fail(h, DFX_ERR_HIP, "the engine holds no pair slots (a dfx_set_size failed for lack of memory): set a size again");
     int rc = dfx_ensure_img_staging(h, B);
     if (rc == DFX_OK)
         rc = dfx_ensure_jpeg(h, B, quality);
     if (rc != DFX_OK)
         return rc;
     const size_t plane = (size_t)h->W * h->H;
-    const int chunk_max = 2 * h->img_slots; // a staging set holds that many planes back to back
+    // a staging set holds 2 * img_slots planes back to back (after dfx_set_size possibly more than the encoder is sized for)
+    const int chunk_max = 2 * std::min(h->img_slots, h->jpeg.slots);
     for (int i0 = 0; i0 < n; i0 += chunk_max) {
         const int nc = std::min(chunk_max, n - i0);
         for (int j = 0; j < nc; ++j)
@@ -454,16 +506,44 @@ size_t dfx_jpeg_capacity(dfx_handle h) {
 int dfx_next_segments(dfx_handle h, const int *seg_frames, int n_segments) {
     if (!h)
         return DFX_ERR_INVALID;
-    h->next_segments.clear();
+    h->clear_segments();
     if (n_segments < 0 || (n_segments > 0 && !seg_frames))
         return dfx_fail(h, DFX_ERR_INVALID, "dfx_next_segments: NULL clip lengths");
     for (int i = 0; i < n_segments; ++i) {
         if (seg_frames[i] < 0) {
-            h->next_segments.clear();
+            h->clear_segments();
             return dfx_fail(h, DFX_ERR_INVALID, "dfx_next_segments: negative clip length");
         }
         h->next_segments.push_back(seg_frames[i]);
     }
+    return DFX_OK;
+}
+
+int dfx_next_segments_src(dfx_handle h, const int *seg_frames, const int *seg_src_wh, const size_t *seg_pitch,
+                          int n_segments, int channels) {
+    if (!h)
+        return DFX_ERR_INVALID;
+    h->clear_segments();
+    if (n_segments == 0)
+        return DFX_OK;
+    if (n_segments < 0 || !seg_frames || !seg_src_wh || !seg_pitch)
+        return dfx_fail(h, DFX_ERR_INVALID, "dfx_next_segments_src: NULL clip lengths, sizes or pitches");
+    if (channels != 1 && channels != 3)
+        return dfx_fail(h, DFX_ERR_INVALID, "channels must be 1 (gray) or 3 (BGR)");
+    for (int i = 0; i < n_segments; ++i) {
+        const int w = seg_src_wh[2 * i], hh = seg_src_wh[2 * i + 1];
+        const char *bad = seg_frames[i] < 0                                   ? "dfx_next_segments_src: negative clip length"
+                          : (w < 1 || hh < 1 || w > 32768 || hh > 32768)      ? "invalid source frame size"
+                          : seg_pitch[i] < (size_t)w * (size_t)channels       ? "pitch smaller than a row"
+                                                                              : nullptr;
+        if (bad) {
+            h->clear_segments();
+            return dfx_fail(h, DFX_ERR_INVALID, bad);
+        }
+        h->next_segments.push_back(seg_frames[i]);
+        h->next_seg_fmt.push_back({w, hh, seg_pitch[i]});
+    }
+    h->next_seg_ch = channels;
     return DFX_OK;
 }
 
@@ -479,6 +559,8 @@ int dfx_calc_batch_u8_device(dfx_handle h, const uint8_t *d_frames, size_t pitch
     if (!h)
         return DFX_ERR_INVALID;
     SegmentsScope seg_scope(h);
+    if (src_segments_pending(h))
+        return dfx_fail(h, DFX_ERR_UNSUPPORTED, "dfx_next_segments_src applies to host-pointer calls only");
     const int M = std::max(n_frames - abs_step(step), 0);
     if (M > 0 && (!d_frames || !d_img_x || !d_img_y))
         return dfx_fail(h, DFX_ERR_INVALID, "NULL device frames or image planes");

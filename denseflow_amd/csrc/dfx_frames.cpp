@@ -18,6 +18,8 @@ class FramesEngine : public AlgoEngine {
   public:
     explicit FramesEngine(dfx_context *c) : c_(c) {}
     int create() override { return DFX_OK; }
+    int set_size(int, int) override { return DFX_OK; } // the colour state follows at its next use (ensure_colour)
+    size_t device_bytes() const override { return 0; }  // that state is counted on its own (dfx_frames_device_bytes)
     int batch() const override;
     int ensure_frame_slots(int) override { return refuse(); }
     int frame_slots() const override { return 0; }
@@ -30,22 +32,22 @@ class FramesEngine : public AlgoEngine {
     dfx_context *c_;
 };
 
-// Frames per device batch: dfx_params.max_batch, or 32 Mpx of output frames (16 at 1080p: 100 MB of source frames per
-// staging parity, enough blocks — 780 000 — to fill the device many times over).
-int frames_batch(const dfx_context *c) {
-    if (c->prm.max_batch > 0)
-        return c->prm.max_batch;
-    const long long px = (long long)c->W * c->H;
-    return (int)std::max<long long>(1, std::min<long long>(256, (32ll << 20) / px));
-}
+int frames_batch(const dfx_context *c) { return frames_plan_batch(c->W, c->H, c->prm.max_batch); } // engine_plan.h
 
 int FramesEngine::batch() const { return frames_batch(c_); }
 
 size_t round4(size_t v) { return (v + 3) & ~(size_t)3; }
 
-template <class T> int dev_alloc(dfx_context *c, T *&p, size_t bytes) {
-    HIPCHK(c, hipMalloc((void **)&p, bytes));
-    c->colour.device_bytes += bytes;
+// p holds `need` bytes of device memory (cap: what it holds now); the colour state's byte count follows
+template <class T> int dev_grow(dfx_context *c, T *&p, size_t &cap, size_t need) {
+    if (need <= cap)
+        return DFX_OK;
+    dfx_free_dev(p);
+    c->colour.device_bytes -= cap;
+    cap = 0;
+    HIPCHK(c, hipMalloc((void **)&p, need));
+    cap = need;
+    c->colour.device_bytes += need;
     return DFX_OK;
 }
 
@@ -56,51 +58,74 @@ void free_staging(dfx_context *c) {
     dfx_free_dev(j.d_bgr);
     j.src_slots = j.bgr_slots = 0;
     j.src_pitch = j.src_frame_bytes = 0;
+    j.src_cap[0] = j.src_cap[1] = j.bgr_cap = 0;
+    j.tab_cap = j.dc_cap = j.bits_cap = j.pbits_cap = j.pbase_cap = j.hdr_cap = j.stream_cap[0] = j.stream_cap[1] = 0;
+    j.info_slots = 0;
 }
 
-// Everything of the colour state, sized for batches of `frames` frames at `quality` from sw x sh sources.  Any change
-// re-allocates the lot (a handle is used with one source size and one quality).
+// Everything of the colour state, for batches of `frames` frames at `quality` from sw x sh sources into the handle's
+// W x H.  Every buffer is kept by what it holds and only grows: another source size, output size (dfx_set_size) or
+// quality re-uses what is large enough, and a handle that sees one of each allocates what it always did.
 int ensure_colour(dfx_context *c, int frames, int quality, int sw, int sh) {
     auto &j = c->colour;
     const bool resize = sw != c->W || sh != c->H;
     const size_t sp = round4((size_t)sw * 3), fb = sp * (size_t)sh;
-    if (j.quality == quality && frames <= j.slots && frames <= j.src_slots && j.src_frame_bytes == fb && j.src_pitch == sp &&
-        (!resize || frames <= j.bgr_slots))
+    if (j.quality == quality && j.hdr_w == c->W && j.hdr_h == c->H && frames <= j.slots && frames <= j.src_slots &&
+        j.src_frame_bytes == fb && j.src_pitch == sp && (!resize || frames <= j.bgr_slots))
         return DFX_OK;
     return dfx_regrow(c, j.slots, frames, [&]() -> int {
-        dfx_jpeg_free(c->colour);
-        free_staging(c);
-        j.device_bytes = 0;
+        j.hdr_w = j.hdr_h = 0;
+        j.quality = 0;
+        j.src_slots = j.bgr_slots = 0;
         const size_t mcus = (size_t)((c->W + 15) / 16) * ((c->H + 15) / 16), nblk = mcus * 6;
         JpegTables t[2];
         jpeg_build_colour_tables(quality, t);
         j.header = jpeg_colour_file_header(c->W, c->H, quality);
-        int rc = dev_alloc(c, j.d_tab, sizeof t);
+        int rc = dev_grow(c, j.d_tab, j.tab_cap, sizeof t);
         if (rc != DFX_OK)
             return rc;
         HIPCHK(c, hipMemcpy(j.d_tab, t, sizeof t, hipMemcpyHostToDevice));
-        if ((rc = dev_alloc(c, j.d_dc, (size_t)frames * nblk * sizeof(short))) != DFX_OK ||
-            (rc = dev_alloc(c, j.d_bits, (size_t)frames * nblk * sizeof(unsigned))) != DFX_OK ||
-            (rc = dev_alloc(c, j.d_plane_bits, (size_t)frames * 8)) != DFX_OK ||
-            (rc = dev_alloc(c, j.d_plane_base, (size_t)frames * 8)) != DFX_OK || (rc = dev_alloc(c, j.d_hdr, 16)) != DFX_OK)
+        if ((rc = dev_grow(c, j.d_dc, j.dc_cap, (size_t)frames * nblk * sizeof(short))) != DFX_OK ||
+            (rc = dev_grow(c, j.d_bits, j.bits_cap, (size_t)frames * nblk * sizeof(unsigned))) != DFX_OK ||
+            (rc = dev_grow(c, j.d_plane_bits, j.pbits_cap, (size_t)frames * 8)) != DFX_OK ||
+            (rc = dev_grow(c, j.d_plane_base, j.pbase_cap, (size_t)frames * 8)) != DFX_OK ||
+            (rc = dev_grow(c, j.d_hdr, j.hdr_cap, 16)) != DFX_OK)
             return rc;
         // shared stream buffer: 4 bits per pixel on average over the batch (a photographic frame at quality 95 needs 1.5 - 3;
         // a batch that does not fit is measured and coded again after dfx_jpeg_grow)
-        j.capacity = (((size_t)frames * c->W * c->H / 2 + (64u << 10)) + 255) & ~(size_t)255;
+        const size_t cap = (((size_t)frames * c->W * c->H / 2 + (64u << 10)) + 255) & ~(size_t)255;
         for (int p = 0; p < 2; ++p) {
-            if ((rc = dev_alloc(c, j.d_stream[p], j.capacity)) != DFX_OK)
+            j.stream_cap[p] = std::max(j.stream_cap[p], j.d_stream[p] ? j.capacity : (size_t)0); // dfx_jpeg_grow may have grown it
+            if ((rc = dev_grow(c, j.d_stream[p], j.stream_cap[p], cap)) != DFX_OK)
                 return rc;
-            j.h_capacity[p] = j.capacity;
-            HIPCHK(c, hipHostMalloc((void **)&j.h_stream[p], j.h_capacity[p], hipHostMallocDefault));
-            HIPCHK(c, hipHostMalloc((void **)&j.h_info[p], (2 + 2 * (size_t)frames) * 8, hipHostMallocMapped));
-            std::memset(j.h_info[p], 0, (2 + 2 * (size_t)frames) * 8);
-            HIPCHK(c, hipHostGetDevicePointer((void **)&j.d_info[p], j.h_info[p], 0));
-            if ((rc = dev_alloc(c, j.d_src[p], (size_t)frames * fb)) != DFX_OK)
+            if (cap > j.h_capacity[p]) {
+                j.h_capacity[p] = 0;
+                dfx_free_host(j.h_stream[p]);
+                HIPCHK(c, hipHostMalloc((void **)&j.h_stream[p], cap, hipHostMallocDefault));
+                j.h_capacity[p] = cap;
+            }
+        }
+        j.capacity = std::min(j.stream_cap[0], j.stream_cap[1]);
+        if (frames > j.info_slots) {
+            j.info_slots = 0;
+            for (int p = 0; p < 2; ++p) {
+                dfx_free_host(j.h_info[p]);
+                j.d_info[p] = nullptr;
+                HIPCHK(c, hipHostMalloc((void **)&j.h_info[p], (2 + 2 * (size_t)frames) * 8, hipHostMallocMapped));
+                HIPCHK(c, hipHostGetDevicePointer((void **)&j.d_info[p], j.h_info[p], 0));
+            }
+            j.info_slots = frames;
+        }
+        for (int p = 0; p < 2; ++p) {
+            std::memset(j.h_info[p], 0, (2 + 2 * (size_t)j.info_slots) * 8);
+            if ((rc = dev_grow(c, j.d_src[p], j.src_cap[p], (size_t)frames * fb)) != DFX_OK)
                 return rc;
         }
-        if (resize && (rc = dev_alloc(c, j.d_bgr, (size_t)frames * round4((size_t)c->W * 3) * c->H)) != DFX_OK)
+        const size_t out_frame = round4((size_t)c->W * 3) * c->H;
+        if (resize && (rc = dev_grow(c, j.d_bgr, j.bgr_cap, (size_t)frames * out_frame)) != DFX_OK)
             return rc;
         j.quality = quality;
+        j.hdr_w = c->W, j.hdr_h = c->H;
         j.src_slots = frames;
         j.bgr_slots = resize ? frames : 0;
         j.src_pitch = sp;
@@ -251,6 +276,8 @@ int extract_entry(dfx_handle h, const uint8_t *const *frames, size_t pitch, int 
 } // namespace
 
 AlgoEngine *dfx_make_frames_engine(dfx_context *c) { return new FramesEngine(c); }
+
+void dfx_colour_resized(dfx_context *c) { c->colour.slots = 0; } // ensure_colour works everything out again, in place
 
 void dfx_free_colour(dfx_context *c) {
     dfx_jpeg_free(c->colour);

@@ -21,6 +21,7 @@
 #include "dfx_device.h"
 #include "dfx_handover.h"
 #include "dfx_helper.h"
+#include "engine_plan.h"
 
 // An algorithm engine owns every device buffer of one handle.  The common driver (dfx_pipeline.cpp)
 // walks a FlowBuffer in batches of `batch()` pairs, keeps the per-frame derived data (pyramids,
@@ -30,15 +31,15 @@
 //     account       - fold the finished batch into dfx_stats (after the stream is synchronised)
 struct dfx_context;
 
-// Automatic batch (dfx_params.max_batch = 0): as many pairs as 256 Mpx of level-0 pixels hold (129 at 1080p), at most
-// this many.  Small frames reach it: 2048 pairs of 224 x 224 are 103 Mpx — 0.4 of the 1080p batch — and a FlowBuffer
-// only fills such a batch when it joins several clips (dfx_next_segments).
-constexpr long long DFX_MAX_BATCH = 2048;
-
 class AlgoEngine {
   public:
     virtual ~AlgoEngine() {}
     virtual int create() = 0;
+    // dfx_set_size: plan the engine for W x H frames (engine_plan.h) and make every buffer hold what the plan needs; a
+    // buffer that is large enough stays as it is.  create() runs the same two steps on an empty engine.  The context is
+    // idle.  A failure leaves the engine at its previous size, in buffers that still hold it.
+    virtual int set_size(int W, int H) = 0;
+    virtual size_t device_bytes() const = 0; // device memory the engine holds
     virtual int batch() const = 0;
     virtual int ensure_frame_slots(int need) = 0;
     virtual int frame_slots() const = 0;
@@ -58,6 +59,8 @@ class AlgoEngine {
 // the device reports (dfx_streams.cpp).
 struct JpegStreams {
     int quality = 0, slots = 0; // what the buffers below are sized for (slots: pairs of a flow batch / colour frames)
+    int hdr_w = 0, hdr_h = 0;   // frame size `header` and `slots` were worked out for (the gray encoder: dfx_ensure_jpeg)
+    size_t blocks_cap = 0, planes_cap = 0; // gray encoder: 8 x 8 blocks d_dc / d_bits hold, planes the per-plane arrays hold
     struct JpegTables *d_tab = nullptr;
     short *d_dc = nullptr;
     unsigned *d_bits = nullptr;
@@ -108,6 +111,8 @@ struct dfx_context {
 
     // staging shared by every engine
     // host-mode staging, two sets each so that copies of batch i+-1 overlap the compute of batch i
+    // The buffers are kept by their size in bytes (dfx_set_size re-plans a handle inside them); the slot counts are what
+    // those bytes hold at the current W x H / source format.
     unsigned char *d_u8[2] = {nullptr, nullptr}; // u8_slots dense W*H frames per set
     int u8_slots = 0;
     float *d_flow_out[2] = {nullptr, nullptr};   // flow_slots dense H*W*2 flows per set
@@ -115,6 +120,7 @@ struct dfx_context {
     unsigned char *d_src[2] = {nullptr, nullptr}; // source-format frames before preparation (src_slots per set)
     int src_slots = 0;
     size_t src_frame_bytes = 0;
+    size_t u8_bytes = 0, flow_bytes = 0, src_bytes = 0, img_bytes = 0; // per set
     // page-locked bounce buffers for FlowBuffers of small frames: one copy per batch instead of one per frame
     unsigned char *h_in[2] = {nullptr, nullptr}, *h_out[2] = {nullptr, nullptr};
     size_t h_in_bytes = 0, h_out_bytes = 0;
@@ -138,6 +144,10 @@ struct dfx_context {
         size_t src_pitch = 0, src_frame_bytes = 0;
         unsigned char *d_bgr = nullptr; // bgr_slots frames of W x H (only when the source size differs)
         int bgr_slots = 0;
+        // what the buffers hold, in bytes (they only grow: dfx_frames.cpp ensure_colour); info_slots: frames h_info holds
+        size_t src_cap[2] = {0, 0}, bgr_cap = 0, tab_cap = 0, dc_cap = 0, bits_cap = 0, pbits_cap = 0, pbase_cap = 0,
+               hdr_cap = 0, stream_cap[2] = {0, 0};
+        int info_slots = 0;
         unsigned long long seq = 0;   // device batches are numbered across calls: parity = seq & 1
         size_t device_bytes = 0;      // device memory held by this state
     } colour;
@@ -150,6 +160,18 @@ struct dfx_context {
     // Batches are numbered across calls: staging set, bounce buffer and event of batch q are those of parity q & 1.
     unsigned long long batch_seq = 0;
     std::vector<int> next_segments; // dfx_next_segments: clip lengths of the NEXT FlowBuffer (consumed by that call)
+    // dfx_next_segments_src: with every clip's own source format (one entry per clip, or none), channels common to them
+    struct SegFormat {
+        int w, h;
+        size_t pitch;
+    };
+    std::vector<SegFormat> next_seg_fmt;
+    int next_seg_ch = 1;
+    void clear_segments() {
+        next_segments.clear();
+        next_seg_fmt.clear();
+        next_seg_ch = 1;
+    }
     // Deferred tails of dfx_submit_*: the last download of a FlowBuffer (and, for small frames, the hand-over from
     // the bounce buffer to the caller's buffers) completes on a helper thread while the next FlowBuffer is issued.
     // A tail stays registered in `tails` until its worker has FINISHED (done, set under tails_mtx): whoever asks about
@@ -235,6 +257,17 @@ template <class T> inline void dfx_free_host(T *&p) {
     }
 }
 
+// Slots of `each` bytes that a buffer of `bytes` holds, as an int.
+inline int dfx_slots_in(size_t bytes, size_t each) {
+    return each ? (int)std::min<size_t>(bytes / each, (size_t)1 << 30) : 0;
+}
+
+// A buffer that only grows (the engines' set_size): `cap` is what p holds, in bytes.  Large enough: untouched.  Otherwise
+// the old buffer is freed first (a pair-slot array is most of a handle's memory: two of them may not fit) and, should the
+// new allocation fail, allocated again at its old size, so that the owner can go on at the size it had.  host_flags < 0:
+// device memory, otherwise hipHostMalloc with these flags.  Nothing may be using the buffer.
+template <class T> inline int dfx_grow_buf(dfx_context *c, T *&p, size_t &cap, size_t need, int host_flags = -1);
+
 // Grow a set of buffers that is sized for `count` slots to `need`: nothing may use the old ones (deferred tails, device
 // work), and `alloc` — which frees them and allocates the new ones — may fail half-way.
 template <class N, class F> inline int dfx_regrow(dfx_context *c, N &count, N need, F alloc) {
@@ -246,6 +279,39 @@ template <class N, class F> inline int dfx_regrow(dfx_context *c, N &count, N ne
         count = need;
     return rc;
 }
+
+template <class T> inline int dfx_grow_buf(dfx_context *c, T *&p, size_t &cap, size_t need, int host_flags) {
+    if (need <= cap)
+        return DFX_OK;
+    const auto alloc = [&](size_t bytes) {
+        return host_flags < 0 ? hipMalloc((void **)&p, bytes) : hipHostMalloc((void **)&p, bytes, (unsigned)host_flags);
+    };
+    if (host_flags < 0)
+        dfx_free_dev(p);
+    else
+        dfx_free_host(p);
+    const hipError_t e = alloc(need);
+    if (e == hipSuccess) {
+        cap = need;
+        return DFX_OK;
+    }
+    (void)hipGetLastError();
+    p = nullptr;
+    if (cap > 0 && alloc(cap) != hipSuccess) {
+        (void)hipGetLastError();
+        p = nullptr;
+        cap = 0;
+    }
+    char buf[256];
+    snprintf(buf, sizeof buf, "allocating %zu bytes failed: %s", need, hipGetErrorString(e));
+    c->set_err(buf);
+    return DFX_ERR_HIP;
+}
+
+// dfx_set_size: the shared staging of dfx_pipeline.cpp re-counted for the context's new W x H (nothing is allocated)
+void dfx_pipeline_resized(dfx_context *c);
+// dfx_set_size: the colour state follows the new W x H at its next use (dfx_frames.cpp)
+void dfx_colour_resized(dfx_context *c);
 
 // ---- JPEG stream state (dfx_streams.cpp) ----
 void dfx_jpeg_free(JpegStreams &j);

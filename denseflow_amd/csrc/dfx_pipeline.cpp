@@ -30,15 +30,20 @@ template <class T> int realloc_pair(dfx_context *c, T *(&pair)[2], size_t bytes,
     return DFX_OK;
 }
 
-int ensure_src_staging(dfx_context *c, int need) {
-    const size_t fb = c->in_row_bytes() * c->in_h();
-    if (need <= c->src_slots && fb == c->src_frame_bytes)
+// The staging sets are kept by their size in bytes and only grow: a set that holds `need` slots at the current frame size
+// (after dfx_set_size or another source format: more or fewer than it was allocated for) is used as it is.
+int ensure_src_staging(dfx_context *c, int need, size_t fb) { // fb: bytes of a staging slot (the largest source frame)
+    if (fb != c->src_frame_bytes) { // another source format: re-count what the buffers hold
+        c->src_frame_bytes = fb;
+        c->src_slots = dfx_slots_in(c->src_bytes, fb);
+    }
+    if (need <= c->src_slots)
         return DFX_OK;
     return dfx_regrow(c, c->src_slots, need, [&]() -> int {
-        c->src_frame_bytes = 0;
+        c->src_bytes = 0;
         const int rc = realloc_pair(c, c->d_src, (size_t)need * fb);
         if (rc == DFX_OK)
-            c->src_frame_bytes = fb;
+            c->src_bytes = (size_t)need * fb;
         return rc;
     });
 }
@@ -56,10 +61,21 @@ int ensure_staging(dfx_context *c, int u8_need, int flow_need) {
     const size_t plane = (size_t)c->W * c->H;
     int rc = DFX_OK;
     if (u8_need > c->u8_slots)
-        rc = dfx_regrow(c, c->u8_slots, u8_need, [&] { return realloc_pair(c, c->d_u8, (size_t)u8_need * plane); });
+        rc = dfx_regrow(c, c->u8_slots, u8_need, [&]() -> int {
+            c->u8_bytes = 0;
+            const int arc = realloc_pair(c, c->d_u8, (size_t)u8_need * plane);
+            if (arc == DFX_OK)
+                c->u8_bytes = (size_t)u8_need * plane;
+            return arc;
+        });
     if (rc == DFX_OK && flow_need > c->flow_slots)
-        rc = dfx_regrow(c, c->flow_slots, flow_need,
-                        [&] { return realloc_pair(c, c->d_flow_out, (size_t)flow_need * plane * 2 * sizeof(float)); });
+        rc = dfx_regrow(c, c->flow_slots, flow_need, [&]() -> int {
+            c->flow_bytes = 0;
+            const int arc = realloc_pair(c, c->d_flow_out, (size_t)flow_need * plane * 2 * sizeof(float));
+            if (arc == DFX_OK)
+                c->flow_bytes = (size_t)flow_need * plane * 2 * sizeof(float);
+            return arc;
+        });
     return rc;
 }
 
@@ -93,6 +109,18 @@ struct FlowRun {
     bool host_mode = false, prep = false, bounce_in = false, bounce = false;
     size_t plane = 0;
     std::vector<DfxJpegCoded> coded; // JPEG mode: what the device reported for each batch
+    // Source format of the host frames.  Normally the handle's (dfx_set_source_format) for every frame; under
+    // dfx_next_segments_src every clip has its own size and pitch (clip_fmt, clip_of[frame id]), and the staging slots
+    // are sized for the largest of them.  Rows are dense in the staging set.
+    std::vector<dfx_context::SegFormat> clip_fmt;
+    std::vector<int> clip_of;
+    int seg_ch = 1, src_ch = 1;
+    size_t src_stride = 0; // bytes between the frames of a staging set / bounce buffer
+    dfx_context::SegFormat fmt(long long f) const {
+        if (clip_fmt.empty())
+            return {c->in_w(), c->in_h(), in.frame_pitch};
+        return clip_fmt[clip_of[(size_t)f]];
+    }
 
     FlowRun(dfx_context *ctx, const InSpec &i, const OutSpec &o, int s) : c(ctx), in(i), out(o), step(s) {}
     ~FlowRun() { (void)c->helper.finish(); }
@@ -119,16 +147,28 @@ int FlowRun::prepare(const std::vector<int> &seg) {
     HIPCHK(c, hipSetDevice(c->device));
     E = c->engine;
     int B = E->batch();
+    if (B < 1) // a dfx_set_size that failed could not even get the engine's old buffers back
+        return dfx_fail(c, DFX_ERR_HIP, "the engine holds no pair slots (a dfx_set_size failed for lack of memory): set a size again");
     const int F_need = std::max(dfx_frames_needed(pairs, B), std::min(B, M) + std::abs(step));
     int rc = E->ensure_frame_slots(F_need);
     host_mode = in.frames != nullptr;
     // float flows land in the caller's device array, or in a staging set when they are copied to the host
     // or only feed the bounding kernel
-    prep = c->prepares(); // inputs are source-format frames: convert / resize them on the device first
+    // inputs are source-format frames: convert / resize them on the device first
+    prep = c->prepares() || !clip_fmt.empty();
+    src_ch = !clip_fmt.empty() ? seg_ch : c->prepares() ? c->src_ch : 1;
+    src_stride = c->in_row_bytes() * c->in_h();
+    if (!clip_fmt.empty()) {
+        src_stride = 0;
+        for (size_t s = 0; s < clip_fmt.size(); ++s) {
+            src_stride = std::max(src_stride, (size_t)clip_fmt[s].w * src_ch * clip_fmt[s].h);
+            clip_of.insert(clip_of.end(), (size_t)seg[s], (int)s);
+        }
+    }
     if (rc == DFX_OK)
         rc = ensure_staging(c, (host_mode || prep) ? F_need : 0, (host_mode || out.quantized) ? B : 0);
     if (rc == DFX_OK && prep && host_mode)
-        rc = ensure_src_staging(c, F_need);
+        rc = ensure_src_staging(c, F_need, src_stride);
     if (rc == DFX_OK && out.quantized && host_mode)
         rc = dfx_ensure_img_staging(c, B);
     if (rc == DFX_OK && out.jpeg)
@@ -142,7 +182,7 @@ int FlowRun::prepare(const std::vector<int> &seg) {
     // 224x224 frames is ~900 of them (a third of the batch's compute time).  Such FlowBuffers go through page-locked
     // bounce buffers instead: the host gathers / scatters the frames with memcpy and the copy stream moves one block
     // per batch and direction.
-    const size_t in_fb = c->in_row_bytes() * c->in_h();
+    const size_t in_fb = src_stride;
     const size_t out_pb = out.quantized ? 2 * plane : plane * 8; // bytes per pair leaving the device
     // Decided per direction: a 224x224 frame is 50 KB (gathered), but its float flow is 401 KB — one direct copy per
     // flow (~10 us of driver time) is cheaper than a second pass of host memcpy over 120 MB per clip.
@@ -173,7 +213,7 @@ int FlowRun::prepare(const std::vector<int> &seg) {
 int FlowRun::upload(size_t k) { // host frames of batch k -> staging set par(k) (upload stream)
     const DfxBatchPlan &p = plan[k];
     const int q = par(k);
-    const size_t rb = c->in_row_bytes(), fb = rb * c->in_h();
+    const size_t fb = src_stride;
     unsigned char *dst = prep ? c->d_src[q] : c->d_u8[q];
     // the staging set was last read by the frame preparation of batch q-2 (compute stream)
     if (seq0 + k >= 2)
@@ -182,14 +222,20 @@ int FlowRun::upload(size_t k) { // host frames of batch k -> staging set par(k) 
         if (seq0 + k >= 2) // the copy that last read this bounce buffer (batch q-2) has long finished; make it formal
             HIPCHK(c, hipEventSynchronize(c->ev_h2d[q]));
         unsigned char *hb = c->h_in[q];
-        for (int j = 0; j < p.n_new; ++j)
-            dfx_copy_rows(hb + (size_t)j * fb, rb, in.frames[p.first_new + j], in.frame_pitch, rb, c->in_h());
+        for (int j = 0; j < p.n_new; ++j) {
+            const auto f = fmt(p.first_new + j);
+            const size_t rb = (size_t)f.w * src_ch;
+            dfx_copy_rows(hb + (size_t)j * fb, rb, in.frames[p.first_new + j], f.pitch, rb, f.h);
+        }
         if (p.n_new > 0)
             HIPCHK(c, hipMemcpyAsync(dst, hb, (size_t)p.n_new * fb, hipMemcpyHostToDevice, c->copy_stream));
     } else {
-        for (int j = 0; j < p.n_new; ++j)
-            HIPCHK(c, copy_rows_async(dst + (size_t)j * fb, rb, in.frames[p.first_new + j], in.frame_pitch, rb, c->in_h(),
+        for (int j = 0; j < p.n_new; ++j) {
+            const auto f = fmt(p.first_new + j);
+            const size_t rb = (size_t)f.w * src_ch;
+            HIPCHK(c, copy_rows_async(dst + (size_t)j * fb, rb, in.frames[p.first_new + j], f.pitch, rb, f.h,
                                       hipMemcpyHostToDevice, c->copy_stream));
+        }
     }
     HIPCHK(c, hipEventRecord(c->ev_h2d[q], c->copy_stream));
     return DFX_OK;
@@ -337,12 +383,24 @@ int FlowRun::compute(size_t k) { // batch k on the compute stream, up to its sta
         const unsigned char *src = host_mode ? (prep ? c->d_src[q] : c->d_u8[q])
                                              : in.d_frames + (size_t)p.first_new * in.d_frame_stride;
         long long pitch = host_mode ? (long long)c->in_row_bytes() : (long long)in.d_pitch;
-        long long stride = !host_mode ? (long long)in.d_frame_stride : prep ? (long long)c->src_frame_bytes : (long long)plane;
-        if (prep) { // cvtColor + cv::resize of load_frames_batch (src/denseflow_gpu.cpp:163, :169), on the device
+        long long stride = !host_mode ? (long long)in.d_frame_stride : prep ? (long long)src_stride : (long long)plane;
+        if (prep && clip_fmt.empty()) { // cvtColor + cv::resize of load_frames_batch (src/denseflow_gpu.cpp:163, :169), on the device
             prepare_launch(c->stream, src, pitch, stride, c->src_w, c->src_h, c->src_ch, p.n_new, c->d_u8[q], c->W,
                            (long long)plane, c->W, c->H);
             HIPCHK(c, hipGetLastError());
             c->stats.kernel_launches += 1;
+            src = c->d_u8[q], pitch = c->W, stride = (long long)plane;
+        } else if (prep) { // the same, one launch per run of frames of one source size (at most one per clip)
+            std::vector<int> fw, fh;
+            for (const auto &f : clip_fmt)
+                fw.push_back(f.w), fh.push_back(f.h);
+            for (const DfxFormatRun &r : dfx_format_runs(fw, fh, clip_of, p.first_new, p.n_new)) { // dfx_plan.h, CPU-tested
+                const auto &f = clip_fmt[(size_t)r.clip];
+                prepare_launch(c->stream, src + (size_t)r.j0 * src_stride, (long long)f.w * src_ch, stride, f.w, f.h, src_ch,
+                               r.n, c->d_u8[q] + (size_t)r.j0 * plane, c->W, (long long)plane, c->W, c->H);
+                HIPCHK(c, hipGetLastError());
+                c->stats.kernel_launches += 1;
+            }
             src = c->d_u8[q], pitch = c->W, stride = (long long)plane;
         }
         rc = E->build_frames(src, stride, pitch, p.n_new, c->h_slots.data());
@@ -446,6 +504,10 @@ int flowbuffer_body(dfx_context *c, const InSpec &in, int n_frames, int step, co
     // dfx_next_segments applies to this call only, whatever becomes of it
     std::vector<int> seg;
     seg.swap(c->next_segments);
+    std::vector<dfx_context::SegFormat> seg_fmt;
+    seg_fmt.swap(c->next_seg_fmt);
+    const int seg_ch = c->next_seg_ch;
+    c->next_seg_ch = 1;
     if (ticket)
         *ticket = 0;
     else
@@ -465,7 +527,11 @@ int flowbuffer_body(dfx_context *c, const InSpec &in, int n_frames, int step, co
     }
     if (total != n_frames)
         return dfx_fail(c, DFX_ERR_INVALID, "dfx_next_segments: the clip lengths do not add up to n_frames");
+    if (!seg_fmt.empty() && !in.frames)
+        return dfx_fail(c, DFX_ERR_UNSUPPORTED, "dfx_next_segments_src applies to host-pointer calls only");
     FlowRun run(c, in, out, step);
+    run.clip_fmt.swap(seg_fmt); // one per clip (dfx_next_segments_src), or none
+    run.seg_ch = seg_ch;
     const int rc = run.prepare(seg);
     return rc == DFX_OK && !run.plan.empty() ? run.run(ticket) : rc;
 }
@@ -484,7 +550,26 @@ int dfx_run_flowbuffer(dfx_context *c, const InSpec &in, int n_frames, int step,
 int dfx_ensure_img_staging(dfx_context *c, int need) {
     if (need <= c->img_slots)
         return DFX_OK;
-    return dfx_regrow(c, c->img_slots, need, [&] { return realloc_pair(c, c->d_img, (size_t)need * 2 * c->W * c->H); });
+    return dfx_regrow(c, c->img_slots, need, [&]() -> int {
+        c->img_bytes = 0;
+        const int rc = realloc_pair(c, c->d_img, (size_t)need * 2 * c->W * c->H);
+        if (rc == DFX_OK)
+            c->img_bytes = (size_t)need * 2 * c->W * c->H;
+        return rc;
+    });
+}
+
+// dfx_set_size: what the staging sets hold at the new W x H.  The source format is back at its default, and the gray
+// JPEG encoder works its header and its slot count out again at its next use (dfx_ensure_jpeg).
+void dfx_pipeline_resized(dfx_context *c) {
+    const size_t plane = (size_t)c->W * c->H;
+    c->u8_slots = dfx_slots_in(c->u8_bytes, plane);
+    c->flow_slots = dfx_slots_in(c->flow_bytes, plane * 2 * sizeof(float));
+    c->img_slots = dfx_slots_in(c->img_bytes, 2 * plane);
+    c->src_frame_bytes = 0;
+    c->src_slots = 0;
+    c->jpeg.slots = 0;
+    c->jpeg.hdr_w = c->jpeg.hdr_h = 0;
 }
 
 int dfx_ensure_png(dfx_context *c, int need) {
@@ -506,35 +591,70 @@ int dfx_ensure_png(dfx_context *c, int need) {
 // not fit is measured, and coded again after dfx_jpeg_grow).
 int dfx_ensure_jpeg(dfx_context *c, int pairs, int quality) {
     auto &j = c->jpeg;
-    if (j.quality == quality && pairs <= j.slots)
+    if (j.quality == quality && j.hdr_w == c->W && j.hdr_h == c->H && pairs <= j.slots)
         return DFX_OK;
+    // Every buffer is kept by what it holds and only grows: another frame size (dfx_set_size) or quality re-uses what is
+    // large enough.  A handle that sees one size and one quality allocates what it always did.
     return dfx_regrow(c, j.slots, pairs, [&]() -> int {
-        dfx_jpeg_free(j);
         const size_t planes = 2 * (size_t)pairs, nblk = (size_t)((c->W + 7) / 8) * ((c->H + 7) / 8);
         JpegTables t;
         unsigned char q[64];
         jpeg_build_tables(quality, t, q);
         j.header = jpeg_file_header(c->W, c->H, q);
-        HIPCHK(c, hipMalloc(&j.d_tab, sizeof(JpegTables)));
+        j.hdr_w = j.hdr_h = 0;
+        j.quality = 0;
+        if (!j.d_tab)
+            HIPCHK(c, hipMalloc(&j.d_tab, sizeof(JpegTables)));
         HIPCHK(c, hipMemcpy(j.d_tab, &t, sizeof t, hipMemcpyHostToDevice));
-        HIPCHK(c, hipMalloc(&j.d_dc, planes * nblk * sizeof(short)));
-        HIPCHK(c, hipMalloc(&j.d_bits, planes * nblk * sizeof(unsigned)));
-        HIPCHK(c, hipMalloc(&j.d_plane_bits, planes * 8));
-        HIPCHK(c, hipMalloc(&j.d_plane_base, planes * 8));
-        HIPCHK(c, hipMalloc(&j.d_hdr, 16));
-        j.capacity = ((planes * (size_t)c->W * c->H / 2 + (64u << 10)) + 255) & ~(size_t)255;
+        if (planes * nblk > j.blocks_cap) {
+            j.blocks_cap = 0;
+            dfx_free_dev(j.d_dc);
+            dfx_free_dev(j.d_bits);
+            HIPCHK(c, hipMalloc(&j.d_dc, planes * nblk * sizeof(short)));
+            HIPCHK(c, hipMalloc(&j.d_bits, planes * nblk * sizeof(unsigned)));
+            j.blocks_cap = planes * nblk;
+        }
+        if (!j.d_hdr)
+            HIPCHK(c, hipMalloc(&j.d_hdr, 16));
+        if (planes > j.planes_cap) {
+            j.planes_cap = 0;
+            dfx_free_dev(j.d_plane_bits);
+            dfx_free_dev(j.d_plane_base);
+            HIPCHK(c, hipMalloc(&j.d_plane_bits, planes * 8));
+            HIPCHK(c, hipMalloc(&j.d_plane_base, planes * 8));
+            for (int p = 0; p < 2; ++p) {
+                dfx_free_host(j.h_info[p]);
+                j.d_info[p] = nullptr;
+                HIPCHK(c, hipHostMalloc(&j.h_info[p], (2 + 2 * planes) * 8, hipHostMallocMapped));
+                HIPCHK(c, hipHostGetDevicePointer((void **)&j.d_info[p], j.h_info[p], 0));
+            }
+            j.planes_cap = planes;
+        }
+        for (int p = 0; p < 2; ++p)
+            std::memset(j.h_info[p], 0, (2 + 2 * j.planes_cap) * 8);
+        const size_t cap = ((planes * (size_t)c->W * c->H / 2 + (64u << 10)) + 255) & ~(size_t)255;
+        if (cap > j.capacity) {
+            j.capacity = 0;
+            for (int p = 0; p < 2; ++p) {
+                dfx_free_dev(j.d_stream[p]);
+                HIPCHK(c, hipMalloc(&j.d_stream[p], cap));
+            }
+            j.capacity = cap;
+        }
         for (int p = 0; p < 2; ++p) {
-            HIPCHK(c, hipMalloc(&j.d_stream[p], j.capacity));
             // The page-locked landing buffer starts at 1 bit per pixel (flow planes code to ~0.3-0.5) and grows to what a batch
             // really needs (dfx_jpeg_ensure_landing): pinning 4 bits per pixel twice was ~0.1 s of a 1080p handle's first call
             // (profiles/round5/e2e/) for bytes that never arrive.
-            j.h_capacity[p] = (j.capacity / 4 + 255) & ~(size_t)255;
-            HIPCHK(c, hipHostMalloc(&j.h_stream[p], j.h_capacity[p], hipHostMallocDefault));
-            HIPCHK(c, hipHostMalloc(&j.h_info[p], (2 + 2 * planes) * 8, hipHostMallocMapped));
-            std::memset(j.h_info[p], 0, (2 + 2 * planes) * 8);
-            HIPCHK(c, hipHostGetDevicePointer((void **)&j.d_info[p], j.h_info[p], 0));
+            const size_t hcap = (cap / 4 + 255) & ~(size_t)255;
+            if (hcap > j.h_capacity[p]) {
+                j.h_capacity[p] = 0;
+                dfx_free_host(j.h_stream[p]);
+                HIPCHK(c, hipHostMalloc(&j.h_stream[p], hcap, hipHostMallocDefault));
+                j.h_capacity[p] = hcap;
+            }
         }
         j.quality = quality;
+        j.hdr_w = c->W, j.hdr_h = c->H;
         return DFX_OK;
     });
 }

@@ -68,3 +68,25 @@ inline std::vector<DfxBatchPlan> dfx_plan_batches(const DfxPairs &p, int batch) 
     }
     return plan;
 }
+
+// Clips with their own source formats (dfx_next_segments_src): the new frames of a batch, [first, first + n) by frame id,
+// cut into runs of consecutive frames of one source size — each run is one launch of the preparation kernel.  clip_of[f]
+// is the clip of frame id f; w / h the source size per clip.  A run never spans two sizes, the runs cover the frames once
+// and in order, and neighbouring clips of one size share a run (at most one launch per clip).
+struct DfxFormatRun {
+    int j0, n; // frames [first + j0, first + j0 + n)
+    int clip;  // a clip of that size (its first one in the run)
+};
+inline std::vector<DfxFormatRun> dfx_format_runs(const std::vector<int> &w, const std::vector<int> &h,
+                                                 const std::vector<int> &clip_of, long long first, int n) {
+    std::vector<DfxFormatRun> runs;
+    for (int j0 = 0; j0 < n;) {
+        const int c0 = clip_of[(size_t)(first + j0)];
+        int j1 = j0 + 1;
+        while (j1 < n && w[clip_of[(size_t)(first + j1)]] == w[c0] && h[clip_of[(size_t)(first + j1)]] == h[c0])
+            ++j1;
+        runs.push_back(DfxFormatRun{j0, j1 - j0, c0});
+        j0 = j1;
+    }
+    return runs;
+}

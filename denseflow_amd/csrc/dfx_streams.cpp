@@ -101,6 +101,8 @@ void dfx_jpeg_free(JpegStreams &j) {
         j.d_info[q] = nullptr;
     }
     j.quality = j.slots = 0;
+    j.hdr_w = j.hdr_h = 0;
+    j.blocks_cap = j.planes_cap = 0;
     j.capacity = 0;
 }
 

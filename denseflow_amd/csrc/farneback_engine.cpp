@@ -15,8 +15,6 @@
 
 namespace {
 
-constexpr int kMinSize = 32; // upstream MIN_SIZE
-
 struct FLevel {
     FarnLevelGeom g;
     double sigma;
@@ -67,52 +65,13 @@ void prepare_poly(int n, double sigma, FarnPolyConsts *out) {
     }
 }
 
-// B.6: cv::getGaussianKernel(ksize, sigma, CV_32F); returns taps centre-first (k[0] = centre)
-bool gaussian_taps(int n, double sigma, std::vector<float> &half_out) {
-    if (n < 1 || !(n & 1))
-        return false;
-    std::vector<double> k(n);
-    bool fixed = false;
-    if (sigma <= 0) {
-        static const double t3[] = {0.25, 0.5, 0.25};
-        static const double t5[] = {0.0625, 0.25, 0.375, 0.25, 0.0625};
-        static const double t7[] = {0.03125, 0.109375, 0.21875, 0.28125, 0.21875, 0.109375, 0.03125};
-        const double *t = n == 3 ? t3 : n == 5 ? t5 : n == 7 ? t7 : nullptr;
-        if (n == 1) {
-            k[0] = 1.0;
-            fixed = true;
-        } else if (t) {
-            std::copy(t, t + n, k.begin());
-            fixed = true;
-        }
-    }
-    if (!fixed) {
-        const double sx = sigma > 0 ? sigma : ((n - 1) * 0.5 - 1) * 0.3 + 0.8;
-        const double scale2x = -0.125 / (sx * sx);
-        const int n2 = (n - 1) / 2;
-        double sum = 0;
-        for (int i = 0, x = 1 - n; i < n2; i++, x += 2) {
-            k[i] = std::exp((double)(x * x) * scale2x);
-            sum += k[i];
-        }
-        sum = sum * 2 + 1.0;
-        const double mul = 1.0 / sum;
-        for (int i = 0; i < n2; ++i)
-            k[n - 1 - i] = k[i] = (double)(float)(k[i] * mul);
-        k[n2] = (double)(float)mul;
-    }
-    const int half = n / 2;
-    half_out.resize(half + 1);
-    for (int j = 0; j <= half; ++j)
-        half_out[j] = (float)k[half + j];
-    return true;
-}
-
 class FarnebackEngine final : public AlgoEngine {
   public:
     explicit FarnebackEngine(dfx_context *ctx) : c(ctx) {}
     ~FarnebackEngine() override { destroy(); }
     int create() override;
+    int set_size(int W, int H) override;
+    size_t device_bytes() const override;
     int batch() const override { return B; }
     int ensure_frame_slots(int need) override;
     int frame_slots() const override { return n_frame_slots; }
@@ -123,7 +82,13 @@ class FarnebackEngine final : public AlgoEngine {
 
   private:
     void destroy();
+    int grow_frame_slots(int need, long long elems, long long plane);
+    int slots_held() const;
     dfx_context *c;
+    // what the buffers hold, in bytes (they only grow: set_size re-plans the engine inside them); slot_ids: entries of
+    // d_frame_slots / h_slots_pinned; pair_cap: pairs d_pairs / h_pairs_pinned hold
+    size_t gker_cap = 0, R_cap = 0, f32_cap = 0, tmpv_cap = 0, pyr_cap = 0, planes_cap = 0;
+    int slot_ids = 0, pair_cap = 0;
     int nlev = 0; // levels 0..nlev-1 (nlev = numLevelsCropped + 1)
     FLevel lv[DFX_LVL_MAX];
     long long frame_elems = 0;
@@ -183,90 +148,122 @@ int FarnebackEngine::create() {
         !(p.farn_pyr_scale > 0.0 && p.farn_pyr_scale < 1.0))
         return dfx_fail(c, DFX_ERR_INVALID, "invalid Farneback parameters");
 
-    const int W = c->W, H = c->H;
-    pitch0 = dfx_round_up(W, 64);
-    // B.2: crop levels whose size would drop below MIN_SIZE
-    double scale = 1;
-    int cropped = 0;
-    for (; cropped < p.farn_num_levels; cropped++) {
-        scale *= p.farn_pyr_scale;
-        if (W * scale < kMinSize || H * scale < kMinSize)
-            break;
-    }
-    nlev = cropped + 1;
-    std::vector<float> all_taps;
-    long long off = 0;
-    for (int k = 0; k < nlev; ++k) {
-        scale = 1;
-        for (int i = 0; i < k; i++)
-            scale *= p.farn_pyr_scale;
-        FLevel &L = lv[k];
-        L.sigma = (1. / scale - 1) * 0.5;
-        int smooth = dfx_cv_round(L.sigma * 5) | 1;
-        smooth = std::max(smooth, 3);
-        L.half = smooth / 2;
-        L.g.w = dfx_cv_round(W * scale);
-        L.g.h = dfx_cv_round(H * scale);
-        L.g.pitch = dfx_round_up(L.g.w, 64);
-        L.g.r_off = off;
-        off += 5LL * L.g.pitch * L.g.h;
-        L.ifx = (float)(1.0 / ((double)L.g.w / (double)W)); // dsize given (E.1)
-        L.ify = (float)(1.0 / ((double)L.g.h / (double)H));
-        std::vector<float> taps;
-        if (!gaussian_taps(smooth, L.sigma, taps))
-            return dfx_fail(c, DFX_ERR_INVALID, "Farneback: bad Gaussian kernel size");
-        L.ker_off = (int)all_taps.size();
-        all_taps.insert(all_taps.end(), taps.begin(), taps.end());
-    }
-    frame_elems = off;
     prepare_poly(p.farn_poly_n, p.farn_poly_sigma, &pc);
-    HIPCHK(c, hipMalloc(&d_gker, sizeof(float) * all_taps.size()));
-    HIPCHK(c, hipMemcpy(d_gker, all_taps.data(), sizeof(float) * all_taps.size(), hipMemcpyHostToDevice));
-
-    plane_stride = (long long)pitch0 * H;
     // The default iteration kernel keeps M on chip: a pair slot is its two flow sets (4 planes, 33 MB at 1080p).  The
     // M-in-HBM kernels (another window size, impl = 1, DFX_VAR_FARN_M_IN_HBM) need the two M sets as well (14 planes).
     m_on_chip = p.impl == 0 && p.farn_win_size / 2 == 6 && !(p.variant & DFX_VAR_FARN_M_IN_HBM);
-    slot_stride = plane_stride * (m_on_chip ? (int)FARN_PL_M0 : (int)FARN_PL_COUNT);
-    B = p.max_batch;
-    if (B <= 0) {
-        const long long px0 = (long long)W * H;
-        B = (int)std::max<long long>(1, std::min<long long>(DFX_MAX_BATCH, (256LL << 20) / std::max<long long>(px0, 1)));
-    }
-    size_t free_b = 0, total_b = 0;
-    HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
-    const size_t per_pair = (size_t)slot_stride * 4 + (size_t)frame_elems * 4 + (size_t)plane_stride * 16 + (size_t)W * H * 9;
-    while (B > 1 && per_pair * (size_t)(B + 2) > free_b / 2)
-        B /= 2;
-    HIPCHK(c, hipMalloc(&d_planes, (size_t)slot_stride * B * sizeof(float)));
-    HIPCHK(c, hipMalloc(&d_pairs, sizeof(PairDesc) * B));
-    HIPCHK(c, hipHostMalloc(&h_pairs_pinned, sizeof(PairDesc) * B, hipHostMallocDefault));
     for (auto &e : ev_it) {
         HIPCHK(c, hipEventCreateWithFlags(&e[0], dfx_event_flags(c, true)));
         HIPCHK(c, hipEventCreateWithFlags(&e[1], dfx_event_flags(c, true)));
     }
-    return ensure_frame_slots(B + 1);
+    return set_size(c->W, c->H);
+}
+
+size_t FarnebackEngine::device_bytes() const {
+    return gker_cap + R_cap + f32_cap + tmpv_cap + pyr_cap + planes_cap + sizeof(int) * (size_t)slot_ids +
+           sizeof(PairDesc) * (size_t)pair_cap;
+}
+
+// Plan (engine_plan.h: host arithmetic) + ensure capacity.  Nothing of the engine changes before the last allocation has
+// succeeded; the buffers a failed attempt has already grown stay grown.
+int FarnebackEngine::set_size(int W, int H) {
+    FarnPlan pl;
+    farn_plan(pl, W, H, c->prm, m_on_chip ? (int)FARN_PL_M0 : (int)FARN_PL_COUNT);
+    if (pl.bad_kernel)
+        return dfx_fail(c, DFX_ERR_INVALID, "Farneback: bad Gaussian kernel size");
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
+    int nB = dfx_plan_fit_batch(pl.batch, pl.per_pair, free_b + device_bytes());
+    const size_t slot_bytes = (size_t)pl.slot_stride * sizeof(float);
+    if (dfx_grow_buf(c, d_planes, planes_cap, slot_bytes * nB) != DFX_OK) {
+        if (planes_cap == 0)
+            B = 0; // not even the array it had came back: no FlowBuffer runs until a dfx_set_size succeeds
+        if (planes_cap < slot_bytes)
+            return DFX_ERR_HIP;
+        nB = (int)std::min<size_t>(planes_cap / slot_bytes, (size_t)nB); // what the allocation it had holds
+    }
+    if (nB > pair_cap) {
+        PairDesc *nd = nullptr, *nh = nullptr;
+        if (hipMalloc(&nd, sizeof(PairDesc) * nB) != hipSuccess ||
+            hipHostMalloc(&nh, sizeof(PairDesc) * nB, hipHostMallocDefault) != hipSuccess) {
+            (void)hipGetLastError();
+            dfx_free_dev(nd);
+            return dfx_fail(c, DFX_ERR_HIP, "farn: allocating the pair descriptors failed");
+        }
+        dfx_free_dev(d_pairs);
+        dfx_free_host(h_pairs_pinned);
+        d_pairs = nd, h_pairs_pinned = nh;
+        pair_cap = nB;
+    }
+    int rc = dfx_grow_buf(c, d_gker, gker_cap, sizeof(float) * pl.taps.size());
+    if (rc == DFX_OK)
+        rc = grow_frame_slots(nB + 1, pl.frame_elems, pl.plane_stride);
+    if (rc != DFX_OK) { // the engine goes on at its old size, on the frame slots the buffers still hold
+        n_frame_slots = std::min(n_frame_slots, slots_held());
+        return rc;
+    }
+    // the context is idle: the taps of the previous size are no longer read
+    HIPCHK(c, hipMemcpy(d_gker, pl.taps.data(), sizeof(float) * pl.taps.size(), hipMemcpyHostToDevice));
+    nlev = pl.nlev;
+    for (int k = 0; k < DFX_LVL_MAX; ++k) {
+        const FarnPlanLevel &P = pl.lv[k];
+        lv[k] = FLevel{FarnLevelGeom{P.w, P.h, P.pitch, P.r_off}, P.sigma, P.half, P.ker_off, P.ifx, P.ify};
+    }
+    frame_elems = pl.frame_elems;
+    pitch0 = pl.pitch0;
+    plane_stride = pl.plane_stride;
+    slot_stride = pl.slot_stride;
+    B = nB;
+    n_frame_slots = slots_held();
+    return DFX_OK;
+}
+
+// frame slots the buffers hold at the current geometry
+int FarnebackEngine::slots_held() const {
+    const size_t pb = (size_t)plane_stride * sizeof(float);
+    int n = std::min(dfx_slots_in(R_cap, (size_t)frame_elems * sizeof(float)), slot_ids);
+    n = std::min(n, std::min(dfx_slots_in(tmpv_cap, 2 * pb), dfx_slots_in(pyr_cap, pb)));
+    if (!skip_zero_weights)
+        n = std::min(n, dfx_slots_in(f32_cap, pb));
+    return n;
+}
+
+// `need` frame slots of `elems` floats of R and `plane` floats per scratch plane.  A failure leaves every buffer at least
+// as large as it was.
+int FarnebackEngine::grow_frame_slots(int need, long long elems, long long plane) {
+    const size_t pb = (size_t)need * plane * sizeof(float);
+    int rc = dfx_grow_buf(c, d_R, R_cap, (size_t)need * elems * sizeof(float));
+    if (rc == DFX_OK && !skip_zero_weights) // only the cross-check chain converts the frames to a float plane first
+        rc = dfx_grow_buf(c, d_f32, f32_cap, pb);
+    if (rc == DFX_OK)
+        rc = dfx_grow_buf(c, d_tmpv, tmpv_cap, 2 * pb);
+    if (rc == DFX_OK)
+        rc = dfx_grow_buf(c, d_pyr, pyr_cap, pb);
+    if (rc != DFX_OK)
+        return rc;
+    if (need > slot_ids) {
+        int *nd = nullptr, *nh = nullptr;
+        if (hipMalloc(&nd, sizeof(int) * need) != hipSuccess ||
+            hipHostMalloc(&nh, sizeof(int) * need, hipHostMallocDefault) != hipSuccess) {
+            (void)hipGetLastError();
+            dfx_free_dev(nd);
+            return dfx_fail(c, DFX_ERR_HIP, "farn: allocating the frame-slot tables failed");
+        }
+        dfx_free_dev(d_frame_slots);
+        dfx_free_host(h_slots_pinned);
+        d_frame_slots = nd, h_slots_pinned = nh;
+        slot_ids = need;
+    }
+    return DFX_OK;
 }
 
 int FarnebackEngine::ensure_frame_slots(int need) {
     if (need <= n_frame_slots)
         return DFX_OK;
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    dfx_free_dev(d_R);
-    dfx_free_dev(d_frame_slots);
-    dfx_free_host(h_slots_pinned);
-    dfx_free_dev(d_f32);
-    dfx_free_dev(d_tmpv);
-    dfx_free_dev(d_pyr);
-    HIPCHK(c, hipMalloc(&d_R, (size_t)need * frame_elems * sizeof(float)));
-    HIPCHK(c, hipMalloc(&d_frame_slots, sizeof(int) * need));
-    HIPCHK(c, hipHostMalloc(&h_slots_pinned, sizeof(int) * need, hipHostMallocDefault));
-    if (!skip_zero_weights) // only the cross-check chain converts the frames to a float plane first
-        HIPCHK(c, hipMalloc(&d_f32, (size_t)need * plane_stride * sizeof(float)));
-    HIPCHK(c, hipMalloc(&d_tmpv, (size_t)need * plane_stride * 2 * sizeof(float)));
-    HIPCHK(c, hipMalloc(&d_pyr, (size_t)need * plane_stride * sizeof(float)));
-    n_frame_slots = need;
-    return DFX_OK;
+    const int rc = grow_frame_slots(need, frame_elems, plane_stride);
+    n_frame_slots = slots_held();
+    return rc;
 }
 
 int FarnebackEngine::build_frames(const unsigned char *d_src, long long src_frame_stride, long long src_pitch, int n,

@@ -19,10 +19,7 @@
 
 namespace {
 
-struct Level {
-    int w, h, pitch;
-    long long off; // element offset inside a frame slot
-};
+using Level = DfxPlanLevel; // engine_plan.h
 
 class Tvl1Engine final : public AlgoEngine {
   public:
@@ -30,6 +27,8 @@ class Tvl1Engine final : public AlgoEngine {
     ~Tvl1Engine() override { destroy(); }
 
     int create() override;
+    int set_size(int W, int H) override;
+    size_t device_bytes() const override;
     int batch() const override { return B; }
     int ensure_frame_slots(int need) override;
     int frame_slots() const override { return n_frame_slots; }
@@ -41,6 +40,11 @@ class Tvl1Engine final : public AlgoEngine {
 
   private:
     void destroy();
+    int grow_frame_slots(int need, long long elems);
+    int frame_slots_held(long long elems) const { // frame slots of `elems` floats per pyramid that the buffers hold
+        const size_t least = std::min(pyr_cap[0], std::min(pyr_cap[1], pyr_cap[2]));
+        return elems > 0 ? std::min(dfx_slots_in(least, (size_t)elems * sizeof(float)), slot_ids) : 0;
+    }
     Tvl1LevelCtx level_ctx(int s, int n_pairs) const;
     int steps_per_group(int s, int nb) const;
 
@@ -53,6 +57,11 @@ class Tvl1Engine final : public AlgoEngine {
     float *dI = nullptr, *dIx = nullptr, *dIy = nullptr;
     int *d_frame_slots = nullptr;
     int *h_slots_pinned = nullptr;
+    // what the buffers hold (they only grow: set_size re-plans the engine inside them).  pyr_cap: bytes of dI / dIx /
+    // dIy; slot_ids: entries of d_frame_slots / h_slots_pinned; planes_cap / partials_cap: bytes; pair_cap: pairs the
+    // per-pair arrays (state, descriptors, tables) hold.
+    size_t pyr_cap[3] = {0, 0, 0}, planes_cap = 0, partials_cap = 0;
+    int slot_ids = 0, pair_cap = 0;
 
     int B = 0;
     float *d_planes = nullptr;
@@ -134,25 +143,6 @@ int Tvl1Engine::create() {
     // warp + head of the loop in one launch (round 6): the tuned forms only — every cross-check variant keeps its own kernels
     warp_head = split_warp && geom == 1 && !(p.variant & (DFX_VAR_TVL1_NO_HEAD | DFX_VAR_TVL1_WARP_GATHER));
 
-    // pyramid (A.2 step 3): cvRound(size*scaleStep) per level; a level below 16 px is discarded
-    {
-        long long off = 0;
-        int w = c->W, h = c->H;
-        nlevels = 0;
-        for (int s = 0; s < p.tvl1_nscales && s < DFX_LVL_MAX; ++s) {
-            if (s > 0) {
-                w = dfx_cv_round(lv[s - 1].w * p.tvl1_scale_step);
-                h = dfx_cv_round(lv[s - 1].h * p.tvl1_scale_step);
-                if (w < 16 || h < 16)
-                    break;
-            }
-            lv[s] = Level{w, h, dfx_round_up(w, 64), off};
-            off += (long long)lv[s].pitch * h;
-            nlevels = s + 1;
-        }
-        frame_elems = off;
-    }
-
     loop.warps = p.tvl1_warps;
     loop.iterations = p.tvl1_iterations;
     if (p.impl == 1)
@@ -164,42 +154,8 @@ int Tvl1Engine::create() {
     kc.theta = (float)p.tvl1_theta;
     kc.hyp = p.tvl1_math == 1 ? 0 : p.tvl1_math; // tvl1_math.h: TVL1_HYP_* (the fast mode never reaches a scalar form)
 
-    // batch: enough pairs that the coarse levels fill 256 CUs, bounded by memory
-    const long long plane = (long long)lv[0].pitch * c->H;
-    plane_stride = plane;
-    slot_stride = plane_stride * PL_COUNT;
-    // the tile kernels address a pair slot with 32-bit byte offsets behind a buffer descriptor (tvl1_device_common.h)
-    if ((unsigned long long)slot_stride * sizeof(float) >= (1ull << 32))
-        return dfx_fail(c, DFX_ERR_INVALID, "tvl1: frame too large (a pair's 16 work planes must stay below 4 GiB: round_up(width, 64) x height x 64 B < 2^32)");
-    B = p.max_batch;
-    if (B <= 0) {
-        const long long px0 = (long long)c->W * c->H;
-        B = (int)std::max<long long>(1, std::min<long long>(DFX_MAX_BATCH, (256LL << 20) / std::max<long long>(px0, 1)));
-    }
-    size_t free_b = 0, total_b = 0;
-    HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
-    const size_t per_pair = (size_t)slot_stride * 4 + (size_t)c->W * c->H * 9 + (size_t)frame_elems * 12;
-    while (B > 1 && per_pair * (size_t)(B + 2) > free_b / 2)
-        B /= 2;
-
-    HIPCHK(c, hipMalloc(&d_planes, (size_t)slot_stride * B * sizeof(float)));
-    HIPCHK(c, hipMalloc(&d_state, sizeof(Tvl1State) * B));
-    HIPCHK(c, hipMemset(d_state, 0, sizeof(Tvl1State) * B));
-    HIPCHK(c, hipMalloc(&d_pairs, sizeof(PairDesc) * B));
-    HIPCHK(c, hipHostMalloc(&h_pairs_pinned, sizeof(PairDesc) * B, hipHostMallocDefault));
-    partials_stride = ((lv[0].w + 63) / 64) * ((c->H + 3) / 4) + 64; // >= workgroups of any step variant
-    HIPCHK(c, hipMalloc(&d_partials, sizeof(double) * (size_t)partials_stride * B));
-    HIPCHK(c, hipMalloc(&d_iters_out, sizeof(int) * B * DFX_LVL_MAX * TVL1_MAX_WARPS));
-    HIPCHK(c, hipMalloc(&d_checks_out, sizeof(int) * B * DFX_LVL_MAX * 2));
-    HIPCHK(c, hipMalloc(&d_work_out, sizeof(long long) * B * DFX_LVL_MAX * 2));
-    HIPCHK(c, hipMemset(d_work_out, 0, sizeof(long long) * B * DFX_LVL_MAX * 2));
-    HIPCHK(c, hipHostMalloc(&h_work, sizeof(long long) * B * DFX_LVL_MAX * 2, hipHostMallocDefault));
-    HIPCHK(c, hipHostMalloc(&h_iters, sizeof(int) * B * DFX_LVL_MAX * TVL1_MAX_WARPS, hipHostMallocDefault));
-    HIPCHK(c, hipHostMalloc(&h_checks, sizeof(int) * B * DFX_LVL_MAX * 2, hipHostMallocDefault));
     HIPCHK(c, hipMalloc(&d_level_done, sizeof(unsigned int)));
-    HIPCHK(c, hipMemset(d_level_done, 0, sizeof(unsigned int)));
     HIPCHK(c, hipHostMalloc(&h_done_flag, 64, hipHostMallocMapped));
-    *h_done_flag = 0;
     HIPCHK(c, hipHostGetDevicePointer((void **)&d_done_flag, h_done_flag, 0));
     HIPCHK(c, hipEventCreateWithFlags(&ev_group[0], dfx_event_flags(c, false)));
     HIPCHK(c, hipEventCreateWithFlags(&ev_group[1], dfx_event_flags(c, false)));
@@ -207,26 +163,128 @@ int Tvl1Engine::create() {
         HIPCHK(c, hipEventCreateWithFlags(&e[0], dfx_event_flags(c, true)));
         HIPCHK(c, hipEventCreateWithFlags(&e[1], dfx_event_flags(c, true)));
     }
-    return ensure_frame_slots(B + 1);
+    return set_size(c->W, c->H);
+}
+
+size_t Tvl1Engine::device_bytes() const {
+    const size_t per_pair = sizeof(Tvl1State) + sizeof(PairDesc) + sizeof(int) * DFX_LVL_MAX * (TVL1_MAX_WARPS + 2) +
+                            sizeof(long long) * DFX_LVL_MAX * 2;
+    return planes_cap + partials_cap + pyr_cap[0] + pyr_cap[1] + pyr_cap[2] + sizeof(int) * (size_t)slot_ids + per_pair * (size_t)pair_cap +
+           (d_level_done ? sizeof(unsigned int) : 0);
+}
+
+// Plan (engine_plan.h: host arithmetic) + ensure capacity.  Nothing of the engine changes before the last allocation has
+// succeeded; the buffers a failed attempt has already grown stay grown.
+int Tvl1Engine::set_size(int W, int H) {
+    Tvl1Plan pl;
+    tvl1_plan(pl, W, H, c->prm);
+    if (pl.slot_too_large)
+        return dfx_fail(c, DFX_ERR_INVALID, "tvl1: frame too large (a pair's 16 work planes must stay below 4 GiB: round_up(width, 64) x height x 64 B < 2^32)");
+    // batch: enough pairs that the coarse levels fill 256 CUs, bounded by memory — by what is free now plus what this
+    // engine holds and would give back for a larger allocation
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
+    int nB = dfx_plan_fit_batch(pl.batch, pl.per_pair, free_b + device_bytes());
+    const size_t slot_bytes = (size_t)pl.slot_stride * sizeof(float);
+    if (dfx_grow_buf(c, d_planes, planes_cap, slot_bytes * nB) != DFX_OK) {
+        if (planes_cap == 0)
+            B = 0; // not even the array it had came back: no FlowBuffer runs until a dfx_set_size succeeds
+        if (planes_cap < slot_bytes)
+            return DFX_ERR_HIP;
+        nB = (int)std::min<size_t>(planes_cap / slot_bytes, (size_t)nB); // what the allocation it had holds
+    }
+    if (nB > pair_cap) {
+        // small arrays: the new set first, the old one is freed only when every allocation has succeeded
+        Tvl1State *n_state = nullptr;
+        PairDesc *n_pairs = nullptr, *n_hpairs = nullptr;
+        int *n_iters = nullptr, *n_checks = nullptr, *n_hiters = nullptr, *n_hchecks = nullptr;
+        long long *n_work = nullptr, *n_hwork = nullptr;
+        const size_t it = sizeof(int) * nB * DFX_LVL_MAX * TVL1_MAX_WARPS, ck = sizeof(int) * nB * DFX_LVL_MAX * 2,
+                     wk = sizeof(long long) * nB * DFX_LVL_MAX * 2;
+        const bool ok = hipMalloc(&n_state, sizeof(Tvl1State) * nB) == hipSuccess &&
+                        hipMalloc(&n_pairs, sizeof(PairDesc) * nB) == hipSuccess &&
+                        hipHostMalloc(&n_hpairs, sizeof(PairDesc) * nB, hipHostMallocDefault) == hipSuccess &&
+                        hipMalloc(&n_iters, it) == hipSuccess && hipMalloc(&n_checks, ck) == hipSuccess &&
+                        hipMalloc(&n_work, wk) == hipSuccess && hipHostMalloc(&n_hwork, wk, hipHostMallocDefault) == hipSuccess &&
+                        hipHostMalloc(&n_hiters, it, hipHostMallocDefault) == hipSuccess &&
+                        hipHostMalloc(&n_hchecks, ck, hipHostMallocDefault) == hipSuccess;
+        if (!ok) {
+            (void)hipGetLastError();
+            dfx_free_dev(n_state), dfx_free_dev(n_pairs), dfx_free_host(n_hpairs), dfx_free_dev(n_iters);
+            dfx_free_dev(n_checks), dfx_free_dev(n_work), dfx_free_host(n_hwork), dfx_free_host(n_hiters);
+            dfx_free_host(n_hchecks);
+            return dfx_fail(c, DFX_ERR_HIP, "tvl1: allocating the per-pair tables failed");
+        }
+        dfx_free_dev(d_state), dfx_free_dev(d_pairs), dfx_free_host(h_pairs_pinned), dfx_free_dev(d_iters_out);
+        dfx_free_dev(d_checks_out), dfx_free_dev(d_work_out), dfx_free_host(h_work), dfx_free_host(h_iters);
+        dfx_free_host(h_checks);
+        d_state = n_state, d_pairs = n_pairs, h_pairs_pinned = n_hpairs, d_iters_out = n_iters, d_checks_out = n_checks;
+        d_work_out = n_work, h_work = n_hwork, h_iters = n_hiters, h_checks = n_hchecks;
+        pair_cap = nB;
+        // as create leaves them: should a later allocation of this call fail, the engine goes on at its old size on these
+        HIPCHK(c, hipMemset(d_state, 0, sizeof(Tvl1State) * pair_cap));
+        HIPCHK(c, hipMemset(d_work_out, 0, sizeof(long long) * pair_cap * DFX_LVL_MAX * 2));
+    }
+    int rc = dfx_grow_buf(c, d_partials, partials_cap, sizeof(double) * (size_t)pl.partials_stride * nB);
+    if (rc == DFX_OK)
+        rc = grow_frame_slots(nB + 1, pl.frame_elems);
+    if (rc != DFX_OK)
+        return rc;
+    // commit: the geometry every launch derives its Tvl1LevelCtx from, and the control state as it is after create
+    nlevels = pl.nlevels;
+    for (int s = 0; s < DFX_LVL_MAX; ++s)
+        lv[s] = pl.lv[s];
+    frame_elems = pl.frame_elems;
+    plane_stride = pl.plane_stride;
+    slot_stride = pl.slot_stride;
+    partials_stride = pl.partials_stride;
+    B = nB;
+    n_frame_slots = frame_slots_held(frame_elems);
+    HIPCHK(c, hipMemset(d_state, 0, sizeof(Tvl1State) * pair_cap));
+    HIPCHK(c, hipMemset(d_work_out, 0, sizeof(long long) * pair_cap * DFX_LVL_MAX * 2));
+    HIPCHK(c, hipMemset(d_level_done, 0, sizeof(unsigned int)));
+    *h_done_flag = 0;
+    done_token = 0;
+    last_nb = 0;
+    for (auto &n : launched_steps)
+        n = 0;
+    return DFX_OK;
+}
+
+// `need` frame slots of `elems` floats per pyramid
+int Tvl1Engine::grow_frame_slots(int need, long long elems) {
+    const size_t bytes = (size_t)need * elems * sizeof(float);
+    // each pyramid by what it holds: after a failure every one of them is at least as large as it was (or gone, and then
+    // frame_slots_held() counts none)
+    if (dfx_grow_buf(c, dI, pyr_cap[0], bytes) != DFX_OK || dfx_grow_buf(c, dIx, pyr_cap[1], bytes) != DFX_OK ||
+        dfx_grow_buf(c, dIy, pyr_cap[2], bytes) != DFX_OK) {
+        n_frame_slots = std::min(n_frame_slots, frame_slots_held(frame_elems));
+        return DFX_ERR_HIP;
+    }
+    if (need > slot_ids) {
+        int *nd = nullptr, *nh = nullptr;
+        if (hipMalloc(&nd, sizeof(int) * need) != hipSuccess ||
+            hipHostMalloc(&nh, sizeof(int) * need, hipHostMallocDefault) != hipSuccess) {
+            (void)hipGetLastError();
+            dfx_free_dev(nd);
+            return dfx_fail(c, DFX_ERR_HIP, "tvl1: allocating the frame-slot tables failed");
+        }
+        dfx_free_dev(d_frame_slots);
+        dfx_free_host(h_slots_pinned);
+        d_frame_slots = nd, h_slots_pinned = nh;
+        slot_ids = need;
+    }
+    return DFX_OK;
 }
 
 int Tvl1Engine::ensure_frame_slots(int need) {
     if (need <= n_frame_slots)
         return DFX_OK;
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    dfx_free_dev(dI);
-    dfx_free_dev(dIx);
-    dfx_free_dev(dIy);
-    dfx_free_dev(d_frame_slots);
-    dfx_free_host(h_slots_pinned);
-    const size_t bytes = (size_t)need * frame_elems * sizeof(float);
-    HIPCHK(c, hipMalloc(&dI, bytes));
-    HIPCHK(c, hipMalloc(&dIx, bytes));
-    HIPCHK(c, hipMalloc(&dIy, bytes));
-    HIPCHK(c, hipMalloc(&d_frame_slots, sizeof(int) * need));
-    HIPCHK(c, hipHostMalloc(&h_slots_pinned, sizeof(int) * need, hipHostMallocDefault));
-    n_frame_slots = need;
-    return DFX_OK;
+    const int rc = grow_frame_slots(need, frame_elems);
+    if (rc == DFX_OK)
+        n_frame_slots = frame_slots_held(frame_elems);
+    return rc;
 }
 
 // float pyramids + centred gradients (A.2 steps 1-3, A.3) of `n` new frames

@@ -191,6 +191,8 @@ def load_library():
     L.dfx_jpeg_capacity.restype = sz
     L.dfx_next_segments.argtypes = [vp, C.POINTER(C.c_int), i]
     L.dfx_next_segments.restype = i
+    L.dfx_next_segments_src.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(sz), i, i]
+    L.dfx_next_segments_src.restype = i
     L.dfx_wait.argtypes = [vp, C.c_uint64]
     L.dfx_wait.restype = i
     L.dfx_calc_batch_u8_device.argtypes = [vp, vp, sz, sz, i, i, C.c_double, C.c_double, vp, vp, sz, sz]
@@ -227,6 +229,10 @@ def load_library():
     L.dfx_submit_extract_frames.restype = i
     L.dfx_frames_device_bytes.argtypes = [vp]
     L.dfx_frames_device_bytes.restype = sz
+    L.dfx_set_size.argtypes = [vp, i, i]
+    L.dfx_set_size.restype = i
+    L.dfx_device_bytes.argtypes = [vp]
+    L.dfx_device_bytes.restype = sz
     L.dfx_get_stats.argtypes = [vp, C.POINTER(DfxStats)]
     L.dfx_get_stats.restype = i
     L.dfx_reset_stats.argtypes = [vp]
@@ -275,7 +281,8 @@ def default_params() -> DfxParams:
 
 
 class FlowEngine:
-    """One handle = one device + one private stream set (not thread-safe), sized for width x height."""
+    """One handle = one device + one private stream set (not thread-safe), sized for width x height (set_size re-plans it
+    for another size inside its allocations)."""
 
     def __init__(self, width: int, height: int, algorithm: str = "tvl1", device: int = 0,
                  params: DfxParams | None = None, **knobs):
@@ -319,6 +326,20 @@ class FlowEngine:
     def __exit__(self, *a):
         self.close()
 
+    # -- one handle, many frame sizes (dfx_set_size) ------------------------------------------------------------
+    def set_size(self, width: int, height: int):
+        """Re-plan the engine for width x height frames inside its allocations: waits for everything outstanding, cancels
+        a pending next_segments, restores the default source format.  Afterwards the engine computes what a fresh one of
+        that size computes.  On failure (DfxError) it stays usable at its previous size."""
+        self._pending_seg = self._armed_seg = self._pending_src = self._armed_src = None
+        self._check(self._L.dfx_set_size(self._h, int(width), int(height)))
+        self.width, self.height = int(width), int(height)
+        self._src = None
+
+    def device_bytes(self) -> int:
+        """Device memory this handle holds right now, all kinds together."""
+        return int(self._L.dfx_device_bytes(self._h))
+
     # -- frame preparation on the device (reference: cvtColor + cv::resize in load_frames_batch) ----------
     def set_source_format(self, src_width: int = 0, src_height: int = 0, channels: int = 1):
         """Frames passed to calc / calc_optflows* are src_width x src_height with 1 (gray) or 3 (BGR) channels
@@ -353,25 +374,79 @@ class FlowEngine:
                                                       gray_frame_stride))
 
     # -- several short clips in one FlowBuffer (dfx_next_segments) ------------------------------------------
-    def next_segments(self, seg_frames):
+    def next_segments(self, seg_frames, src_sizes=None, channels: int = 1):
         """The NEXT calc_optflows* / submit_optflows call carries len(seg_frames) clips back to back, clip s being
-        seg_frames[s] consecutive frames; pairs are formed inside each clip only (outputs in clip order)."""
+        seg_frames[s] consecutive frames; pairs are formed inside each clip only (outputs in clip order).
+
+        src_sizes: one (width, height) per clip (dfx_next_segments_src) — that one call then accepts frames of differing
+        shapes, (h, w) for channels = 1 or (h, w, 3) for channels = 3, each clip with its own row pitch (the frames of a
+        clip may be views with padded rows; they must share their strides); every clip is converted / resized to the
+        engine's size on the device."""
         self._pending_seg = [int(x) for x in seg_frames]
+        self._pending_src = None
+        if src_sizes is not None:
+            src = [(int(w), int(h)) for w, h in src_sizes]
+            if len(src) != len(self._pending_seg) or channels not in (1, 3):
+                self._pending_seg = None
+                raise ValueError("one (width, height) per clip, and channels 1 or 3")
+            self._pending_src = (src, int(channels))
 
     def _num_pairs(self, n: int, step: int) -> int:
         seg, self._pending_seg = getattr(self, "_pending_seg", None), None
-        self._armed_seg = None
+        src, self._pending_src = getattr(self, "_pending_src", None), None
+        self._armed_seg = self._armed_src = self._armed_pitch = None
         if seg is None:
             return max(n - abs(step), 0)
         if sum(seg) != n or min(seg, default=0) < 0:
             raise ValueError("segment lengths must be >= 0 and add up to the number of frames")
-        self._armed_seg = seg
+        self._armed_seg, self._armed_src = seg, src
         return sum(max(x - abs(step), 0) for x in seg)
+
+    def _frames_in(self, frames):
+        """The frames of a call as uint8 arrays: C-contiguous, or — under next_segments(src_sizes=...) — with dense pixels
+        and any row pitch."""
+        if getattr(self, "_pending_src", None) is None:
+            return [np.ascontiguousarray(f, dtype=np.uint8) for f in frames]
+        out = []
+        for f in frames:
+            f = np.asarray(f)
+            dense = f.dtype == np.uint8 and f.ndim in (2, 3) and f.strides[-1] == 1 and (f.ndim == 2 or f.strides[1] == f.shape[2])
+            out.append(f if dense else np.ascontiguousarray(f, dtype=np.uint8))
+        return out
+
+    def _check_shapes(self, frames):
+        src = getattr(self, "_armed_src", None)
+        if src is None:
+            for f in frames:
+                if f.shape != self._frame_shape():
+                    raise ValueError("frame shape does not match the engine")
+            return
+        sizes, ch = src
+        pitches, k = [], 0
+        for (w, h), n in zip(sizes, self._armed_seg):
+            want = (h, w) if ch == 1 else (h, w, 3)
+            clip = frames[k:k + n]
+            k += n
+            if any(f.shape != want or f.strides != clip[0].strides for f in clip):
+                self._armed_seg = self._armed_src = None
+                raise ValueError("the frames of a clip must have its declared shape and one row pitch")
+            pitches.append(clip[0].strides[0] if clip else w * ch)
+        self._armed_pitch = pitches
 
     def _arm(self):  # right in front of the library call the declaration is meant for
         seg, self._armed_seg = getattr(self, "_armed_seg", None), None
-        if seg is not None:
-            self._check(self._L.dfx_next_segments(self._h, (C.c_int * max(len(seg), 1))(*seg), len(seg)))
+        src, self._armed_src = getattr(self, "_armed_src", None), None
+        if seg is None:
+            return
+        cnt = max(len(seg), 1)
+        if src is None:
+            self._check(self._L.dfx_next_segments(self._h, (C.c_int * cnt)(*seg), len(seg)))
+            return
+        sizes, ch = src
+        pitches = getattr(self, "_armed_pitch", None) or [w * ch for w, _ in sizes]
+        wh = [v for s in sizes for v in s]
+        self._check(self._L.dfx_next_segments_src(self._h, (C.c_int * cnt)(*seg), (C.c_int * (2 * cnt))(*wh),
+                                                  (C.c_size_t * cnt)(*pitches), len(seg), ch))
 
     # -- the hot path ------------------------------------------------------------------------
     def calc(self, frame_a: np.ndarray, frame_b: np.ndarray) -> np.ndarray:
@@ -387,15 +462,13 @@ class FlowEngine:
 
     def calc_optflows(self, frames_gray, step: int):
         """The loop of DenseFlow::calc_optflows_imp (src/denseflow_gpu.cpp:307-342) for one FlowBuffer."""
-        frames = [np.ascontiguousarray(f, dtype=np.uint8) for f in frames_gray]
+        frames = self._frames_in(frames_gray)
         n = len(frames)
         m = self._num_pairs(n, step)
         flows = [np.empty((self.height, self.width, 2), dtype=np.float32) for _ in range(m)]
         if m == 0:
             return flows
-        for f in frames:
-            if f.shape != self._frame_shape():
-                raise ValueError("frame shape does not match the engine")
+        self._check_shapes(frames)
         fp = (C.c_void_p * n)(*[f.ctypes.data for f in frames])
         op = (C.c_void_p * m)(*[f.ctypes.data for f in flows])
         self._arm()
@@ -407,12 +480,10 @@ class FlowEngine:
         """dfx_submit_batch (bound None: float flows) or dfx_submit_batch_u8 (planes bounded to [-bound, bound]).
         Returns (ticket, outputs); the outputs are valid after wait(ticket).  The output arrays are created here and
         must be kept alive by the caller until then."""
-        frames = [np.ascontiguousarray(f, dtype=np.uint8) for f in frames_gray]
+        frames = self._frames_in(frames_gray)
         n = len(frames)
         m = self._num_pairs(n, step)
-        for f in frames:
-            if f.shape != self._frame_shape():
-                raise ValueError("frame shape does not match the engine")
+        self._check_shapes(frames)
         t = C.c_uint64(0)
         fp = (C.c_void_p * max(n, 1))(*[f.ctypes.data for f in frames])
         pitch = frames[0].strides[0] if n else self.width
@@ -448,16 +519,14 @@ class FlowEngine:
 
         Returns (img_x, img_y): two lists of M (H, W) uint8 planes.  The reference bounds to
         [-bound, bound]; pass `lower` for an asymmetric interval [lower, bound]."""
-        frames = [np.ascontiguousarray(f, dtype=np.uint8) for f in frames_gray]
+        frames = self._frames_in(frames_gray)
         n = len(frames)
         m = self._num_pairs(n, step)
         img_x = [np.empty((self.height, self.width), dtype=np.uint8) for _ in range(m)]
         img_y = [np.empty((self.height, self.width), dtype=np.uint8) for _ in range(m)]
         if m == 0:
             return img_x, img_y
-        for f in frames:
-            if f.shape != self._frame_shape():
-                raise ValueError("frame shape does not match the engine")
+        self._check_shapes(frames)
         lo = -float(bound) if lower is None else float(lower)
         fp = (C.c_void_p * n)(*[f.ctypes.data for f in frames])
         xp = (C.c_void_p * m)(*[f.ctypes.data for f in img_x])
@@ -475,7 +544,7 @@ class FlowEngine:
         Returns (img_x, img_y, bounds): two lists of M (H, W) uint8 planes and an (M, 2) float64 array of
         (bound_x, bound_y).  png_bgr() assembles the reference's 3-channel image from them.  submit=True goes through
         dfx_submit_batch_png + dfx_wait (the host shell's form)."""
-        frames = [np.ascontiguousarray(f, dtype=np.uint8) for f in frames_gray]
+        frames = self._frames_in(frames_gray)
         n = len(frames)
         m = self._num_pairs(n, step)
         img_x = [np.empty((self.height, self.width), dtype=np.uint8) for _ in range(m)]
@@ -483,9 +552,7 @@ class FlowEngine:
         bounds = np.zeros((m, 2), np.float64)
         if m == 0:
             return img_x, img_y, bounds
-        for f in frames:
-            if f.shape != self._frame_shape():
-                raise ValueError("frame shape does not match the engine")
+        self._check_shapes(frames)
         fp = (C.c_void_p * n)(*[f.ctypes.data for f in frames])
         xp = (C.c_void_p * m)(*[f.ctypes.data for f in img_x])
         yp = (C.c_void_p * m)(*[f.ctypes.data for f in img_y])
@@ -528,14 +595,12 @@ class FlowEngine:
     def calc_optflows_jpeg(self, frames_gray, step: int, bound: float, quality: int = 95):
         """encodeFlowMap of every flow of the FlowBuffer on the device (src/common.cpp:48-64): returns two lists of
         `bytes`, the flow_x and flow_y JPEG files (bounded to [-bound, bound], quality like cv::imencode)."""
-        frames = [np.ascontiguousarray(f, dtype=np.uint8) for f in frames_gray]
+        frames = self._frames_in(frames_gray)
         n = len(frames)
         m = self._num_pairs(n, step)
         if m == 0:
             return [], []
-        for f in frames:
-            if f.shape != self._frame_shape():
-                raise ValueError("frame shape does not match the engine")
+        self._check_shapes(frames)
         cap = int(self._L.dfx_jpeg_capacity(self._h))
         bx = [np.empty(cap, np.uint8) for _ in range(m)]
         by = [np.empty(cap, np.uint8) for _ in range(m)]

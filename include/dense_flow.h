@@ -139,6 +139,7 @@ class DenseFlow {
     // the device engine (replaces Ptr<cuda::*OpticalFlow> + cv::cuda::Stream)
     dfx_handle dfx_;
     Size dfx_size_;
+    int dfx_algo_ = -1; // dfx_algo of dfx_ (a handle is re-planned for another size, created anew for another algorithm)
     Stream stream; // reference member (include/dense_flow.h:33)
     // the FlowBuffer whose last download is still in flight (dfx_submit_batch*), and whether the buffer being
     // processed is the last of the run

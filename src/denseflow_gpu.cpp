@@ -483,6 +483,14 @@ void DenseFlow::enqueue_pending(std::unique_ptr<PendingFlows> p) {
     pending_cv_.notify_all();
 }
 
+// dfx_set_size is resolved weakly, as the colour entry points below are: against an ABI without it (the CPU pipeline
+// tests' fake) the shell keeps destroying and creating its handle when the size changes.
+#pragma weak dfx_set_size
+#pragma weak dfx_next_segments_src
+static bool resize_handle() { return dfx_set_size && !std::getenv("DF_NO_RESIZE_HANDLE"); }
+// clips that differ in source size only may share a library call (every clip is resized on the device to the one target)
+static bool join_mixed_sources() { return dfx_next_segments_src && !std::getenv("DF_NO_RESIZE_HANDLE"); }
+
 // The engine for flows of size sz (reference: the create() calls of :299-303, per FlowBuffer there).
 void DenseFlow::prepare_engine(const string &algorithm, const Size &sz) {
     dfx_algo algo;
@@ -491,9 +499,19 @@ void DenseFlow::prepare_engine(const string &algorithm, const Size &sz) {
         char msg[256];
         throw std::runtime_error(dfx_algo_error_message(rc, algorithm.c_str(), msg, sizeof msg));
     }
-    if (dfx_ && sz == dfx_size_)
+    if (dfx_ && dfx_algo_ == (int)algo && sz == dfx_size_)
         return;
     flush_pending();
+    // A list of clips of mixed sizes (--ns=256: the output follows every clip's aspect ratio) changes the size for almost
+    // every clip: the handle of this algorithm is re-planned inside its allocations (dfx_set_size) instead of being
+    // destroyed and created again.  DF_NO_RESIZE_HANDLE=1, or a libdfx without the entry point: destroy and create.
+    if (dfx_ && dfx_algo_ == (int)algo && resize_handle()) {
+        if (dfx_set_size(dfx_, sz.width, sz.height) != DFX_OK)
+            throw std::runtime_error(dfx_last_error(dfx_));
+        dfx_size_ = sz;
+        TRACE("calc: engine re-planned for %dx%d", sz.width, sz.height);
+        return;
+    }
     if (dfx_)
         dfx_destroy(dfx_);
     dfx_ = nullptr;
@@ -509,6 +527,7 @@ void DenseFlow::prepare_engine(const string &algorithm, const Size &sz) {
     if (dfx_create(&dfx_, device, algo, sz.width, sz.height, &prm) != DFX_OK)
         throw std::runtime_error(dfx_last_error(nullptr));
     dfx_size_ = sz;
+    dfx_algo_ = (int)algo;
     TRACE("calc: engine for %dx%d ready", sz.width, sz.height);
 }
 
@@ -552,19 +571,30 @@ void DenseFlow::submit_group(vector<FlowBuffer> &group, const string &algorithm,
             if (!fb.item_data.empty())
                 target = fb.target;
         const Size sz = target.width > 0 ? target : in_sz; // size of the flows
-        // One pitch and one source format describe the whole call: every frame must have the first one's geometry (the
-        // reference resizes frame by frame, :166-170, so mixed-size image directories work there; here they would be
-        // read out of bounds).
+        // One pitch and one source format describe a clip: every frame must have the geometry of its FlowBuffer's first
+        // one (the reference resizes frame by frame, :166-170, so mixed-size image directories work there; here they would
+        // be read out of bounds).  FlowBuffers that differ from each other (joined clips that share the target size only)
+        // are declared with their own formats.
         vector<const uint8_t *> in;
         in.reserve(N);
-        for (const FlowBuffer &fb : group)
+        bool mixed = false;
+        vector<int> seg_wh;
+        vector<size_t> seg_pitch;
+        for (const FlowBuffer &fb : group) {
+            const Mat *head = fb.item_data.empty() ? first : &fb.item_data[0];
+            mixed = mixed || !(head->size() == in_sz) || head->step != first->step;
+            seg_wh.push_back(head->cols), seg_wh.push_back(head->rows);
+            seg_pitch.push_back(head->step);
             for (const Mat &f : fb.item_data) {
-                if (!(f.size() == in_sz) || f.step != first->step || f.type() != CV_8UC1)
+                if (!(f.size() == head->size()) || f.step != head->step || f.type() != CV_8UC1)
                     throw std::runtime_error("frames of one FlowBuffer differ in size (" + std::to_string(f.cols) + "x" +
                                              std::to_string(f.rows) + " after " + std::to_string(in_sz.width) + "x" +
                                              std::to_string(in_sz.height) + ")");
                 in.push_back(f.ptr<uint8_t>());
             }
+        }
+        if (mixed && (!join_mixed_sources() || !(target.width > 0)))
+            throw std::runtime_error("FlowBuffers of different frame sizes in one group");
         TRACE("calc: %d frames of %d FlowBuffer(s) -> %d flows, %dx%d, algorithm %s", N, (int)group.size(), M, sz.width,
               sz.height, algorithm.c_str());
         prepare_engine(algorithm, sz); // sized per video; reused across its FlowBuffers (usually created already: engine_hint)
@@ -572,8 +602,14 @@ void DenseFlow::submit_group(vector<FlowBuffer> &group, const string &algorithm,
         if (dfx_set_source_format(dfx_, sz == in_sz ? 0 : in_sz.width, sz == in_sz ? 0 : in_sz.height, 1) != DFX_OK)
             throw std::runtime_error(dfx_last_error(dfx_));
         auto declare = [&] { // more than one clip in this call: pairs never cross a clip boundary
-            if (group.size() > 1 && dfx_next_segments(dfx_, seg.data(), (int)seg.size()) != DFX_OK)
+            if (group.size() <= 1)
+                return;
+            const int drc = mixed ? dfx_next_segments_src(dfx_, seg.data(), seg_wh.data(), seg_pitch.data(), (int)seg.size(), 1)
+                                  : dfx_next_segments(dfx_, seg.data(), (int)seg.size());
+            if (drc != DFX_OK)
                 throw std::runtime_error(dfx_last_error(dfx_));
+            if (mixed)
+                TRACE("calc: %d clips of different source sizes in one call", (int)group.size());
         };
         uint64_t ticket = 0;
         bool encoded_on_device = false;
@@ -706,9 +742,16 @@ void DenseFlow::calc_optflows(bool verbose) {
         auto frame_px = [](const FlowBuffer &b) {
             return b.item_data.empty() ? (size_t)0 : b.item_data.size() * (size_t)b.item_data[0].rows * b.item_data[0].cols;
         };
-        auto same_geometry = [](const FlowBuffer &a, const FlowBuffer &b) {
+        // With the resize on the device and per-clip source formats in the library (dfx_next_segments_src), clips join on
+        // their target size, channel count and type; their source sizes may differ.  Otherwise on the source size too.
+        const bool mixed_ok = join_mixed_sources();
+        auto same_geometry = [mixed_ok](const FlowBuffer &a, const FlowBuffer &b) {
             const Mat &x = a.item_data[0], &y = b.item_data[0];
-            return x.size() == y.size() && x.step == y.step && x.type() == y.type() && a.target == b.target;
+            if (x.type() != y.type() || !(a.target == b.target))
+                return false;
+            if (mixed_ok && a.target.width > 0)
+                return true;
+            return x.size() == y.size() && x.step == y.step;
         };
         std::unique_ptr<std::pair<FlowBuffer, bool>> carry; // popped while joining, but it does not fit the group
         while (true) {
@@ -906,13 +949,20 @@ int DenseFlow::extract_frames_colour(vector<path> &frames_path, bool do_resize, 
     const bool have_abi = dfx_submit_extract_frames && dfx_prepare_frames_bgr && dfx_jpeg_capacity_bgr;
     const bool host_resize = !have_abi || !device_resize, host_jpeg = !have_abi || std::getenv("DF_HOST_JPEG");
     const bool need_device = !host_jpeg || (do_resize && !host_resize);
-    if (need_device && (!dfx_ || dfx_size_.width != size.width || dfx_size_.height != size.height)) {
-        if (dfx_)
-            dfx_destroy(dfx_);
-        dfx_ = nullptr;
-        const int rc = dfx_create(&dfx_, device, DFX_ALGO_FRAMES, size.width, size.height, nullptr);
-        if (rc != DFX_OK)
-            throw std::runtime_error(string("dfx_create failed: ") + dfx_last_error(nullptr));
+    if (need_device && (!dfx_ || dfx_algo_ != (int)DFX_ALGO_FRAMES || dfx_size_.width != size.width ||
+                        dfx_size_.height != size.height)) {
+        if (dfx_ && dfx_algo_ == (int)DFX_ALGO_FRAMES && resize_handle()) { // the next video's size: re-plan the handle
+            if (dfx_set_size(dfx_, size.width, size.height) != DFX_OK)
+                throw std::runtime_error(string("dfx_set_size failed: ") + dfx_last_error(dfx_));
+        } else {
+            if (dfx_)
+                dfx_destroy(dfx_);
+            dfx_ = nullptr;
+            const int rc = dfx_create(&dfx_, device, DFX_ALGO_FRAMES, size.width, size.height, nullptr);
+            if (rc != DFX_OK)
+                throw std::runtime_error(string("dfx_create failed: ") + dfx_last_error(nullptr));
+            dfx_algo_ = (int)DFX_ALGO_FRAMES;
+        }
         dfx_size_ = size;
     }
     const size_t frame_bytes = (size_t)src_w_ * src_h_ * 3;
