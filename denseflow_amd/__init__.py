@@ -4,6 +4,9 @@ This package is a thin ctypes binding of the C ABI in include/dfx.h (implemented
 hand-written HIP kernels under denseflow_amd/csrc/).  It exists so that tests and bench.py can
 drive the exact entry points a denseflow maintainer would bind; the compute path is entirely
 inside libdfx.so.  There is no CPU fallback: a missing library or GPU raises.
+
+Tensor consumers: FlowEngine.calc_optflows_planar (numpy) and FlowEngine.flow_tensor (torch tensors in, an
+(M, 2, H, W) float32 torch tensor out, optionally bounded to [-1, 1]); torch is imported only inside flow_tensor.
 """
 from .engine import (  # noqa: F401
     DfxError,

@@ -26,7 +26,7 @@ class BroxEngine final : public AlgoEngine {
     int frame_slots() const override { return n_frame_slots; }
     int build_frames(const unsigned char *d_src, long long src_frame_stride, long long src_pitch, int n,
                      const int *h_slots) override;
-    int run_pairs(int nb, const PairDesc *h_pairs, float *d_out, long long out_stride) override;
+    int run_pairs(int nb, const PairDesc *h_pairs, float *d_out, long long out_stride, const DfxPlanarOut *planar) override;
     int account(int nb) override;
 
   private:
@@ -218,7 +218,7 @@ BroxLevelCtx BroxEngine::level_ctx(int l, int nb) const {
     return x;
 }
 
-int BroxEngine::run_pairs(int nb, const PairDesc *h_pairs, float *d_out, long long out_stride) {
+int BroxEngine::run_pairs(int nb, const PairDesc *h_pairs, float *d_out, long long out_stride, const DfxPlanarOut *planar) {
     std::memcpy(h_pairs_pinned, h_pairs, sizeof(PairDesc) * nb);
     HIPCHK(c, hipMemcpyAsync(d_pairs, h_pairs_pinned, sizeof(PairDesc) * nb, hipMemcpyHostToDevice, c->stream));
     const dfx_params &p = c->prm;
@@ -255,7 +255,10 @@ int BroxEngine::run_pairs(int nb, const PairDesc *h_pairs, float *d_out, long lo
             uv ^= 1;
             batch_launches += 1;
         } else {
-            brox_launch_merge(c->stream, x, uv, d_out, out_stride);
+            if (planar)
+                brox_launch_merge_planar(c->stream, x, uv, *planar);
+            else
+                brox_launch_merge(c->stream, x, uv, d_out, out_stride);
             batch_launches += 1;
         }
     }

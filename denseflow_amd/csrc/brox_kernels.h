@@ -56,3 +56,4 @@ void brox_launch_add_increment(hipStream_t s, const BroxLevelCtx &c, int uv_set,
 void brox_launch_prolongate(hipStream_t s, const BroxLevelCtx &c_coarse, int uv_set, int dw, int dh, int dpitch,
                             float factor, float mul);
 void brox_launch_merge(hipStream_t s, const BroxLevelCtx &c0, int uv_set, float *out, long long out_stride);
+void brox_launch_merge_planar(hipStream_t s, const BroxLevelCtx &c0, int uv_set, const DfxPlanarOut &o); // u and v planes, bounded

@@ -907,6 +907,12 @@ __global__ __launch_bounds__(256) void k_brox_merge(BroxLevelCtx c, int uv_set, 
     reinterpret_cast<float2 *>(out + (long long)b * out_stride)[(long long)y * c.w + x] = v;
 }
 
+// The same flow as two planes (DfxPlanarOut, dfx_device.h): u and v each go to the caller's plane, bounded on the way.
+__global__ __launch_bounds__(256) void k_brox_merge_planar(BroxLevelCtx c, int uv_set, DfxPlanarOut o) {
+    const int b = blockIdx.z;
+    dfx_planar_merge_tile(o, b, bplane(c, b, BROX_PL_U0 + 2 * uv_set), bplane(c, b, BROX_PL_V0 + 2 * uv_set), c.w, c.h, c.pitch);
+}
+
 // ------------------------------------------------------------------------------------------------ launchers
 
 void brox_launch_u8_to_f32(hipStream_t s, const unsigned char *src, long long src_frame_stride, long long src_pitch,
@@ -968,4 +974,8 @@ void brox_launch_prolongate(hipStream_t s, const BroxLevelCtx &c, int uv_set, in
 }
 void brox_launch_merge(hipStream_t s, const BroxLevelCtx &c, int uv_set, float *out, long long out_stride) {
     hipLaunchKernelGGL(k_brox_merge, bgrid(c.w, c.h, c.n_pairs), dim3(256), 0, s, c, uv_set, out, out_stride);
+}
+
+void brox_launch_merge_planar(hipStream_t s, const BroxLevelCtx &c, int uv_set, const DfxPlanarOut &o) {
+    hipLaunchKernelGGL(k_brox_merge_planar, dfx_planar_merge_grid(c.w, c.h, c.n_pairs), dim3(256), 0, s, c, uv_set, o);
 }

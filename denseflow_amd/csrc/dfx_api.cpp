@@ -2,6 +2,7 @@
 // The FlowBuffer driver is dfx_pipeline.cpp, colour frame extraction dfx_frames.cpp; the algorithms live in *_engine.cpp.
 #include <algorithm>
 #include <climits>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 
@@ -413,6 +414,67 @@ int dfx_calc_batch_device(dfx_handle h, const uint8_t *d_frames, size_t pitch, s
     OutSpec out;
     out.d_flows = d_flows;
     out.d_flow_stride = flow_stride_floats;
+    return dfx_run_flowbuffer(h, InSpec::device(d_frames, pitch, frame_stride), n_frames, step, out, nullptr);
+}
+
+namespace {
+// norm_bound of the planar forms: 0 (raw) or a bound that is a positive finite float
+bool planar_bound_ok(double norm_bound) {
+    if (norm_bound == 0.0)
+        return true;
+    const float b = (float)norm_bound;
+    return std::isfinite(norm_bound) && norm_bound > 0.0 && std::isfinite(b) && b > 0.0f;
+}
+const char *const kPlanarBound = "norm_bound must be 0 (raw values) or a positive finite float";
+} // namespace
+
+int dfx_calc_batch_planar(dfx_handle h, const uint8_t *const *frames, size_t frame_pitch, int n_frames, int step,
+                          double norm_bound, float *const *flows_u, float *const *flows_v, size_t out_pitch) {
+    if (!h)
+        return DFX_ERR_INVALID;
+    SegmentsScope seg_scope(h);
+    if (!planar_bound_ok(norm_bound))
+        return dfx_fail(h, DFX_ERR_INVALID, kPlanarBound);
+    const int M = std::max(n_frames - abs_step(step), 0);
+    if (M > 0 && (!frames || !flows_u || !flows_v))
+        return dfx_fail(h, DFX_ERR_INVALID, "NULL frames or flow plane arrays");
+    if (M > 0 && (pitch_too_small(h, frame_pitch) || out_pitch < (size_t)h->W * 4))
+        return dfx_fail(h, DFX_ERR_INVALID, "pitch smaller than a row");
+    OutSpec out;
+    out.planar = true;
+    out.norm_bound = (float)norm_bound;
+    out.flows_u = flows_u, out.flows_v = flows_v;
+    out.out_pitch = out_pitch;
+    return dfx_run_flowbuffer(h, InSpec::host(frames, frame_pitch), n_frames, step, out, nullptr);
+}
+
+int dfx_calc_batch_planar_device(dfx_handle h, const uint8_t *d_frames, size_t pitch, size_t frame_stride, int n_frames,
+                                 int step, double norm_bound, float *d_out, size_t row_pitch_floats,
+                                 size_t plane_stride_floats, size_t flow_stride_floats) {
+    if (!h)
+        return DFX_ERR_INVALID;
+    SegmentsScope seg_scope(h);
+    if (src_segments_pending(h))
+        return dfx_fail(h, DFX_ERR_UNSUPPORTED, "dfx_next_segments_src applies to host-pointer calls only");
+    if (!planar_bound_ok(norm_bound))
+        return dfx_fail(h, DFX_ERR_INVALID, kPlanarBound);
+    const int M = std::max(n_frames - abs_step(step), 0);
+    if (M > 0 && (!d_frames || !d_out))
+        return dfx_fail(h, DFX_ERR_INVALID, "NULL device frames or flow planes");
+    if (M > 0 && (pitch < h->in_row_bytes() || frame_stride < pitch * (size_t)h->in_h()))
+        return dfx_fail(h, DFX_ERR_INVALID, "pitch/stride smaller than a frame");
+    // the products cannot overflow: W, H <= 32768, and a stride that passes the check before it is what the next one multiplies
+    if (M > 0 && (row_pitch_floats < (size_t)h->W || row_pitch_floats > ((size_t)1 << 40) ||
+                  plane_stride_floats < (size_t)h->H * row_pitch_floats || plane_stride_floats > ((size_t)1 << 60) ||
+                  flow_stride_floats < 2 * plane_stride_floats))
+        return dfx_fail(h, DFX_ERR_INVALID,
+                        "planar output: row_pitch_floats >= W, plane_stride_floats >= H * row_pitch_floats and "
+                        "flow_stride_floats >= 2 * plane_stride_floats are required");
+    OutSpec out;
+    out.planar = true;
+    out.norm_bound = (float)norm_bound;
+    out.d_planar = d_out;
+    out.d_row_pitch = row_pitch_floats, out.d_plane_stride = plane_stride_floats, out.d_flow_stride = flow_stride_floats;
     return dfx_run_flowbuffer(h, InSpec::device(d_frames, pitch, frame_stride), n_frames, step, out, nullptr);
 }
 

@@ -79,6 +79,22 @@ struct Tvl1LevelCtx {
 static inline int dfx_round_up(int v, int m) { return (v + m - 1) / m * m; }
 
 // ------------------------------------------------------------------------------------------------
+// Planar float output (dfx_calc_batch_planar*): flow i of a launch is a u plane at base + i * flow_stride and a v plane
+// plane_stride floats behind it, rows row_pitch floats apart — the [M, 2, H, W] layout of a tensor consumer.  Every
+// engine's last writer stores both planes itself (dfx_planar_store*), the bound applied in the same store.
+struct DfxPlanarOut {
+    float *base;                                    // u plane of the launch's first flow
+    long long flow_stride, plane_stride, row_pitch; // in floats
+    float bound;                                    // 0: raw values; b > 0: clamp(x, -b, b) / b
+    int vec;                                        // floats per store that base and all three strides keep aligned: 4, 2 or 1
+};
+static inline int dfx_planar_vec(const float *base, long long flow_stride, long long plane_stride, long long row_pitch) {
+    const unsigned long long bits = (unsigned long long)(size_t)base | ((unsigned long long)flow_stride * 4) |
+                                    ((unsigned long long)plane_stride * 4) | ((unsigned long long)row_pitch * 4);
+    return (bits & 15) == 0 ? 4 : (bits & 7) == 0 ? 2 : 1;
+}
+
+// ------------------------------------------------------------------------------------------------
 // XCD-aware workgroup -> tile mapping (device code only).  MI355X has 8 XCDs with a private 4 MiB L2 each and the
 // dispatcher is observed to place workgroup b of a launch on XCD b % 8 (MI355X_MICROARCH.md, "Workgroup dispatch"):
 // with the plain blockIdx -> tile mapping the neighbours of a tile — whose halo, box-filter or gather footprint
@@ -93,6 +109,72 @@ DFX_HD int dfx_xcd_tile_index(int lin, int nt) {
     return k * q + (k < rem ? k : rem) + (lin >> 3);
 }
 #if defined(__HIPCC__)
+// One value on its way to a plane of DfxPlanarOut.  b == 0: the value itself, the bits the interleaved output holds.
+// b > 0: the clamped value through ONE IEEE division (no reciprocal), NaN -> 0: float32 np.clip(x, -b, b) / b.
+__device__ __forceinline__ float dfx_planar_value(float x, float b) {
+    if (b > 0.0f)
+        x = x != x ? 0.0f : __builtin_fminf(__builtin_fmaxf(x, -b), b) / b;
+    return x;
+}
+// Pixels x .. x + n - 1 (x a multiple of 4, n = 1..4) of row y of flow i, u and v each to its plane: one 16-byte store per
+// plane where o.vec and n allow, 8-byte stores for aligned pairs, single floats otherwise (odd widths, unaligned pitches).
+__device__ __forceinline__ void dfx_planar_store4(const DfxPlanarOut &o, int i, int x, int y, int n, const float (&u)[4],
+                                                  const float (&v)[4]) {
+    float *du = o.base + (long long)i * o.flow_stride + (long long)y * o.row_pitch + x;
+    float *dv = du + o.plane_stride;
+    float a[4], c[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        a[k] = dfx_planar_value(u[k], o.bound), c[k] = dfx_planar_value(v[k], o.bound);
+    if (o.vec == 4 && n == 4) {
+        *reinterpret_cast<float4 *>(du) = make_float4(a[0], a[1], a[2], a[3]);
+        *reinterpret_cast<float4 *>(dv) = make_float4(c[0], c[1], c[2], c[3]);
+        return;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; k += 2) {
+        if (o.vec >= 2 && k + 1 < n) {
+            *reinterpret_cast<float2 *>(du + k) = make_float2(a[k], a[k + 1]);
+            *reinterpret_cast<float2 *>(dv + k) = make_float2(c[k], c[k + 1]);
+        } else {
+            if (k < n)
+                du[k] = a[k], dv[k] = c[k];
+            if (k + 1 < n)
+                du[k + 1] = a[k + 1], dv[k + 1] = c[k + 1];
+        }
+    }
+}
+// The same for a lane that holds two pixels (x even, n = 1 or 2).
+__device__ __forceinline__ void dfx_planar_store2(const DfxPlanarOut &o, int i, int x, int y, int n, float u0, float u1,
+                                                  float v0, float v1) {
+    float *du = o.base + (long long)i * o.flow_stride + (long long)y * o.row_pitch + x;
+    float *dv = du + o.plane_stride;
+    const float a0 = dfx_planar_value(u0, o.bound), a1 = dfx_planar_value(u1, o.bound);
+    const float c0 = dfx_planar_value(v0, o.bound), c1 = dfx_planar_value(v1, o.bound);
+    if (o.vec >= 2 && n == 2) {
+        *reinterpret_cast<float2 *>(du) = make_float2(a0, a1);
+        *reinterpret_cast<float2 *>(dv) = make_float2(c0, c1);
+        return;
+    }
+    du[0] = a0, dv[0] = c0;
+    if (n == 2)
+        du[1] = a1, dv[1] = c1;
+}
+// The merge kernels' planar form: a workgroup of 256 lanes covers 256 x 4 pixels, a lane four neighbouring pixels of
+// one row — 16-byte loads from the engine's u and v planes (their pitch is a multiple of 64 floats, so the four floats
+// at a multiple of 4 below w exist), and a wave writes 1 KB of one row per plane.  su / sv: the planes' first pixel.
+__device__ __forceinline__ void dfx_planar_merge_tile(const DfxPlanarOut &o, int i, const float *su, const float *sv, int w,
+                                                      int h, int pitch) {
+    const int x = ((int)blockIdx.x * 64 + ((int)threadIdx.x & 63)) * 4;
+    const int y = (int)blockIdx.y * 4 + ((int)threadIdx.x >> 6);
+    if (x >= w || y >= h)
+        return;
+    const long long s = (long long)y * pitch + x;
+    const float4 a = *reinterpret_cast<const float4 *>(su + s), c = *reinterpret_cast<const float4 *>(sv + s);
+    const float u[4] = {a.x, a.y, a.z, a.w}, v[4] = {c.x, c.y, c.z, c.w};
+    dfx_planar_store4(o, i, x, y, min(4, w - x), u, v);
+}
+static inline dim3 dfx_planar_merge_grid(int w, int h, int n) { return dim3((w + 255) / 256, (h + 3) / 4, n); }
 #ifndef DFX_XCD_REMAP
 #define DFX_XCD_REMAP 1 // 0: plain blockIdx (A/B builds, scripts/build_variant.sh)
 #endif

@@ -45,7 +45,9 @@ class AlgoEngine {
     virtual int frame_slots() const = 0;
     virtual int build_frames(const unsigned char *d_src, long long src_frame_stride, long long src_pitch, int n,
                              const int *h_slots) = 0;
-    virtual int run_pairs(int nb, const PairDesc *h_pairs, float *d_out, long long out_stride) = 0;
+    // planar != nullptr: the flows go to *planar's u and v planes (dfx_device.h) instead, d_out / out_stride unused
+    virtual int run_pairs(int nb, const PairDesc *h_pairs, float *d_out, long long out_stride,
+                          const DfxPlanarOut *planar = nullptr) = 0;
     virtual int account(int nb) = 0; // reads per-batch event timers; stream is idle
     // dfxi_tvl1_batch_tables (dfx_api.cpp): the per-pair TVL1 tables of the last accounted batch, in pair order
     virtual int batch_tables(int max_pairs, int *iters, int *checks) const {

@@ -279,6 +279,12 @@ int FlowRun::download(size_t k) { // results of batch k: staging set par(k) -> h
                                           hipMemcpyDeviceToHost, c->d2h_stream));
                 HIPCHK(c, copy_rows_async(out.img_y[p.i0 + j], out.img_pitch, sy, c->W, c->W, c->H,
                                           hipMemcpyDeviceToHost, c->d2h_stream));
+            } else if (out.planar) { // staged dense: the u plane of flow j, then its v plane
+                const float *su = c->d_flow_out[q] + (size_t)j * plane * 2;
+                HIPCHK(c, copy_rows_async(out.flows_u[p.i0 + j], out.out_pitch, su, (size_t)c->W * 4, (size_t)c->W * 4, c->H,
+                                          hipMemcpyDeviceToHost, c->d2h_stream));
+                HIPCHK(c, copy_rows_async(out.flows_v[p.i0 + j], out.out_pitch, su + plane, (size_t)c->W * 4, (size_t)c->W * 4,
+                                          c->H, hipMemcpyDeviceToHost, c->d2h_stream));
             } else {
                 HIPCHK(c, copy_rows_async(out.flows[p.i0 + j], out.out_pitch, c->d_flow_out[q] + (size_t)j * plane * 2,
                                           (size_t)c->W * 8, (size_t)c->W * 8, c->H, hipMemcpyDeviceToHost,
@@ -310,12 +316,16 @@ DfxHandover FlowRun::describe(size_t k) const {
     } else if (bounce) {
         h.block = c->h_out[par(k)];
         h.two_planes = out.quantized;
+        h.float_planes = out.planar;
         h.W = c->W, h.H = c->H;
         h.pitch = out.quantized ? out.img_pitch : out.out_pitch;
         for (int j = 0; j < p.nb; ++j) {
             if (out.quantized) {
                 h.dst_a.push_back(out.img_x[p.i0 + j]);
                 h.dst_b.push_back(out.img_y[p.i0 + j]);
+            } else if (out.planar) {
+                h.dst_a.push_back(out.flows_u[p.i0 + j]);
+                h.dst_b.push_back(out.flows_v[p.i0 + j]);
             } else {
                 h.dst_a.push_back(out.flows[p.i0 + j]);
             }
@@ -414,9 +424,20 @@ int FlowRun::compute(size_t k) { // batch k on the compute stream, up to its sta
         c->h_pairs[j].frame_b = dfx_pair_b(pairs, i, step) % F;
     }
     const bool staged = host_mode || out.quantized;
-    float *dst = staged ? c->d_flow_out[q] : out.d_flows + (size_t)p.i0 * out.d_flow_stride;
+    float *dst = staged ? c->d_flow_out[q] : out.planar ? nullptr : out.d_flows + (size_t)p.i0 * out.d_flow_stride;
     const long long dst_stride = staged ? (long long)plane * 2 : (long long)out.d_flow_stride;
-    rc = E->run_pairs(p.nb, c->h_pairs.data(), dst, dst_stride);
+    if (out.planar) { // the engine's last kernel writes the planes: the caller's (device mode) or dense ones in staging set q
+        DfxPlanarOut po;
+        po.base = staged ? dst : out.d_planar + (size_t)p.i0 * out.d_flow_stride;
+        po.flow_stride = dst_stride;
+        po.plane_stride = staged ? (long long)plane : (long long)out.d_plane_stride;
+        po.row_pitch = staged ? (long long)c->W : (long long)out.d_row_pitch;
+        po.bound = out.norm_bound;
+        po.vec = dfx_planar_vec(po.base, po.flow_stride, po.plane_stride, po.row_pitch);
+        rc = E->run_pairs(p.nb, c->h_pairs.data(), nullptr, 0, &po);
+    } else {
+        rc = E->run_pairs(p.nb, c->h_pairs.data(), dst, dst_stride);
+    }
     if (rc != DFX_OK)
         return rc;
     if (out.quantized) {

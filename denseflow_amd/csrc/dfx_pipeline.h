@@ -21,7 +21,7 @@ struct InSpec {
     }
 };
 
-// Where the flows of a FlowBuffer go: float (u, v) fields or planes bounded to 8 bits on the device.
+// Where the flows of a FlowBuffer go: float (u, v) fields, float u and v planes, or planes bounded to 8 bits on the device.
 struct OutSpec {
     bool quantized = false;
     double lo = 0, hi = 0;
@@ -30,6 +30,13 @@ struct OutSpec {
     size_t out_pitch = 0;
     float *d_flows = nullptr; // device mode: flow i dense at d_flows + i*d_flow_stride
     size_t d_flow_stride = 0;
+    // planar float output (dfx_calc_batch_planar*): every engine's last kernel writes a u and a v plane per flow, raw
+    // (norm_bound = 0) or clamped to +-norm_bound and divided by it
+    bool planar = false;
+    float norm_bound = 0.f;
+    float *const *flows_u = nullptr, *const *flows_v = nullptr; // host mode: one pointer per plane, out_pitch bytes per row
+    float *d_planar = nullptr; // device mode: u plane of flow i at d_planar + i*d_flow_stride, v plane d_plane_stride behind
+    size_t d_row_pitch = 0, d_plane_stride = 0; // it, rows d_row_pitch floats apart (all in floats)
     // 8-bit output
     uint8_t *const *img_x = nullptr, *const *img_y = nullptr; // host mode: one pointer per plane
     size_t img_pitch = 0;                                     // bytes per row (host and device mode)

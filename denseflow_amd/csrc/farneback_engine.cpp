@@ -77,7 +77,7 @@ class FarnebackEngine final : public AlgoEngine {
     int frame_slots() const override { return n_frame_slots; }
     int build_frames(const unsigned char *d_src, long long src_frame_stride, long long src_pitch, int n,
                      const int *h_slots) override;
-    int run_pairs(int nb, const PairDesc *h_pairs, float *d_out, long long out_stride) override;
+    int run_pairs(int nb, const PairDesc *h_pairs, float *d_out, long long out_stride, const DfxPlanarOut *planar) override;
     int account(int nb) override;
 
   private:
@@ -294,7 +294,7 @@ int FarnebackEngine::build_frames(const unsigned char *d_src, long long src_fram
     return DFX_OK;
 }
 
-int FarnebackEngine::run_pairs(int nb, const PairDesc *h_pairs, float *d_out, long long out_stride) {
+int FarnebackEngine::run_pairs(int nb, const PairDesc *h_pairs, float *d_out, long long out_stride, const DfxPlanarOut *planar) {
     std::memcpy(h_pairs_pinned, h_pairs, sizeof(PairDesc) * nb);
     HIPCHK(c, hipMemcpyAsync(d_pairs, h_pairs_pinned, sizeof(PairDesc) * nb, hipMemcpyHostToDevice, c->stream));
     const dfx_params &p = c->prm;
@@ -327,8 +327,10 @@ int FarnebackEngine::run_pairs(int nb, const PairDesc *h_pairs, float *d_out, lo
             HIPCHK(c, hipEventRecord(ev_it[k][0], c->stream));
             for (int it = 0; it < p.farn_num_iters; ++it) {
                 const bool last = k == 0 && it == p.farn_num_iters - 1;
-                float *merged = last ? d_out : nullptr;
-                if (it == 0)
+                float *merged = last && !planar ? d_out : nullptr;
+                if (last && planar && it > 0)
+                    farn_launch_iter_stream_planar(c->stream, x, cur, cur ^ 1, box_inv, *planar);
+                else if (it == 0)
                     farn_launch_iter_stream_init(c->stream, x, cur, cur ^ 1, box_inv, merged, out_stride, P.w, P.h, P.pitch, ifx,
                                                  ify, up, top ? 1 : 0);
                 else
@@ -337,6 +339,10 @@ int FarnebackEngine::run_pairs(int nb, const PairDesc *h_pairs, float *d_out, lo
             }
             HIPCHK(c, hipEventRecord(ev_it[k][1], c->stream));
             c->stats.kernel_launches += p.farn_num_iters;
+        }
+        if (planar && p.farn_num_iters == 1) { // level 0's only iteration wrote plane set `cur`
+            farn_launch_merge_planar(c->stream, x, cur, *planar);
+            c->stats.kernel_launches += 1;
         }
         return DFX_OK;
     }
@@ -365,7 +371,10 @@ int FarnebackEngine::run_pairs(int nb, const PairDesc *h_pairs, float *d_out, lo
         set ^= 1; // the next (finer) level is initialised into the other set, from the one this level ended in
     }
     set ^= 1; // the set level 0 ended in
-    farn_launch_merge(c->stream, x, set, d_out, out_stride);
+    if (planar)
+        farn_launch_merge_planar(c->stream, x, set, *planar);
+    else
+        farn_launch_merge(c->stream, x, set, d_out, out_stride);
     c->stats.kernel_launches += 1;
     return DFX_OK;
 }

@@ -78,3 +78,8 @@ void farn_launch_iter_stream_init(hipStream_t s, const FarnPairCtx &c, int prev_
                                   float *merged, long long merged_stride, int prev_w, int prev_h, int prev_pitch, float ifx,
                                   float ify, float up, int zero);
 void farn_launch_merge(hipStream_t s, const FarnPairCtx &c, int flow_set, float *out, long long out_stride);
+// Planar output (DfxPlanarOut, dfx_device.h).  The last iteration of level 0 in the row-stream form, when it is not also
+// the level's first: the new flow goes to the caller's u and v planes, bounded.
+void farn_launch_iter_stream_planar(hipStream_t s, const FarnPairCtx &c, int flow_in, int flow_out, float box_inv,
+                                    const DfxPlanarOut &o);
+void farn_launch_merge_planar(hipStream_t s, const FarnPairCtx &c, int flow_set, const DfxPlanarOut &o);

@@ -859,10 +859,13 @@ struct FarnInit {
     int prev_w, prev_h, prev_pitch;
     float ifx, ify, up;
 };
-template <int HALF, bool INIT>
+// PLANAR: the last iteration of level 0 writes the caller's u and v planes (`po`, dfx_device.h) instead of interleaved rows:
+// an instantiation of its own (126 registers, 4 workgroups per CU), so that the kernels of every other launch stay the
+// code they were.  Not with INIT (a level of one iteration): that form would spill, and k_farn_merge_planar serves it.
+template <int HALF, bool INIT, bool PLANAR = false>
 __global__ __launch_bounds__(256, FARN_STREAM_WPS) void k_farn_iter_stream(FarnPairCtx c, int flow_in, int flow_out, float box_inv,
                                                              int seg_rows, float *merged, long long merged_stride,
-                                                             FarnInit init) {
+                                                             FarnInit init, DfxPlanarOut po) {
     constexpr int TW = 64, IW = TW + 2 * HALF, RB = 6, RING = RB + 2 * HALF, NP = IW / 2; // 38 column pairs per row
     static_assert(HALF == 6 && RING == 18 && RB * NP <= 256 && RB * (TW / 2) <= 256, "work split worked out for 6-row steps");
     __shared__ __attribute__((aligned(16))) f2 A[RING][IW];    // (M0, M2)
@@ -1090,7 +1093,11 @@ __global__ __launch_bounds__(256, FARN_STREAM_WPS) void k_farn_iter_stream(FarnP
                 fyo[i] = (g22 * h1 - g12 * h2) * detInv;
             }
             const unsigned o = (unsigned)(y * pitch + x);
-            if (merged) {
+            if constexpr (PLANAR) {
+                // a lane's two pixels go to both planes (8-byte stores where the caller's strides allow): 32 lanes write
+                // 256 B of one row per plane, bounded in the same store
+                dfx_planar_store2(po, b, x, y, x + 1 < w ? 2 : 1, fxo[0], fxo[1], fyo[0], fyo[1]);
+            } else if (merged) {
                 // the last iteration of level 0 writes the caller's interleaved (u, v) rows itself (k_farn_merge's job:
                 // one launch and 16 B/px of traffic less per pair); w may be odd, so an 8-byte store per pixel
                 float2 *dst = reinterpret_cast<float2 *>(merged + (long long)b * merged_stride) + ((long long)y * w + x);
@@ -1122,6 +1129,13 @@ __global__ __launch_bounds__(256) void k_farn_merge(FarnPairCtx c, int flow_set,
     v.x = farn_plane(c, b, FARN_PL_FX0 + 2 * flow_set)[o];
     v.y = farn_plane(c, b, FARN_PL_FY0 + 2 * flow_set)[o];
     reinterpret_cast<float2 *>(out + (long long)b * out_stride)[(long long)y * c.L.w + x] = v;
+}
+
+// The same flow as two planes (DfxPlanarOut, dfx_device.h): for the forms whose last iteration does not write the caller's rows.
+__global__ __launch_bounds__(256) void k_farn_merge_planar(FarnPairCtx c, int flow_set, DfxPlanarOut o) {
+    const int b = blockIdx.z;
+    dfx_planar_merge_tile(o, b, farn_plane(c, b, FARN_PL_FX0 + 2 * flow_set), farn_plane(c, b, FARN_PL_FY0 + 2 * flow_set), c.L.w,
+                          c.L.h, c.L.pitch);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1209,7 +1223,15 @@ void farn_launch_iter_stream(hipStream_t s, const FarnPairCtx &c, int flow_in, i
     const int seg_rows = farn_stream_seg_rows(c.L.w, c.L.h, c.n_pairs);
     const dim3 grid((c.L.w + 63) / 64, (c.L.h + seg_rows - 1) / seg_rows, c.n_pairs);
     hipLaunchKernelGGL((k_farn_iter_stream<6, false>), grid, dim3(256), 0, s, c, flow_in, flow_out, box_inv, seg_rows, merged,
-                       merged_stride, FarnInit{});
+                       merged_stride, FarnInit{}, DfxPlanarOut{});
+}
+
+void farn_launch_iter_stream_planar(hipStream_t s, const FarnPairCtx &c, int flow_in, int flow_out, float box_inv,
+                                    const DfxPlanarOut &o) {
+    const int seg_rows = farn_stream_seg_rows(c.L.w, c.L.h, c.n_pairs);
+    const dim3 grid((c.L.w + 63) / 64, (c.L.h + seg_rows - 1) / seg_rows, c.n_pairs);
+    hipLaunchKernelGGL((k_farn_iter_stream<6, false, true>), grid, dim3(256), 0, s, c, flow_in, flow_out, box_inv, seg_rows,
+                       (float *)nullptr, 0ll, FarnInit{}, o);
 }
 
 void farn_launch_iter_stream_init(hipStream_t s, const FarnPairCtx &c, int prev_set, int flow_out, float box_inv,
@@ -1220,10 +1242,14 @@ void farn_launch_iter_stream_init(hipStream_t s, const FarnPairCtx &c, int prev_
     FarnInit in;
     in.zero = zero, in.prev_w = prev_w, in.prev_h = prev_h, in.prev_pitch = prev_pitch, in.ifx = ifx, in.ify = ify, in.up = up;
     hipLaunchKernelGGL((k_farn_iter_stream<6, true>), grid, dim3(256), 0, s, c, prev_set, flow_out, box_inv, seg_rows, merged,
-                       merged_stride, in);
+                       merged_stride, in, DfxPlanarOut{});
 }
 
 void farn_launch_merge(hipStream_t s, const FarnPairCtx &c, int flow_set, float *out, long long out_stride) {
     hipLaunchKernelGGL(k_farn_merge, grid64x4(c.L.w, c.L.h, c.n_pairs), dim3(256), 0, s, c, flow_set, out,
                        out_stride);
+}
+
+void farn_launch_merge_planar(hipStream_t s, const FarnPairCtx &c, int flow_set, const DfxPlanarOut &o) {
+    hipLaunchKernelGGL(k_farn_merge_planar, dfx_planar_merge_grid(c.L.w, c.L.h, c.n_pairs), dim3(256), 0, s, c, flow_set, o);
 }

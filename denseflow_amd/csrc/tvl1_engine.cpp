@@ -34,7 +34,7 @@ class Tvl1Engine final : public AlgoEngine {
     int frame_slots() const override { return n_frame_slots; }
     int build_frames(const unsigned char *d_src, long long src_frame_stride, long long src_pitch, int n,
                      const int *h_slots) override;
-    int run_pairs(int nb, const PairDesc *h_pairs, float *d_out, long long out_stride) override;
+    int run_pairs(int nb, const PairDesc *h_pairs, float *d_out, long long out_stride, const DfxPlanarOut *planar) override;
     int account(int nb) override;
     int batch_tables(int max_pairs, int *iters, int *checks) const override;
 
@@ -361,7 +361,7 @@ int Tvl1Engine::steps_per_group(int s, int nb) const {
     return std::max(min_group, std::min(16, g));
 }
 
-int Tvl1Engine::run_pairs(int nb, const PairDesc *h_pairs, float *d_out, long long out_stride) {
+int Tvl1Engine::run_pairs(int nb, const PairDesc *h_pairs, float *d_out, long long out_stride, const DfxPlanarOut *planar) {
     last_nb = 0; // the read-backs below overwrite the last batch's tables
     std::memcpy(h_pairs_pinned, h_pairs, sizeof(PairDesc) * nb);
     HIPCHK(c, hipMemcpyAsync(d_pairs, h_pairs_pinned, sizeof(PairDesc) * nb, hipMemcpyHostToDevice, c->stream));
@@ -411,6 +411,8 @@ int Tvl1Engine::run_pairs(int nb, const PairDesc *h_pairs, float *d_out, long lo
             const float ifx = (float)(1.0 / ((double)D.w / (double)S.w));
             const float ify = (float)(1.0 / ((double)D.h / (double)S.h));
             tvl1_launch_upsample_u(c->stream, x, D.w, D.h, D.pitch, ifx, ify, up);
+        } else if (planar) {
+            tvl1_launch_merge_planar(c->stream, x, *planar);
         } else {
             tvl1_launch_merge(c->stream, x, d_out, out_stride);
         }

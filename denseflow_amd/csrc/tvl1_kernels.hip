@@ -166,6 +166,13 @@ __global__ __launch_bounds__(256) void k_tvl1_merge(Tvl1LevelCtx c, float *out, 
     reinterpret_cast<float2 *>(out + (long long)b * out_stride)[(long long)y * c.w + x] = v;
 }
 
+// The same flow as two planes (DfxPlanarOut, dfx_device.h): u1 and u2 each go to the caller's plane, bounded on the way.
+__global__ __launch_bounds__(256) void k_tvl1_merge_planar(Tvl1LevelCtx c, DfxPlanarOut o) {
+    const int b = blockIdx.z;
+    const int cur = c.state[b].cur;
+    dfx_planar_merge_tile(o, b, pair_plane(c, b, PL_U1_0 + 2 * cur), pair_plane(c, b, PL_U2_0 + 2 * cur), c.w, c.h, c.pitch);
+}
+
 // ------------------------------------------------------------------------------------------------
 // A.6 primal update of one pixel from planes in global memory (simple variant)
 
@@ -790,4 +797,8 @@ void tvl1_launch_upsample_u(hipStream_t s, const Tvl1LevelCtx &c_src, int dw, in
 
 void tvl1_launch_merge(hipStream_t s, const Tvl1LevelCtx &c0, float *out, long long out_stride) {
     hipLaunchKernelGGL(k_tvl1_merge, grid_for(c0.w, c0.h, c0.n_pairs), dim3(256), 0, s, c0, out, out_stride);
+}
+
+void tvl1_launch_merge_planar(hipStream_t s, const Tvl1LevelCtx &c0, const DfxPlanarOut &o) {
+    hipLaunchKernelGGL(k_tvl1_merge_planar, dfx_planar_merge_grid(c0.w, c0.h, c0.n_pairs), dim3(256), 0, s, c0, o);
 }

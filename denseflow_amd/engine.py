@@ -171,6 +171,11 @@ def load_library():
     L.dfx_calc_batch.restype = i
     L.dfx_calc_batch_device.argtypes = [vp, vp, sz, sz, i, i, vp, sz]
     L.dfx_calc_batch_device.restype = i
+    if hasattr(L, "dfx_calc_batch_planar"):  # a library built before the planar output (DFX_LIBRARY A/B) still loads
+        L.dfx_calc_batch_planar.argtypes = [vp, C.POINTER(vp), sz, i, i, C.c_double, C.POINTER(vp), C.POINTER(vp), sz]
+        L.dfx_calc_batch_planar.restype = i
+        L.dfx_calc_batch_planar_device.argtypes = [vp, vp, sz, sz, i, i, C.c_double, vp, sz, sz, sz]
+        L.dfx_calc_batch_planar_device.restype = i
     L.dfx_calc_batch_u8.argtypes = [vp, C.POINTER(vp), sz, i, i, C.c_double, C.c_double, C.POINTER(vp), C.POINTER(vp), sz]
     L.dfx_calc_batch_u8.restype = i
     L.dfx_submit_batch.argtypes = [vp, C.POINTER(vp), sz, i, i, C.POINTER(vp), sz, C.POINTER(C.c_uint64)]
@@ -289,6 +294,7 @@ class FlowEngine:
         self._L = load_library()
         self._h = C.c_void_p()
         self.width, self.height = int(width), int(height)
+        self._device = int(device)
         self.algorithm = algorithm
         # "frames": a handle without flow state, for the colour frame extraction (no -a=<name> maps to it)
         algo = ALGO_FRAMES if algorithm == "frames" else algo_from_name(algorithm)
@@ -512,6 +518,109 @@ class FlowEngine:
         self._arm()
         self._check(self._L.dfx_calc_batch_device(self._h, d_frames_ptr, pitch, frame_stride, n_frames, int(step),
                                                   d_flows_ptr, flow_stride_floats))
+
+    # -- planar float flows for tensor consumers (dfx_calc_batch_planar*) --------------------------------------
+    def calc_optflows_planar(self, frames_gray, step: int, bound: float | None = None) -> np.ndarray:
+        """calc_optflows as one (M, 2, H, W) float32 array: channel 0 = u, 1 = v, written as planes by the engine's last
+        kernel.  bound None: the raw flow values; bound > 0: clamp(x, -bound, bound) / bound in float32, NaN -> 0."""
+        frames = self._frames_in(frames_gray)
+        n = len(frames)
+        m = self._num_pairs(n, step)
+        out = np.empty((m, 2, self.height, self.width), dtype=np.float32)
+        if m == 0:
+            return out
+        self._check_shapes(frames)
+        fp = (C.c_void_p * n)(*[f.ctypes.data for f in frames])
+        up = (C.c_void_p * m)(*[out[k, 0].ctypes.data for k in range(m)])
+        vp = (C.c_void_p * m)(*[out[k, 1].ctypes.data for k in range(m)])
+        self._arm()
+        self._check(self._L.dfx_calc_batch_planar(self._h, fp, frames[0].strides[0], n, int(step),
+                                                  0.0 if bound is None else float(bound), up, vp, self.width * 4))
+        return out
+
+    def calc_optflows_planar_device(self, d_frames_ptr: int, pitch: int, frame_stride: int, n_frames: int, step: int,
+                                    bound: float | None, d_out_ptr: int, row_pitch_floats: int, plane_stride_floats: int,
+                                    flow_stride_floats: int):
+        """Frames and planes resident in HBM (raw device pointers): flow i's u plane at d_out + i * flow_stride_floats, its
+        v plane plane_stride_floats behind it, rows row_pitch_floats apart."""
+        self._num_pairs(n_frames, step)
+        self._arm()
+        self._check(self._L.dfx_calc_batch_planar_device(self._h, d_frames_ptr, pitch, frame_stride, n_frames, int(step),
+                                                         0.0 if bound is None else float(bound), d_out_ptr,
+                                                         row_pitch_floats, plane_stride_floats, flow_stride_floats))
+
+    def flow_tensor(self, frames, step: int, bound: float | None = None, out=None):
+        """Flows of a FlowBuffer of torch frames as an (M, 2, H, W) float32 torch tensor on the same device, the layout
+        (and, with bound, the [-1, 1] scaling) a two-stream / TSN / I3D network takes: no pointer handling, no permute
+        pass, no clamp-and-divide pass.
+
+        frames: torch.uint8 tensor on this handle's device, (N, H, W), or (N, Hs, Ws, 3) BGR / (N, Hs, Ws) gray when a
+        source format is set.  Any strides as long as the innermost dimension is contiguous (for BGR: the pixel's three
+        bytes too); row pitch and frame stride are taken from the tensor.
+        out: optional (M, 2, H, W) float32 tensor on that device to write into, any strides with a contiguous innermost
+        dimension that do not make rows, planes or flows overlap; otherwise the result is allocated.
+        bound None: raw flow values, bit for bit those of calc_optflows; bound > 0: clamp(x, -bound, bound) / bound.
+
+        Streams: torch's current stream on that device is synchronised before the call, so frames produced on it just
+        before are complete; the library call returns with all its device work complete, so the result may be used on
+        any stream afterwards without further synchronisation.
+
+        Raises ValueError — before the library is reached — for a wrong dtype, device, rank or shape, a non-contiguous
+        innermost dimension, or an `out` that does not match."""
+        import torch
+
+        if not isinstance(frames, torch.Tensor):
+            raise ValueError("frames must be a torch tensor")
+        if frames.dtype != torch.uint8:
+            raise ValueError("frames must be torch.uint8")
+        shape = self._frame_shape()
+        if frames.dim() != 1 + len(shape) or tuple(frames.shape[1:]) != tuple(shape):
+            raise ValueError(f"frames must be (N,) + {tuple(shape)}")
+        st = frames.stride()
+        if st[-1] != 1 or (len(shape) == 3 and st[2] != 3):
+            raise ValueError("the innermost dimension of frames must be contiguous")
+        n = int(frames.shape[0])
+        row_bytes = shape[1] * (3 if len(shape) == 3 else 1)
+        pitch = st[1] if shape[0] > 1 else row_bytes  # (the stride of a dimension of size 1 means nothing)
+        frame_stride = st[0] if n > 1 else pitch * shape[0]
+        if pitch < row_bytes or frame_stride < pitch * shape[0]:
+            raise ValueError("frames: rows or frames overlap")
+        dev = frames.device
+        m = self._peek_pairs(n, step)
+        want = (m, 2, self.height, self.width)
+        if out is not None:
+            if not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.device != dev:
+                raise ValueError("out must be a torch.float32 tensor on the frames' device")
+            if tuple(out.shape) != want:
+                raise ValueError(f"out must have shape {want}")
+            so = out.stride()
+            row_pitch = so[2] if self.height > 1 else self.width
+            plane_stride, flow_stride = so[1], (so[0] if m > 1 else 2 * so[1])
+            if so[3] != 1 or row_pitch < self.width or plane_stride < self.height * row_pitch or flow_stride < 2 * plane_stride:
+                raise ValueError("out: the innermost dimension must be contiguous and rows, planes and flows must not overlap")
+        if dev.type != "cuda" or (dev.index is not None and dev.index != getattr(self, "_device", dev.index)):
+            raise ValueError("frames must be on this handle's device")
+        if out is None:
+            out = torch.empty(want, dtype=torch.float32, device=dev)
+            row_pitch, plane_stride = self.width, self.height * self.width
+            flow_stride = 2 * plane_stride
+        self._num_pairs(n, step)
+        torch.cuda.current_stream(dev).synchronize()
+        self._arm()
+        self._check(self._L.dfx_calc_batch_planar_device(self._h, frames.data_ptr() if n else None, pitch, frame_stride, n,
+                                                         int(step), 0.0 if bound is None else float(bound),
+                                                         out.data_ptr() if m else None, row_pitch, plane_stride,
+                                                         flow_stride))
+        return out
+
+    def _peek_pairs(self, n: int, step: int) -> int:
+        """The number of flows the next call gives for n frames, a pending next_segments included; consumes nothing."""
+        seg = getattr(self, "_pending_seg", None)
+        if seg is None:
+            return max(n - abs(int(step)), 0)
+        if sum(seg) != n or min(seg, default=0) < 0:
+            raise ValueError("segment lengths must be >= 0 and add up to the number of frames")
+        return sum(max(x - abs(int(step)), 0) for x in seg)
 
     # -- flow bounding on the device (reference: convertFlowToImage, src/common.cpp:4-16) ------
     def calc_optflows_u8(self, frames_gray, step: int, bound: float, lower: float | None = None):
