@@ -12,6 +12,7 @@
 
 #include "dfx_internal.h"
 #include "farneback_kernels.h"
+#include "farneback_plan.h"
 
 namespace {
 
@@ -138,20 +139,21 @@ int FarnebackEngine::create() {
     // cross-check forms of the frame preparation (dfx_params.variant; same bits both ways)
     skip_zero_weights = (p.variant & DFX_VAR_FARN_EVAL_ZERO_TAPS) ? 0 : farn_skip_zero_weights_default();
     polyexp_rows = (p.variant & DFX_VAR_FARN_POLY_ONE_ROW) ? 0 : farn_polyexp_rows_default();
-    if (p.farn_poly_n != 5)
-        return dfx_fail(c, DFX_ERR_UNSUPPORTED, "Farneback: only polyN = 5 (the reference's default) is built");
+    if (p.farn_poly_n != 5 && p.farn_poly_n != 7)
+        return dfx_fail(c, DFX_ERR_UNSUPPORTED, "Farneback: polyN must be 5 or 7 (the two expansions upstream builds)");
     if (p.farn_flags != 0)
         return dfx_fail(c, DFX_ERR_UNSUPPORTED, "Farneback: only flags = 0 (box-filter update, the reference's default)");
-    if (p.farn_win_size < 1 || !(p.farn_win_size & 1) || p.farn_win_size / 2 > 8)
-        return dfx_fail(c, DFX_ERR_UNSUPPORTED, "Farneback: winSize must be odd and <= 17");
+    if (p.farn_win_size < 1 || !(p.farn_win_size & 1) || p.farn_win_size > 31)
+        return dfx_fail(c, DFX_ERR_UNSUPPORTED, "Farneback: winSize must be odd and <= 31");
     if (p.farn_num_levels < 0 || p.farn_num_levels >= DFX_LVL_MAX || p.farn_num_iters < 1 ||
         !(p.farn_pyr_scale > 0.0 && p.farn_pyr_scale < 1.0))
         return dfx_fail(c, DFX_ERR_INVALID, "invalid Farneback parameters");
 
     prepare_poly(p.farn_poly_n, p.farn_poly_sigma, &pc);
     // The default iteration kernel keeps M on chip: a pair slot is its two flow sets (4 planes, 33 MB at 1080p).  The
-    // M-in-HBM kernels (another window size, impl = 1, DFX_VAR_FARN_M_IN_HBM) need the two M sets as well (14 planes).
-    m_on_chip = p.impl == 0 && p.farn_win_size / 2 == 6 && !(p.variant & DFX_VAR_FARN_M_IN_HBM);
+    // M-in-HBM kernels (a window the row-stream kernel is not built for: farn_stream_has_half; impl = 1;
+    // DFX_VAR_FARN_M_IN_HBM) need the two M sets as well (14 planes).
+    m_on_chip = p.impl == 0 && farn_stream_has_half(p.farn_win_size / 2) && !(p.variant & DFX_VAR_FARN_M_IN_HBM);
     for (auto &e : ev_it) {
         HIPCHK(c, hipEventCreateWithFlags(&e[0], dfx_event_flags(c, true)));
         HIPCHK(c, hipEventCreateWithFlags(&e[1], dfx_event_flags(c, true)));
@@ -288,7 +290,8 @@ int FarnebackEngine::build_frames(const unsigned char *d_src, long long src_fram
                                d_tmpv, plane_stride * 2, skip_zero_weights);
         farn_launch_blur_h_resize(c->stream, d_tmpv, plane_stride * 2, n, W, H, pitch0, L.g.w, L.g.h, L.g.pitch, L.ifx,
                                   L.ify, d_gker + L.ker_off, L.half, d_pyr, plane_stride, skip_zero_weights);
-        farn_launch_polyexp(c->stream, d_pyr, plane_stride, n, d_frame_slots, d_R, frame_elems, L.g, pc, polyexp_rows);
+        farn_launch_polyexp(c->stream, d_pyr, plane_stride, n, d_frame_slots, d_R, frame_elems, L.g, pc, polyexp_rows,
+                            c->prm.farn_poly_n);
     }
     c->stats.kernel_launches += (from_u8 ? 0 : 1) + 3 * nlev;
     return DFX_OK;
@@ -310,8 +313,8 @@ int FarnebackEngine::run_pairs(int nb, const PairDesc *h_pairs, float *d_out, lo
     x.slot_stride = slot_stride;
     x.pairs = d_pairs;
     x.n_pairs = nb;
-    // M recomputed inside the iteration kernel (round 4) unless the window is not the reference's 13 or a cross-check
-    // form is asked for
+    // M recomputed inside the iteration kernel (round 4) unless the window is not one of the row-stream kernel's or a
+    // cross-check form is asked for
     const bool fused = m_on_chip;
     if (fused) {
         // One launch per iteration and nothing else: the first iteration of a level up-samples the coarser level's flow
@@ -329,12 +332,12 @@ int FarnebackEngine::run_pairs(int nb, const PairDesc *h_pairs, float *d_out, lo
                 const bool last = k == 0 && it == p.farn_num_iters - 1;
                 float *merged = last && !planar ? d_out : nullptr;
                 if (last && planar && it > 0)
-                    farn_launch_iter_stream_planar(c->stream, x, cur, cur ^ 1, box_inv, *planar);
+                    farn_launch_iter_stream_planar(c->stream, x, half, cur, cur ^ 1, box_inv, *planar);
                 else if (it == 0)
-                    farn_launch_iter_stream_init(c->stream, x, cur, cur ^ 1, box_inv, merged, out_stride, P.w, P.h, P.pitch, ifx,
+                    farn_launch_iter_stream_init(c->stream, x, half, cur, cur ^ 1, box_inv, merged, out_stride, P.w, P.h, P.pitch, ifx,
                                                  ify, up, top ? 1 : 0);
                 else
-                    farn_launch_iter_stream(c->stream, x, cur, cur ^ 1, box_inv, merged, out_stride);
+                    farn_launch_iter_stream(c->stream, x, half, cur, cur ^ 1, box_inv, merged, out_stride);
                 cur ^= 1;
             }
             HIPCHK(c, hipEventRecord(ev_it[k][1], c->stream));

@@ -52,10 +52,10 @@ void farn_launch_blur_h_resize(hipStream_t s, const float *tmpv, long long tmpv_
                                int H, int pitch0, int dst_w, int dst_h, int dst_pitch, float ifx, float ify,
                                const float *ker_half, int half, float *pyr, long long pyr_frame_stride,
                                int skip_zero_weights);
-// polynomial expansion (B.5) of n_frames level images into their frame slots
+// polynomial expansion (B.5, polyN = poly_n: 5 or 7) of n_frames level images into their frame slots
 void farn_launch_polyexp(hipStream_t s, const float *pyr, long long pyr_frame_stride, int n_frames,
                          const int *frame_slots, float *frame_R, long long frame_stride, FarnLevelGeom L,
-                         FarnPolyConsts pc, int rows_per_workgroup);
+                         FarnPolyConsts pc, int rows_per_workgroup, int poly_n);
 // the defaults of the two frame-preparation switches (the engine overrides them from dfx_params.variant:
 // DFX_VAR_FARN_EVAL_ZERO_TAPS, DFX_VAR_FARN_POLY_ONE_ROW)
 int farn_skip_zero_weights_default();
@@ -67,19 +67,20 @@ void farn_launch_update_matrices(hipStream_t s, const FarnPairCtx &c, int flow_s
 // boxFilter5 + updateFlow (+ updateMatrices) in one launch (B.8, B.9, B.7)
 void farn_launch_iteration(hipStream_t s, const FarnPairCtx &c, int flow_set, int m_src, int half, float box_inv,
                            int do_matrices, int impl);
-// the iteration with M recomputed where the box filter needs it (winSize 13 only): reads flow set flow_in, writes flow
-// set flow_out; a stream down 64-column strips with a ring of 18 M rows in LDS (round 4's default)
+// the iteration with M recomputed where the box filter needs it (half = winSize / 2 with farn_stream_has_half(half),
+// farneback_plan.h: winSize 7 .. 21): reads flow set flow_in, writes flow set flow_out; a stream down 64-column strips
+// with a ring of 6 + 2 * half M rows in LDS (round 4's default)
 // merged != nullptr (the last iteration of level 0): the new flow goes to the caller's interleaved (u, v) rows instead
-void farn_launch_iter_stream(hipStream_t s, const FarnPairCtx &c, int flow_in, int flow_out, float box_inv, float *merged,
-                             long long merged_stride);
+void farn_launch_iter_stream(hipStream_t s, const FarnPairCtx &c, int half, int flow_in, int flow_out, float box_inv,
+                             float *merged, long long merged_stride);
 // the first iteration of a level: its input flow is the coarser level's final flow (plane set prev_set, that level's
 // geometry) up-sampled on the fly, or zero at the coarsest level — no init launch
-void farn_launch_iter_stream_init(hipStream_t s, const FarnPairCtx &c, int prev_set, int flow_out, float box_inv,
+void farn_launch_iter_stream_init(hipStream_t s, const FarnPairCtx &c, int half, int prev_set, int flow_out, float box_inv,
                                   float *merged, long long merged_stride, int prev_w, int prev_h, int prev_pitch, float ifx,
                                   float ify, float up, int zero);
 void farn_launch_merge(hipStream_t s, const FarnPairCtx &c, int flow_set, float *out, long long out_stride);
 // Planar output (DfxPlanarOut, dfx_device.h).  The last iteration of level 0 in the row-stream form, when it is not also
 // the level's first: the new flow goes to the caller's u and v planes, bounded.
-void farn_launch_iter_stream_planar(hipStream_t s, const FarnPairCtx &c, int flow_in, int flow_out, float box_inv,
+void farn_launch_iter_stream_planar(hipStream_t s, const FarnPairCtx &c, int half, int flow_in, int flow_out, float box_inv,
                                     const DfxPlanarOut &o);
 void farn_launch_merge_planar(hipStream_t s, const FarnPairCtx &c, int flow_set, const DfxPlanarOut &o);

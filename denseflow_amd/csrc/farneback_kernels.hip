@@ -24,7 +24,7 @@
 #include "farneback_kernels.h"
 #include "farneback_plan.h"
 
-#define FARN_HALF_MAX 8 // box half-width supported by the fused iteration kernel (winSize <= 17)
+#define FARN_HALF_MAX 15 // box half-width supported by the fused iteration kernel (winSize <= 31)
 
 static inline dim3 grid64x4(int w, int h, int z) { return dim3((w + 63) / 64, (h + 3) / 4, z); }
 
@@ -184,12 +184,13 @@ __global__ __launch_bounds__(256) void k_farn_blur_h_resize(const float *__restr
     pyr[(long long)blockIdx.z * pyr_frame_stride + (long long)dy * dst_pitch + dx] = out;
 }
 
-// B.5: one workgroup = one row segment of 256 - 2*5 output pixels; vertical pass into LDS, then the
-// horizontal combinations.  (polyN = 5.)
+// B.5: one workgroup = one row segment of 256 - 2*N output pixels; vertical pass into LDS, then the
+// horizontal combinations.  N = polyN: 5 (the reference's value) or 7, the two expansions upstream builds.
+template <int N>
 __global__ __launch_bounds__(256) void k_farn_polyexp(const float *pyr, long long pyr_frame_stride,
                                                       const int *frame_slots, float *frame_R, long long frame_stride,
                                                       FarnLevelGeom L, FarnPolyConsts pc) {
-    constexpr int N = 5;
+    static_assert(N == 5 || N == 7, "FarnPolyConsts holds taps 0 .. 7");
     __shared__ float row[3][256];
     const int tx = threadIdx.x;
     const int y = blockIdx.y;
@@ -236,15 +237,15 @@ __global__ __launch_bounds__(256) void k_farn_polyexp(const float *pyr, long lon
     }
 }
 
-// B.5 again, ROWS image rows per workgroup: a thread walks down its column with the 11 source values of the vertical
-// pass in registers (one new load per row instead of eleven), the three vertical sums of a row go to one of two LDS row
+// B.5 again, ROWS image rows per workgroup: a thread walks down its column with the 2N + 1 source values of the vertical
+// pass in registers (one new load per row instead of 2N + 1), the three vertical sums of a row go to one of two LDS row
 // buffers (one barrier per row) and the horizontal combinations are the ones of k_farn_polyexp, in the same order.
-template <int ROWS>
+template <int ROWS, int N>
 __global__ __launch_bounds__(256) void k_farn_polyexp_rows(const float *__restrict__ pyr, long long pyr_frame_stride,
                                                            const int *__restrict__ frame_slots,
                                                            float *__restrict__ frame_R, long long frame_stride,
                                                            FarnLevelGeom L, FarnPolyConsts pc) {
-    constexpr int N = 5;
+    static_assert(N == 5 || N == 7, "FarnPolyConsts holds taps 0 .. 7");
     __shared__ float row[2][3][256];
     const int tx = threadIdx.x;
     const DfxBlockXY blk = dfx_block_xy();
@@ -430,7 +431,8 @@ __global__ __launch_bounds__(256) void k_farn_update_matrices(FarnPairCtx c, int
         farn_plane(c, b, (m_set ? FARN_PL_M1 : FARN_PL_M0) + p)[o] = M[p];
 }
 
-// One Farneback iteration in one launch: 13x13 box filter of the 5 M planes (B.8: vertical sums, then
+// One Farneback iteration in one launch for a run-time box half-width up to FARN_HALF_MAX (rows and columns of the halo
+// clamp, so a level may be narrower or shorter than the window): box filter of the 5 M planes (B.8: vertical sums, then
 // horizontal sums, in upstream's order, replicate border), the 2x2 solve (B.9) and, unless this is
 // the last iteration, the next M (B.7) written to the other M set.
 // Tile: 64 x 16 output pixels per workgroup, 4 rows per thread; LDS: (64+2h) x (16+2h) input tile and
@@ -837,7 +839,8 @@ __device__ __forceinline__ void farn_sample_pair(const float *__restrict__ R1, u
 
 // ------------------------------------------------------------------------------------------------
 // The iteration as a STREAM down a column strip.  A workgroup (4 waves) owns 64 output columns of a segment of rows and
-// walks down it 6 rows at a time with a ring of 18 M rows in LDS (27 KB):
+// walks down it 6 rows at a time with a ring of 6 + 2 * HALF M rows in LDS (18 rows, 27 KB, at the reference's window,
+// HALF = 6, whose figures the comments below quote):
 //     step:  updateMatrices for the 6 rows entering the window (76 columns: halo factor 1.19)   -> ring
 //            vertical 13-sums of the 6 output rows, one column per lane, written over the 6 rows leaving the window
 //            horizontal 13-sums + the 2x2 solve for 6 x 64 pixels                               -> flow_out
@@ -862,12 +865,19 @@ struct FarnInit {
 // PLANAR: the last iteration of level 0 writes the caller's u and v planes (`po`, dfx_device.h) instead of interleaved rows:
 // an instantiation of its own (126 registers, 4 workgroups per CU), so that the kernels of every other launch stay the
 // code they were.  Not with INIT (a level of one iteration): that form would spill, and k_farn_merge_planar serves it.
+// HALF = winSize / 2, 3 .. 10 (farneback_plan.h).  The ring is RB + 2 * HALF rows of 64 + 2 * HALF columns, 20 B each:
+// 16.4 KB at HALF 3, 27.4 KB at 6 (the reference's window), 43.7 KB at 10, where three workgroups fit a CU's LDS — that
+// instantiation is compiled for three waves per SIMD, and so are the PLANAR ones above HALF 6, whose vertical-sum window
+// (RING float2 registers) would spill at 128 registers; the others for four (the resource table in DESIGN.md).
+constexpr int farn_stream_wps(int half, bool planar) { return (half <= 6 || (!planar && half <= 9)) ? FARN_STREAM_WPS : 3; }
 template <int HALF, bool INIT, bool PLANAR = false>
-__global__ __launch_bounds__(256, FARN_STREAM_WPS) void k_farn_iter_stream(FarnPairCtx c, int flow_in, int flow_out, float box_inv,
+__global__ __launch_bounds__(256, farn_stream_wps(HALF, PLANAR)) void k_farn_iter_stream(FarnPairCtx c, int flow_in, int flow_out, float box_inv,
                                                              int seg_rows, float *merged, long long merged_stride,
                                                              FarnInit init, DfxPlanarOut po) {
-    constexpr int TW = 64, IW = TW + 2 * HALF, RB = 6, RING = RB + 2 * HALF, NP = IW / 2; // 38 column pairs per row
-    static_assert(HALF == 6 && RING == 18 && RB * NP <= 256 && RB * (TW / 2) <= 256, "work split worked out for 6-row steps");
+    // WARM: rows of the window above its first output row and below its last; NP: column pairs per row (38 at HALF 6)
+    constexpr int TW = 64, IW = TW + 2 * HALF, RB = 6, WARM = 2 * HALF, RING = RB + WARM, NP = IW / 2;
+    static_assert(HALF >= 3 && HALF <= 10 && RB * NP <= 256 && IW <= 96 && 2 * 96 + NP <= 256 && RB * (TW / 2) <= 256,
+                  "work split worked out for 6-row steps: one updateMatrices item and one vertical-sum column per lane");
     __shared__ __attribute__((aligned(16))) f2 A[RING][IW];    // (M0, M2)
     __shared__ __attribute__((aligned(16))) f2 B[RING][IW];    // (M3, M4)
     __shared__ __attribute__((aligned(16))) float C[RING][IW]; // M1
@@ -895,6 +905,13 @@ __global__ __launch_bounds__(256, FARN_STREAM_WPS) void k_farn_iter_stream(FarnP
     int gx[2];
     gx[0] = xin ? gxa : min(max(gxa, 0), w - 1);
     gx[1] = xin ? gxa + 1 : min(max(gxa + 1, 0), w - 1);
+    // column x0 - HALF + tx is even only where HALF is: an 8-byte aligned pair there, a 4-byte aligned one otherwise
+    auto ld_pair = [](const float *base, unsigned byte_off) {
+        if constexpr (HALF % 2 == 0)
+            return farn_ld2(base, byte_off);
+        else
+            return farn_ld2u(base, byte_off);
+    };
     auto load_flow = [&](int gy, f2 &dx, f2 &dy) {
         if (INIT) {
             if (init.zero) {
@@ -907,8 +924,8 @@ __global__ __launch_bounds__(256, FARN_STREAM_WPS) void k_farn_iter_stream(FarnP
             }
         } else if (xin) {
             const unsigned o = (unsigned)(gy * pitch + gx[0]) * 4u;
-            dx = farn_ld2(FXi, o);
-            dy = farn_ld2(FYi, o);
+            dx = ld_pair(FXi, o);
+            dy = ld_pair(FYi, o);
         } else {
             const unsigned o0 = (unsigned)(gy * pitch + gx[0]) * 4u, o1 = (unsigned)(gy * pitch + gx[1]) * 4u;
             dx = farn_f2(farn_ld1(FXi, o0), farn_ld1(FXi, o1));
@@ -926,7 +943,7 @@ __global__ __launch_bounds__(256, FARN_STREAM_WPS) void k_farn_iter_stream(FarnP
             const unsigned o = (unsigned)(gy * pitch + gx[0]) * 4u;
 #pragma unroll
             for (int p = 0; p < 5; ++p) {
-                const f2 t = farn_ld2(R0 + p * ps, o);
+                const f2 t = ld_pair(R0 + p * ps, o);
                 pr0[0][p] = t.x, pr0[1][p] = t.y;
             }
         } else {
@@ -978,35 +995,41 @@ __global__ __launch_bounds__(256, FARN_STREAM_WPS) void k_farn_iter_stream(FarnP
     const bool has_out = tid < RB * (TW / 2);
     const int hi = tid >> 5, hx = 2 * (tid & 31);
 
-    // the window's first 12 rows, then the loads of step 0's rows and the flows of step 1's
+    // the window's first WARM rows (12 at HALF 6) in NW passes of RB rows — the last pass is partial where RB does not
+    // divide WARM — then the loads of step 0's rows and the flows of step 1's
+    constexpr int NW = (WARM + RB - 1) / RB;
     f2 cdx = farn_f2(0.f, 0.f), cdy = cdx; // flow of the row whose loads are in flight
     f2 ndx = cdx, ndy = cdx;               // flow of the row after that
     if (has_item) {
-        f2 dx0, dy0, dx1, dy1;
-        load_flow(image_row(k1), dx0, dy0);
-        load_flow(image_row(RB + k1), dx1, dy1);
-        load_flow(image_row(2 * RB + k1), cdx, cdy);
-        issue_row(image_row(k1));
-        matrices_row(image_row(k1), dx0, dy0, k1);
-        issue_row(image_row(RB + k1));
-        matrices_row(image_row(RB + k1), dx1, dy1, RB + k1);
-        issue_row(image_row(2 * RB + k1));
-        load_flow(image_row(3 * RB + k1), ndx, ndy);
+        f2 wdx[NW], wdy[NW];
+#pragma unroll
+        for (int q = 0; q < NW; ++q)
+            if ((q + 1) * RB <= WARM || q * RB + k1 < WARM)
+                load_flow(image_row(q * RB + k1), wdx[q], wdy[q]);
+        load_flow(image_row(WARM + k1), cdx, cdy);
+#pragma unroll
+        for (int q = 0; q < NW; ++q)
+            if ((q + 1) * RB <= WARM || q * RB + k1 < WARM) { // ring rows WARM .. belong to step 0
+                issue_row(image_row(q * RB + k1));
+                matrices_row(image_row(q * RB + k1), wdx[q], wdy[q], q * RB + k1);
+            }
+        issue_row(image_row(WARM + k1));
+        load_flow(image_row(WARM + RB + k1), ndx, ndy);
     }
     const int n_steps = (yb - ya + RB - 1) / RB;
     int b0 = 0; // slot of the oldest row of the window = (RB * s) % RING
     for (int s = 0; s < n_steps; ++s) {
-        // rows 12 + 6 s .. 17 + 6 s enter the window: their loads were issued a step ago
+        // rows WARM + 6 s .. WARM + 5 + 6 s enter the window: their loads were issued a step ago
         if (has_item) {
-            int slot = b0 + 2 * RB + k1;
+            int slot = b0 + WARM + k1;
             slot -= slot >= RING ? RING : 0;
 #if FARN_STREAM_MASK & 1
-            matrices_row(image_row(2 * RB + RB * s + k1), cdx, cdy, slot);
+            matrices_row(image_row(WARM + RB * s + k1), cdx, cdy, slot);
             if (s + 1 < n_steps) { // the next step's loads fly while this step sums; the flows of the step after it, too
                 cdx = ndx, cdy = ndy;
-                issue_row(image_row(2 * RB + RB * (s + 1) + k1));
+                issue_row(image_row(WARM + RB * (s + 1) + k1));
                 if (s + 2 < n_steps)
-                    load_flow(image_row(2 * RB + RB * (s + 2) + k1), ndx, ndy);
+                    load_flow(image_row(WARM + RB * (s + 2) + k1), ndx, ndy);
             }
 #else
             A[slot][tx] = cdx, B[slot][tx] = cdy, C[slot][tx] = cdx.x;
@@ -1020,7 +1043,7 @@ __global__ __launch_bounds__(256, FARN_STREAM_WPS) void k_farn_iter_stream(FarnP
         b0 -= b0 >= RING ? RING : 0;
         continue;
 #endif
-        // vertical sums of the 6 output rows (window rows j = 0 .. 17 -> slots (b0 + j) % 18), this lane's column only:
+        // vertical sums of the 6 output rows (window rows j = 0 .. RING - 1 -> slots (b0 + j) % RING), this lane's column only:
         // the sums go where the 6 oldest rows were — nobody else touches this column in this phase
         if (vcol) {
             f2 v[RING];
@@ -1183,17 +1206,14 @@ void farn_launch_blur_h_resize(hipStream_t s, const float *tmpv, long long tmpv_
 
 void farn_launch_polyexp(hipStream_t s, const float *pyr, long long pyr_frame_stride, int n_frames,
                          const int *frame_slots, float *frame_R, long long frame_stride, FarnLevelGeom L,
-                         FarnPolyConsts pc, int rows) {
-    // rows: 16 = k_farn_polyexp_rows<16>, anything else = one image row per workgroup (the first form)
-    if (rows == 16) {
-        const dim3 grid((L.w + 245) / 246, (L.h + 15) / 16, n_frames);
-        hipLaunchKernelGGL(k_farn_polyexp_rows<16>, grid, dim3(256), 0, s, pyr, pyr_frame_stride, frame_slots, frame_R,
-                           frame_stride, L, pc);
-        return;
-    }
-    const dim3 grid((L.w + 245) / 246, L.h, n_frames);
-    hipLaunchKernelGGL(k_farn_polyexp, grid, dim3(256), 0, s, pyr, pyr_frame_stride, frame_slots, frame_R,
-                       frame_stride, L, pc);
+                         FarnPolyConsts pc, int rows, int poly_n) {
+    // rows: 16 = k_farn_polyexp_rows<16, N>, anything else = one image row per workgroup (the first form);
+    // poly_n: 5 or 7 (the engine refuses every other value), 256 - 2 * poly_n output columns per workgroup
+    const int cols = 256 - 2 * poly_n;
+    const dim3 grid((L.w + cols - 1) / cols, rows == 16 ? (L.h + 15) / 16 : L.h, n_frames);
+    auto *k = rows == 16 ? (poly_n == 7 ? k_farn_polyexp_rows<16, 7> : k_farn_polyexp_rows<16, 5>)
+                         : (poly_n == 7 ? k_farn_polyexp<7> : k_farn_polyexp<5>);
+    hipLaunchKernelGGL(k, grid, dim3(256), 0, s, pyr, pyr_frame_stride, frame_slots, frame_R, frame_stride, L, pc);
 }
 
 void farn_launch_init_flow(hipStream_t s, const FarnPairCtx &c, int cur_set, int prev_w, int prev_h, int prev_pitch,
@@ -1218,31 +1238,43 @@ void farn_launch_iteration(hipStream_t s, const FarnPairCtx &c, int flow_set, in
     hipLaunchKernelGGL(k_farn_iteration, grid, dim3(256), 0, s, c, flow_set, m_src, half, box_inv, do_matrices);
 }
 
-void farn_launch_iter_stream(hipStream_t s, const FarnPairCtx &c, int flow_in, int flow_out, float box_inv, float *merged,
-                             long long merged_stride) {
-    const int seg_rows = farn_stream_seg_rows(c.L.w, c.L.h, c.n_pairs);
+// One instantiation per on-chip window (farn_stream_has_half, farneback_plan.h); the engine asks for no other.
+template <bool INIT, bool PLANAR>
+static void farn_stream_launch(hipStream_t s, const FarnPairCtx &c, int half, int flow_in, int flow_out, float box_inv,
+                               float *merged, long long merged_stride, const FarnInit &in, const DfxPlanarOut &o) {
+    const int seg_rows = farn_stream_seg_rows(c.L.w, c.L.h, c.n_pairs, half);
     const dim3 grid((c.L.w + 63) / 64, (c.L.h + seg_rows - 1) / seg_rows, c.n_pairs);
-    hipLaunchKernelGGL((k_farn_iter_stream<6, false>), grid, dim3(256), 0, s, c, flow_in, flow_out, box_inv, seg_rows, merged,
-                       merged_stride, FarnInit{}, DfxPlanarOut{});
+    void (*k)(FarnPairCtx, int, int, float, int, float *, long long, FarnInit, DfxPlanarOut) = nullptr;
+    switch (half) {
+    case 3: k = k_farn_iter_stream<3, INIT, PLANAR>; break;
+    case 4: k = k_farn_iter_stream<4, INIT, PLANAR>; break;
+    case 5: k = k_farn_iter_stream<5, INIT, PLANAR>; break;
+    case 6: k = k_farn_iter_stream<6, INIT, PLANAR>; break;
+    case 7: k = k_farn_iter_stream<7, INIT, PLANAR>; break;
+    case 8: k = k_farn_iter_stream<8, INIT, PLANAR>; break;
+    case 9: k = k_farn_iter_stream<9, INIT, PLANAR>; break;
+    case 10: k = k_farn_iter_stream<10, INIT, PLANAR>; break;
+    default: std::abort(); // FarnebackEngine::create routes every other window to farn_launch_iteration
+    }
+    hipLaunchKernelGGL(k, grid, dim3(256), 0, s, c, flow_in, flow_out, box_inv, seg_rows, merged, merged_stride, in, o);
 }
 
-void farn_launch_iter_stream_planar(hipStream_t s, const FarnPairCtx &c, int flow_in, int flow_out, float box_inv,
+void farn_launch_iter_stream(hipStream_t s, const FarnPairCtx &c, int half, int flow_in, int flow_out, float box_inv,
+                             float *merged, long long merged_stride) {
+    farn_stream_launch<false, false>(s, c, half, flow_in, flow_out, box_inv, merged, merged_stride, FarnInit{}, DfxPlanarOut{});
+}
+
+void farn_launch_iter_stream_planar(hipStream_t s, const FarnPairCtx &c, int half, int flow_in, int flow_out, float box_inv,
                                     const DfxPlanarOut &o) {
-    const int seg_rows = farn_stream_seg_rows(c.L.w, c.L.h, c.n_pairs);
-    const dim3 grid((c.L.w + 63) / 64, (c.L.h + seg_rows - 1) / seg_rows, c.n_pairs);
-    hipLaunchKernelGGL((k_farn_iter_stream<6, false, true>), grid, dim3(256), 0, s, c, flow_in, flow_out, box_inv, seg_rows,
-                       (float *)nullptr, 0ll, FarnInit{}, o);
+    farn_stream_launch<false, true>(s, c, half, flow_in, flow_out, box_inv, nullptr, 0ll, FarnInit{}, o);
 }
 
-void farn_launch_iter_stream_init(hipStream_t s, const FarnPairCtx &c, int prev_set, int flow_out, float box_inv,
+void farn_launch_iter_stream_init(hipStream_t s, const FarnPairCtx &c, int half, int prev_set, int flow_out, float box_inv,
                                   float *merged, long long merged_stride, int prev_w, int prev_h, int prev_pitch, float ifx,
                                   float ify, float up, int zero) {
-    const int seg_rows = farn_stream_seg_rows(c.L.w, c.L.h, c.n_pairs);
-    const dim3 grid((c.L.w + 63) / 64, (c.L.h + seg_rows - 1) / seg_rows, c.n_pairs);
     FarnInit in;
     in.zero = zero, in.prev_w = prev_w, in.prev_h = prev_h, in.prev_pitch = prev_pitch, in.ifx = ifx, in.ify = ify, in.up = up;
-    hipLaunchKernelGGL((k_farn_iter_stream<6, true>), grid, dim3(256), 0, s, c, prev_set, flow_out, box_inv, seg_rows, merged,
-                       merged_stride, in, DfxPlanarOut{});
+    farn_stream_launch<true, false>(s, c, half, prev_set, flow_out, box_inv, merged, merged_stride, in, DfxPlanarOut{});
 }
 
 void farn_launch_merge(hipStream_t s, const FarnPairCtx &c, int flow_set, float *out, long long out_stride) {
