@@ -12,6 +12,8 @@ from .engine import (  # noqa: F401
     DfxError,
     DfxParams,
     DfxStats,
+    FARN_WINDOW_BOX,
+    FARN_WINDOW_GAUSSIAN,
     FlowEngine,
     algo_from_name,
     build_library,
@@ -24,6 +26,8 @@ __all__ = [
     "DfxError",
     "DfxParams",
     "DfxStats",
+    "FARN_WINDOW_BOX",
+    "FARN_WINDOW_GAUSSIAN",
     "FlowEngine",
     "algo_from_name",
     "build_library",

@@ -14,6 +14,7 @@
 
 #include "../../include/dfx.h"
 #include "dfx_device.h"
+#include "farneback_plan.h"
 
 // Automatic batch (dfx_params.max_batch = 0): as many pairs as 256 Mpx of level-0 pixels hold (129 at 1080p), at most
 // this many.  Small frames reach it: 2048 pairs of 224 x 224 are 103 Mpx — 0.4 of the 1080p batch — and a FlowBuffer
@@ -143,6 +144,19 @@ inline bool farn_gaussian_taps(int n, double sigma, std::vector<float> &half_out
     half_out.resize(half + 1);
     for (int j = 0; j <= half; ++j)
         half_out[j] = (float)k[half + j];
+    return true;
+}
+
+// The taps of the Gaussian update window (upstream's updateFlow_gaussianBlur): getGaussianKernel(winSize, sigma, CV_32F)
+// with sigma = (winSize / 2) * 0.3f — an integer division and a float product, widened to double — centre first.
+// winSize 1 gives sigma 0 and hence the fixed table {1}.  They depend on the parameters only, not on the frame size.
+inline bool farn_window_taps(int win_size, FarnWinTaps &out) {
+    const double sigma = (double)((float)(win_size / 2) * 0.3f);
+    std::vector<float> half;
+    out = FarnWinTaps();
+    if (win_size / 2 >= (int)(sizeof out.g / sizeof out.g[0]) || !farn_gaussian_taps(win_size, sigma, half))
+        return false;
+    std::copy(half.begin(), half.end(), out.g);
     return true;
 }
 

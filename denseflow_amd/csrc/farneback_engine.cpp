@@ -105,6 +105,8 @@ class FarnebackEngine final : public AlgoEngine {
     float *d_f32 = nullptr, *d_tmpv = nullptr, *d_pyr = nullptr;
     int skip_zero_weights = 1, polyexp_rows = 16; // frame-preparation forms, fixed when the engine is created
     bool m_on_chip = true;                        // the default iteration kernel (M recomputed, never in HBM)
+    bool gauss_window = false;                    // dfx_params.farn_window: Gaussian taps in place of the box filter
+    FarnWinTaps win_taps{};
 
     int B = 0;
     float *d_planes = nullptr;
@@ -142,7 +144,10 @@ int FarnebackEngine::create() {
     if (p.farn_poly_n != 5 && p.farn_poly_n != 7)
         return dfx_fail(c, DFX_ERR_UNSUPPORTED, "Farneback: polyN must be 5 or 7 (the two expansions upstream builds)");
     if (p.farn_flags != 0)
-        return dfx_fail(c, DFX_ERR_UNSUPPORTED, "Farneback: only flags = 0 (box-filter update, the reference's default)");
+        return dfx_fail(c, DFX_ERR_UNSUPPORTED,
+                        "Farneback: only flags = 0 (the Gaussian window is requested with farn_window, not with flags = 256)");
+    if (p.farn_window != DFX_FARN_WINDOW_BOX && p.farn_window != DFX_FARN_WINDOW_GAUSSIAN)
+        return dfx_fail(c, DFX_ERR_INVALID, "Farneback: farn_window must be DFX_FARN_WINDOW_BOX or DFX_FARN_WINDOW_GAUSSIAN");
     if (p.farn_win_size < 1 || !(p.farn_win_size & 1) || p.farn_win_size > 31)
         return dfx_fail(c, DFX_ERR_UNSUPPORTED, "Farneback: winSize must be odd and <= 31");
     if (p.farn_num_levels < 0 || p.farn_num_levels >= DFX_LVL_MAX || p.farn_num_iters < 1 ||
@@ -150,6 +155,10 @@ int FarnebackEngine::create() {
         return dfx_fail(c, DFX_ERR_INVALID, "invalid Farneback parameters");
 
     prepare_poly(p.farn_poly_n, p.farn_poly_sigma, &pc);
+    // the Gaussian update window's taps follow from the parameters alone: set_size leaves them alone
+    gauss_window = p.farn_window == DFX_FARN_WINDOW_GAUSSIAN;
+    if (gauss_window && !farn_window_taps(p.farn_win_size, win_taps))
+        return dfx_fail(c, DFX_ERR_INVALID, "Farneback: bad Gaussian window");
     // The default iteration kernel keeps M on chip: a pair slot is its two flow sets (4 planes, 33 MB at 1080p).  The
     // M-in-HBM kernels (a window the row-stream kernel is not built for: farn_stream_has_half; impl = 1;
     // DFX_VAR_FARN_M_IN_HBM) need the two M sets as well (14 planes).
@@ -304,6 +313,7 @@ int FarnebackEngine::run_pairs(int nb, const PairDesc *h_pairs, float *d_out, lo
     const int half = p.farn_win_size / 2;
     const float box_inv = 1.f / (float)((1 + 2 * half) * (1 + 2 * half));
     const float up = (float)(1. / p.farn_pyr_scale);
+    const FarnWinTaps *gauss = gauss_window ? &win_taps : nullptr; // nullptr: the box kernels, as before
     FarnPairCtx x;
     std::memset(&x, 0, sizeof x);
     x.frame_R = d_R;
@@ -332,12 +342,12 @@ int FarnebackEngine::run_pairs(int nb, const PairDesc *h_pairs, float *d_out, lo
                 const bool last = k == 0 && it == p.farn_num_iters - 1;
                 float *merged = last && !planar ? d_out : nullptr;
                 if (last && planar && it > 0)
-                    farn_launch_iter_stream_planar(c->stream, x, half, cur, cur ^ 1, box_inv, *planar);
+                    farn_launch_iter_stream_planar(c->stream, x, half, cur, cur ^ 1, box_inv, *planar, gauss);
                 else if (it == 0)
                     farn_launch_iter_stream_init(c->stream, x, half, cur, cur ^ 1, box_inv, merged, out_stride, P.w, P.h, P.pitch, ifx,
-                                                 ify, up, top ? 1 : 0);
+                                                 ify, up, top ? 1 : 0, gauss);
                 else
-                    farn_launch_iter_stream(c->stream, x, half, cur, cur ^ 1, box_inv, merged, out_stride);
+                    farn_launch_iter_stream(c->stream, x, half, cur, cur ^ 1, box_inv, merged, out_stride, gauss);
                 cur ^= 1;
             }
             HIPCHK(c, hipEventRecord(ev_it[k][1], c->stream));
@@ -365,7 +375,7 @@ int FarnebackEngine::run_pairs(int nb, const PairDesc *h_pairs, float *d_out, lo
         HIPCHK(c, hipEventRecord(ev_it[k][0], c->stream));
         for (int it = 0; it < p.farn_num_iters; ++it) {
             const int dm = it < p.farn_num_iters - 1;
-            farn_launch_iteration(c->stream, x, set, m_src, half, box_inv, dm, c->prm.impl);
+            farn_launch_iteration(c->stream, x, set, m_src, half, box_inv, dm, c->prm.impl, gauss);
             if (dm)
                 m_src ^= 1;
         }

@@ -13,6 +13,7 @@
 #include <hip/hip_runtime.h>
 
 #include "dfx_device.h"
+#include "farneback_plan.h"
 
 enum : int { FARN_PL_FX0 = 0, FARN_PL_FY0, FARN_PL_FX1, FARN_PL_FY1, FARN_PL_M0, FARN_PL_M1 = FARN_PL_M0 + 5,
              FARN_PL_COUNT = FARN_PL_M1 + 5 };
@@ -65,22 +66,24 @@ void farn_launch_init_flow(hipStream_t s, const FarnPairCtx &c, int cur_set, int
                            float ifx, float ify, float up, int zero);
 void farn_launch_update_matrices(hipStream_t s, const FarnPairCtx &c, int flow_set, int m_set);
 // boxFilter5 + updateFlow (+ updateMatrices) in one launch (B.8, B.9, B.7)
+// gauss (here and in the row-stream launchers below): nullptr = the box window; otherwise the taps of the Gaussian window
+// (dfx_params.farn_window), which take boxFilter5's place — the Gaussian kernels are launched and box_inv is not used
 void farn_launch_iteration(hipStream_t s, const FarnPairCtx &c, int flow_set, int m_src, int half, float box_inv,
-                           int do_matrices, int impl);
+                           int do_matrices, int impl, const FarnWinTaps *gauss);
 // the iteration with M recomputed where the box filter needs it (half = winSize / 2 with farn_stream_has_half(half),
 // farneback_plan.h: winSize 7 .. 21): reads flow set flow_in, writes flow set flow_out; a stream down 64-column strips
 // with a ring of 6 + 2 * half M rows in LDS (round 4's default)
 // merged != nullptr (the last iteration of level 0): the new flow goes to the caller's interleaved (u, v) rows instead
 void farn_launch_iter_stream(hipStream_t s, const FarnPairCtx &c, int half, int flow_in, int flow_out, float box_inv,
-                             float *merged, long long merged_stride);
+                             float *merged, long long merged_stride, const FarnWinTaps *gauss);
 // the first iteration of a level: its input flow is the coarser level's final flow (plane set prev_set, that level's
 // geometry) up-sampled on the fly, or zero at the coarsest level — no init launch
 void farn_launch_iter_stream_init(hipStream_t s, const FarnPairCtx &c, int half, int prev_set, int flow_out, float box_inv,
                                   float *merged, long long merged_stride, int prev_w, int prev_h, int prev_pitch, float ifx,
-                                  float ify, float up, int zero);
+                                  float ify, float up, int zero, const FarnWinTaps *gauss);
 void farn_launch_merge(hipStream_t s, const FarnPairCtx &c, int flow_set, float *out, long long out_stride);
 // Planar output (DfxPlanarOut, dfx_device.h).  The last iteration of level 0 in the row-stream form, when it is not also
 // the level's first: the new flow goes to the caller's u and v planes, bounded.
 void farn_launch_iter_stream_planar(hipStream_t s, const FarnPairCtx &c, int half, int flow_in, int flow_out, float box_inv,
-                                    const DfxPlanarOut &o);
+                                    const DfxPlanarOut &o, const FarnWinTaps *gauss);
 void farn_launch_merge_planar(hipStream_t s, const FarnPairCtx &c, int flow_set, const DfxPlanarOut &o);

@@ -437,8 +437,16 @@ __global__ __launch_bounds__(256) void k_farn_update_matrices(FarnPairCtx c, int
 // the last iteration, the next M (B.7) written to the other M set.
 // Tile: 64 x 16 output pixels per workgroup, 4 rows per thread; LDS: (64+2h) x (16+2h) input tile and
 // 16 x (64+2h) vertical sums, reused for the 5 planes.
-__global__ __launch_bounds__(256) void k_farn_iteration(FarnPairCtx c, int flow_set, int m_src, int half,
-                                                        float box_inv, int do_matrices) {
+//
+// GAUSS: the Gaussian update window (upstream's updateFlow_gaussianBlur in place of boxFilter5): the same two passes with
+// the centre multiplied by g[0] and every symmetric pair by g[j] — r = r + (a + b) * g[j], a rounded product and a rounded
+// sum, orc_farneback_gaussian_blur's order — and no 1 / area factor.  The taps are a kernel argument (uniform: scalar
+// registers); the loops over them are unrolled to FARN_HALF_MAX with a uniform exit so that every tap index is static.
+// The box kernel and the Gaussian kernel are two __global__ functions around this one body: a box launch runs no
+// instruction of the Gaussian form.
+template <bool GAUSS>
+__device__ __forceinline__ void farn_iteration_body(const FarnPairCtx &c, int flow_set, int m_src, int half, float box_inv,
+                                                    int do_matrices, const FarnWinTaps &wt) {
     constexpr int TW = 64, TH = 16, HM = FARN_HALF_MAX;
     __shared__ float tile[TH + 2 * HM][TW + 2 * HM];
     __shared__ float vs[TH][TW + 2 * HM];
@@ -460,9 +468,20 @@ __global__ __launch_bounds__(256) void k_farn_iteration(FarnPairCtx c, int flow_
         __syncthreads();
         for (int r = wave; r < TH; r += 4) {
             for (int tx = lane; tx < twp; tx += 64) {
-                float v = tile[r + half][tx];
-                for (int j = 1; j <= half; ++j)
-                    v = v + (tile[r + half - j][tx] + tile[r + half + j][tx]);
+                float v;
+                if constexpr (GAUSS) {
+                    v = tile[r + half][tx] * wt.g[0];
+#pragma unroll
+                    for (int j = 1; j <= HM; ++j) {
+                        if (j > half)
+                            break;
+                        v = v + (tile[r + half - j][tx] + tile[r + half + j][tx]) * wt.g[j];
+                    }
+                } else {
+                    v = tile[r + half][tx];
+                    for (int j = 1; j <= half; ++j)
+                        v = v + (tile[r + half - j][tx] + tile[r + half + j][tx]);
+                }
                 vs[r][tx] = v;
             }
         }
@@ -470,10 +489,21 @@ __global__ __launch_bounds__(256) void k_farn_iteration(FarnPairCtx c, int flow_
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int r = wave * 4 + i;
-            float res = vs[r][lane + half];
-            for (int k = 1; k <= half; ++k)
-                res = res + (vs[r][lane + half - k] + vs[r][lane + half + k]);
-            m[p][i] = res * box_inv;
+            if constexpr (GAUSS) {
+                float res = vs[r][lane + half] * wt.g[0];
+#pragma unroll
+                for (int k = 1; k <= HM; ++k) {
+                    if (k > half)
+                        break;
+                    res = res + (vs[r][lane + half - k] + vs[r][lane + half + k]) * wt.g[k];
+                }
+                m[p][i] = res;
+            } else {
+                float res = vs[r][lane + half];
+                for (int k = 1; k <= half; ++k)
+                    res = res + (vs[r][lane + half - k] + vs[r][lane + half + k]);
+                m[p][i] = res * box_inv;
+            }
         }
         __syncthreads();
     }
@@ -505,6 +535,15 @@ __global__ __launch_bounds__(256) void k_farn_iteration(FarnPairCtx c, int flow_
                 farn_plane(c, b, (m_src ? FARN_PL_M0 : FARN_PL_M1) + p)[o] = M[p];
         }
     }
+}
+
+__global__ __launch_bounds__(256) void k_farn_iteration(FarnPairCtx c, int flow_set, int m_src, int half,
+                                                        float box_inv, int do_matrices) {
+    farn_iteration_body<false>(c, flow_set, m_src, half, box_inv, do_matrices, FarnWinTaps{});
+}
+__global__ __launch_bounds__(256) void k_farn_iteration_gauss(FarnPairCtx c, int flow_set, int m_src, int half,
+                                                              int do_matrices, FarnWinTaps wt) {
+    farn_iteration_body<true>(c, flow_set, m_src, half, 0.f, do_matrices, wt);
 }
 
 // The same iteration for a compile-time box half-width, restructured around LDS traffic and latency:
@@ -870,10 +909,16 @@ struct FarnInit {
 // instantiation is compiled for three waves per SIMD, and so are the PLANAR ones above HALF 6, whose vertical-sum window
 // (RING float2 registers) would spill at 128 registers; the others for four (the resource table in DESIGN.md).
 constexpr int farn_stream_wps(int half, bool planar) { return (half <= 6 || (!planar && half <= 9)) ? FARN_STREAM_WPS : 3; }
-template <int HALF, bool INIT, bool PLANAR = false>
-__global__ __launch_bounds__(256, farn_stream_wps(HALF, PLANAR)) void k_farn_iter_stream(FarnPairCtx c, int flow_in, int flow_out, float box_inv,
-                                                             int seg_rows, float *merged, long long merged_stride,
-                                                             FarnInit init, DfxPlanarOut po) {
+// GAUSS: the Gaussian update window (dfx_params.farn_window): both passes multiply the centre by g[0] and every symmetric
+// pair by g[j] — one v_pk_mul_f32 per pair on the float2 lanes, the tap a scalar register — in
+// orc_farneback_gaussian_blur's order (r = r + (a + b) * g[j], nothing contracted), and there is no 1 / area factor.  The
+// ring, the warm-up passes, the work split and the segments are the box form's.  The body is shared; the box kernels
+// (k_farn_iter_stream) and the Gaussian kernels (k_farn_gauss_stream) are separate __global__ functions, so the box
+// kernels stay the code they were.
+template <int HALF, bool INIT, bool PLANAR, bool GAUSS>
+__device__ __forceinline__ void farn_stream_body(const FarnPairCtx &c, int flow_in, int flow_out, float box_inv, int seg_rows,
+                                                 float *merged, long long merged_stride, const FarnInit &init,
+                                                 const DfxPlanarOut &po, const FarnWinTaps &wt) {
     // WARM: rows of the window above its first output row and below its last; NP: column pairs per row (38 at HALF 6)
     constexpr int TW = 64, IW = TW + 2 * HALF, RB = 6, WARM = 2 * HALF, RING = RB + WARM, NP = IW / 2;
     static_assert(HALF >= 3 && HALF <= 10 && RB * NP <= 256 && IW <= 96 && 2 * 96 + NP <= 256 && RB * (TW / 2) <= 256,
@@ -1055,10 +1100,18 @@ __global__ __launch_bounds__(256, farn_stream_wps(HALF, PLANAR)) void k_farn_ite
             }
 #pragma unroll
             for (int i = 0; i < RB; ++i) {
-                f2 acc = v[i + HALF];
+                f2 acc;
+                if constexpr (GAUSS) {
+                    acc = v[i + HALF] * wt.g[0];
 #pragma unroll
-                for (int j = 1; j <= HALF; ++j)
-                    acc = acc + (v[i + HALF - j] + v[i + HALF + j]);
+                    for (int j = 1; j <= HALF; ++j)
+                        acc = acc + (v[i + HALF - j] + v[i + HALF + j]) * wt.g[j];
+                } else {
+                    acc = v[i + HALF];
+#pragma unroll
+                    for (int j = 1; j <= HALF; ++j)
+                        acc = acc + (v[i + HALF - j] + v[i + HALF + j]);
+                }
                 int slot = b0 + i;
                 slot -= slot >= RING ? RING : 0;
                 vcol[slot * vstride] = acc;
@@ -1083,11 +1136,19 @@ __global__ __launch_bounds__(256, farn_stream_wps(HALF, PLANAR)) void k_farn_ite
                 }
 #pragma unroll
                 for (int i = 0; i < 2; ++i) {
-                    f2 acc = v[i + HALF];
+                    if constexpr (GAUSS) {
+                        f2 acc = v[i + HALF] * wt.g[0];
 #pragma unroll
-                    for (int kk = 1; kk <= HALF; ++kk)
-                        acc = acc + (v[i + HALF - kk] + v[i + HALF + kk]);
-                    (q ? s34 : s02)[i] = acc * box_inv;
+                        for (int kk = 1; kk <= HALF; ++kk)
+                            acc = acc + (v[i + HALF - kk] + v[i + HALF + kk]) * wt.g[kk];
+                        (q ? s34 : s02)[i] = acc;
+                    } else {
+                        f2 acc = v[i + HALF];
+#pragma unroll
+                        for (int kk = 1; kk <= HALF; ++kk)
+                            acc = acc + (v[i + HALF - kk] + v[i + HALF + kk]);
+                        (q ? s34 : s02)[i] = acc * box_inv;
+                    }
                 }
             }
             {
@@ -1100,11 +1161,19 @@ __global__ __launch_bounds__(256, farn_stream_wps(HALF, PLANAR)) void k_farn_ite
                 }
 #pragma unroll
                 for (int i = 0; i < 2; ++i) {
-                    float acc = v[i + HALF];
+                    if constexpr (GAUSS) {
+                        float acc = v[i + HALF] * wt.g[0];
 #pragma unroll
-                    for (int kk = 1; kk <= HALF; ++kk)
-                        acc = acc + (v[i + HALF - kk] + v[i + HALF + kk]);
-                    s1[i] = acc * box_inv;
+                        for (int kk = 1; kk <= HALF; ++kk)
+                            acc = acc + (v[i + HALF - kk] + v[i + HALF + kk]) * wt.g[kk];
+                        s1[i] = acc;
+                    } else {
+                        float acc = v[i + HALF];
+#pragma unroll
+                        for (int kk = 1; kk <= HALF; ++kk)
+                            acc = acc + (v[i + HALF - kk] + v[i + HALF + kk]);
+                        s1[i] = acc * box_inv;
+                    }
                 }
             }
             float fxo[2], fyo[2];
@@ -1139,6 +1208,22 @@ __global__ __launch_bounds__(256, farn_stream_wps(HALF, PLANAR)) void k_farn_ite
         b0 += RB;
         b0 -= b0 >= RING ? RING : 0;
     }
+}
+
+template <int HALF, bool INIT, bool PLANAR = false>
+__global__ __launch_bounds__(256, farn_stream_wps(HALF, PLANAR)) void k_farn_iter_stream(FarnPairCtx c, int flow_in, int flow_out, float box_inv,
+                                                             int seg_rows, float *merged, long long merged_stride,
+                                                             FarnInit init, DfxPlanarOut po) {
+    farn_stream_body<HALF, INIT, PLANAR, false>(c, flow_in, flow_out, box_inv, seg_rows, merged, merged_stride, init, po, FarnWinTaps{});
+}
+// Waves per SIMD of the Gaussian instantiations, from the registers the compiler gives them (the resource table in
+// DESIGN.md): the box form's.
+constexpr int farn_gauss_wps(int half, bool planar) { return farn_stream_wps(half, planar); }
+template <int HALF, bool INIT, bool PLANAR = false>
+__global__ __launch_bounds__(256, farn_gauss_wps(HALF, PLANAR)) void k_farn_gauss_stream(FarnPairCtx c, int flow_in, int flow_out, int seg_rows,
+                                                              float *merged, long long merged_stride, FarnInit init,
+                                                              DfxPlanarOut po, FarnWinTaps wt) {
+    farn_stream_body<HALF, INIT, PLANAR, true>(c, flow_in, flow_out, 0.f, seg_rows, merged, merged_stride, init, po, wt);
 }
 
 __global__ __launch_bounds__(256) void k_farn_merge(FarnPairCtx c, int flow_set, float *out, long long out_stride) {
@@ -1228,7 +1313,12 @@ void farn_launch_update_matrices(hipStream_t s, const FarnPairCtx &c, int flow_s
 }
 
 void farn_launch_iteration(hipStream_t s, const FarnPairCtx &c, int flow_set, int m_src, int half, float box_inv,
-                           int do_matrices, int impl) {
+                           int do_matrices, int impl, const FarnWinTaps *gauss) {
+    if (gauss) { // every window and impl: k_farn_iteration_t<6> is the box filter only
+        const dim3 grid((c.L.w + 63) / 64, (c.L.h + 15) / 16, c.n_pairs);
+        hipLaunchKernelGGL(k_farn_iteration_gauss, grid, dim3(256), 0, s, c, flow_set, m_src, half, do_matrices, *gauss);
+        return;
+    }
     if (impl == 0 && half == 6) { // winSize 13, the reference's value: the tuned instantiation
         const dim3 grid((c.L.w + 63) / 64, (c.L.h + 31) / 32, c.n_pairs);
         hipLaunchKernelGGL(k_farn_iteration_t<6>, grid, dim3(256), 0, s, c, flow_set, m_src, box_inv, do_matrices);
@@ -1241,9 +1331,26 @@ void farn_launch_iteration(hipStream_t s, const FarnPairCtx &c, int flow_set, in
 // One instantiation per on-chip window (farn_stream_has_half, farneback_plan.h); the engine asks for no other.
 template <bool INIT, bool PLANAR>
 static void farn_stream_launch(hipStream_t s, const FarnPairCtx &c, int half, int flow_in, int flow_out, float box_inv,
-                               float *merged, long long merged_stride, const FarnInit &in, const DfxPlanarOut &o) {
+                               float *merged, long long merged_stride, const FarnInit &in, const DfxPlanarOut &o,
+                               const FarnWinTaps *gauss) {
     const int seg_rows = farn_stream_seg_rows(c.L.w, c.L.h, c.n_pairs, half);
     const dim3 grid((c.L.w + 63) / 64, (c.L.h + seg_rows - 1) / seg_rows, c.n_pairs);
+    if (gauss) {
+        void (*g)(FarnPairCtx, int, int, int, float *, long long, FarnInit, DfxPlanarOut, FarnWinTaps) = nullptr;
+        switch (half) {
+        case 3: g = k_farn_gauss_stream<3, INIT, PLANAR>; break;
+        case 4: g = k_farn_gauss_stream<4, INIT, PLANAR>; break;
+        case 5: g = k_farn_gauss_stream<5, INIT, PLANAR>; break;
+        case 6: g = k_farn_gauss_stream<6, INIT, PLANAR>; break;
+        case 7: g = k_farn_gauss_stream<7, INIT, PLANAR>; break;
+        case 8: g = k_farn_gauss_stream<8, INIT, PLANAR>; break;
+        case 9: g = k_farn_gauss_stream<9, INIT, PLANAR>; break;
+        case 10: g = k_farn_gauss_stream<10, INIT, PLANAR>; break;
+        default: std::abort();
+        }
+        hipLaunchKernelGGL(g, grid, dim3(256), 0, s, c, flow_in, flow_out, seg_rows, merged, merged_stride, in, o, *gauss);
+        return;
+    }
     void (*k)(FarnPairCtx, int, int, float, int, float *, long long, FarnInit, DfxPlanarOut) = nullptr;
     switch (half) {
     case 3: k = k_farn_iter_stream<3, INIT, PLANAR>; break;
@@ -1260,21 +1367,21 @@ static void farn_stream_launch(hipStream_t s, const FarnPairCtx &c, int half, in
 }
 
 void farn_launch_iter_stream(hipStream_t s, const FarnPairCtx &c, int half, int flow_in, int flow_out, float box_inv,
-                             float *merged, long long merged_stride) {
-    farn_stream_launch<false, false>(s, c, half, flow_in, flow_out, box_inv, merged, merged_stride, FarnInit{}, DfxPlanarOut{});
+                             float *merged, long long merged_stride, const FarnWinTaps *gauss) {
+    farn_stream_launch<false, false>(s, c, half, flow_in, flow_out, box_inv, merged, merged_stride, FarnInit{}, DfxPlanarOut{}, gauss);
 }
 
 void farn_launch_iter_stream_planar(hipStream_t s, const FarnPairCtx &c, int half, int flow_in, int flow_out, float box_inv,
-                                    const DfxPlanarOut &o) {
-    farn_stream_launch<false, true>(s, c, half, flow_in, flow_out, box_inv, nullptr, 0ll, FarnInit{}, o);
+                                    const DfxPlanarOut &o, const FarnWinTaps *gauss) {
+    farn_stream_launch<false, true>(s, c, half, flow_in, flow_out, box_inv, nullptr, 0ll, FarnInit{}, o, gauss);
 }
 
 void farn_launch_iter_stream_init(hipStream_t s, const FarnPairCtx &c, int half, int prev_set, int flow_out, float box_inv,
                                   float *merged, long long merged_stride, int prev_w, int prev_h, int prev_pitch, float ifx,
-                                  float ify, float up, int zero) {
+                                  float ify, float up, int zero, const FarnWinTaps *gauss) {
     FarnInit in;
     in.zero = zero, in.prev_w = prev_w, in.prev_h = prev_h, in.prev_pitch = prev_pitch, in.ifx = ifx, in.ify = ify, in.up = up;
-    farn_stream_launch<true, false>(s, c, half, prev_set, flow_out, box_inv, merged, merged_stride, in, DfxPlanarOut{});
+    farn_stream_launch<true, false>(s, c, half, prev_set, flow_out, box_inv, merged, merged_stride, in, DfxPlanarOut{}, gauss);
 }
 
 void farn_launch_merge(hipStream_t s, const FarnPairCtx &c, int flow_set, float *out, long long out_stride) {

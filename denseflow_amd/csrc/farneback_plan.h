@@ -18,6 +18,13 @@ constexpr int kFarnStreamSlots = 256 * 4; // workgroups the machine holds at onc
 constexpr int kFarnStreamHalfMin = 3, kFarnStreamHalfMax = 10;
 inline bool farn_stream_has_half(int half) { return half >= kFarnStreamHalfMin && half <= kFarnStreamHalfMax; }
 
+// The Gaussian update window (dfx_params.farn_window = DFX_FARN_WINDOW_GAUSSIAN): the non-negative half of
+// getGaussianKernel(winSize, (winSize / 2) * 0.3f), g[0] the centre (farn_window_taps, engine_plan.h).  Handed to the
+// iteration kernels by value: the taps are uniform and live in scalar registers.  16 = half-widths up to 15 (winSize 31).
+struct FarnWinTaps {
+    float g[16];
+};
+
 // The shortest segment worth its warm-up: a segment recomputes the 2 * half rows above and below it (its window's
 // first rows, and the rows its last outputs need), so the floor is four times that, in whole steps — 48 rows at half 6.
 inline int farn_stream_min_seg_rows(int half) {

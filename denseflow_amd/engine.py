@@ -50,6 +50,7 @@ class DfxParams(C.Structure):
         ("farn_poly_n", C.c_int),
         ("farn_poly_sigma", C.c_double),
         ("farn_flags", C.c_int),
+        ("farn_window", C.c_int),
         ("brox_alpha", C.c_float),
         ("brox_gamma", C.c_float),
         ("brox_scale_factor", C.c_float),
@@ -65,6 +66,10 @@ class DfxParams(C.Structure):
         ("blocking_sync", C.c_int),
     ]
 
+
+# dfx_params.farn_window (include/dfx.h): FlowEngine(..., "farn", farn_window=FARN_WINDOW_GAUSSIAN) is how upstream's
+# OPTFLOW_FARNEBACK_GAUSSIAN is requested; farn_flags stays refused unless 0
+FARN_WINDOW_BOX, FARN_WINDOW_GAUSSIAN = 0, 1
 
 # dfx_params.variant bits (include/dfx.h): cross-check / measurement forms of the tuned kernels, all bit-identical
 VAR_TVL1_CLASSIC_GEOM, VAR_TVL1_WARP_IN_STEP = 0x01, 0x02

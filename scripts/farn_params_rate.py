@@ -5,6 +5,7 @@ call per case the cases are timed in turn, ROUNDS times over, so that a drift of
 
     python scripts/farn_params_rate.py --cases defaults,win15,win15_hbm,win21,win21_hbm,poly7 --out rates.json
     DFX_LIBRARY=/path/to/another/libdfx.so python scripts/farn_params_rate.py --cases defaults   # A/B of two builds
+    python scripts/farn_params_rate.py --cases win15,gauss15,gauss15_hbm        # the Gaussian update window (farn_window)
 
 Prints one line per case and round and a JSON summary (min / median / max pairs/s per case)."""
 import argparse
@@ -33,6 +34,11 @@ CASES = {
     "win7_hbm": dict(farn_win_size=7, variant=E.VAR_FARN_M_IN_HBM),
     "win31": dict(farn_win_size=31),
 }
+# the Gaussian update window (dfx_params.farn_window), on chip and with M in HBM: gauss7, gauss7_hbm, gauss13, ...
+G = getattr(E, "FARN_WINDOW_GAUSSIAN", 1)
+for _w in (7, 13, 15, 21, 31):
+    CASES[f"gauss{_w}"] = dict(farn_win_size=_w, farn_window=G)
+    CASES[f"gauss{_w}_hbm"] = dict(farn_win_size=_w, farn_window=G, variant=E.VAR_FARN_M_IN_HBM)
 
 
 def main():

@@ -6,12 +6,14 @@ This environment has no OpenCV, so the flow oracles are "parity
 closes the gap the moment such a machine is reachable: it evaluates the very calls the reference makes
 (/root/reference/src/denseflow_gpu.cpp:299-303, :327-334) on the committed synthetic seeds and writes
 
-    tests/golden/opencv_tvl1.npz   opencv_farn.npz   opencv_brox.npz   [opencv_cpu_tvl1.npz]
+    tests/golden/opencv_tvl1.npz   opencv_farn.npz   opencv_farn_gaussian.npz   opencv_brox.npz   [opencv_cpu_tvl1.npz]
 
 each holding, per case, the two uint8 frames and the CV_32FC2 flow OpenCV returned, plus cv2.getBuildInformation().
 tests/test_opencv_pin.py picks the files up when present: the CPU oracle (-m "not gpu") and the HIP path (-m gpu)
 must then agree with OpenCV within BASELINE.json's 1e-3 max-abs (TVL1, Farneback) — and the Brox oracle, which today
-DEFINES its algorithm, gets its first external check.  Nothing here imports the product or the oracle.
+DEFINES its algorithm, gets its first external check.  opencv_farn_gaussian.npz is the Gaussian update window
+(dfx_params.farn_window, restated from memory and rated MED): winSize 15 with OPTFLOW_FARNEBACK_GAUSSIAN, picked up by
+tests/test_opencv_pin_farn_gaussian.py.  Nothing here imports the product or the oracle.
 
     python scripts/pin_against_opencv.py [--out tests/golden] [--testdata $OPENCV_TEST_DATA_PATH]
 With --testdata the upstream fixtures SURVEY.md §4 names are added as cases: cv/optflow/RubberWhale1.png / 2.png
@@ -61,6 +63,10 @@ def main():
     algos = {
         "tvl1": lambda a, b: cv2.cuda_OpticalFlowDual_TVL1.create().calc(up(a), up(b), None).download(),
         "farn": lambda a, b: cv2.cuda_FarnebackOpticalFlow.create().calc(up(a), up(b), None).download(),
+        # the Gaussian update window at a larger winSize, as OpenCV's documentation recommends it:
+        # create(numLevels, pyrScale, fastPyramids, winSize, numIters, polyN, polySigma, flags)
+        "farn_gaussian": lambda a, b: cv2.cuda_FarnebackOpticalFlow.create(
+            5, 0.5, False, 15, 10, 5, 1.1, cv2.OPTFLOW_FARNEBACK_GAUSSIAN).calc(up(a), up(b), None).download(),
         # src/denseflow_gpu.cpp:303, :332-334: create(0.197f, 50.0f, 0.8f, 10, 77, 10) on frames scaled by 1/255
         "brox": lambda a, b: cv2.cuda_BroxOpticalFlow.create(0.197, 50.0, 0.8, 10, 77, 10).calc(
             up(a.astype(np.float32) * np.float32(1.0 / 255.0)), up(b.astype(np.float32) * np.float32(1.0 / 255.0)),
