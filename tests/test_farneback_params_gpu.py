@@ -233,3 +233,151 @@ def test_defaults_are_still_the_oracles_bits(dfx, oracle):
     with dfx.FlowEngine(w, h, "farn") as eng:
         out = eng.calc(f0, f1)
     assert np.array_equal(out, oracle.farneback_calc(f0, f1))
+
+
+# ------------------------------------------------------------------------------------------------ pyrScale
+#
+# farn_pyr_scale away from 0.5: the pyramid geometry (level count and sizes, pre-blur widths, the run-time resize factors and
+# the 1 / pyrScale flow gain of the INIT form) follows the handle's value.  (pyrScale, numLevels, w, h, seed, levels expected
+# from farn_plan's rule: crop while W * scale < 32 || H * scale < 32).  300 = 4 strips of 64 + 44 columns = one
+# polynomial-expansion workgroup of 242 + 58 columns.  0.9 with 15 levels fills all DFX_LVL_MAX = 16 levels (pre-blur sigma
+# 0.056: the kernel size clamps to 3, taps near {0, 1, 0}); 0.3 gives a pre-blur half width of 3 at level 1.
+#
+# Frames are 8 clip frames apart (12 px of motion per pair): on consecutive frames the coarse levels only refine what
+# level 0 finds anyway, and the oracle's flow moves by 1e-5 .. 7e-4 px with pyrScale — below the 1e-3 px this file
+# requires of every case before it touches the engine.  At this spacing it moves by 0.1 .. 20 px.
+PYR_DT = 8
+PYR_DISCRIMINATION = 1e-3
+PYR_CASES = {1: (0.8, 5, 300, 200, 6), 2: (0.3, 5, 300, 200, 6), 3: (0.9, 15, 300, 200, 6), 4: (0.75, 8, 129, 97, 5)}
+PYR_LEVELS = {1: 6, 2: 2, 3: 16}  # case 4: from _plan_levels
+
+
+def _plan_levels(w, h, pyr_scale, num_levels):
+    """farn_plan (denseflow_amd/csrc/engine_plan.h): levels 0 .. cropped."""
+    scale, cropped = 1.0, 0
+    while cropped < num_levels:
+        scale *= pyr_scale
+        if w * scale < 32 or h * scale < 32:
+            break
+        cropped += 1
+    return cropped + 1
+
+
+def _pyr_frames(w, h, seed, n=4):
+    key = ("pyr", w, h, seed, n)
+    if key not in _clips:
+        clip = SynthClip(w, h, seed)
+        _clips[key] = [clip.frame(PYR_DT * i) for i in range(n)]
+    return _clips[key]
+
+
+def _pyr_ref(oracle, case, **kw):
+    """The oracle's flows of a pyrScale case after the check, on oracle output only, that pyrScale moves every one of them by
+    more than 1e-3 px away from the flow the same parameters give at the default pyrScale and numLevels."""
+    ps, nl, w, h, seed = PYR_CASES[case]
+    frames = _pyr_frames(w, h, seed)
+    ref = _ref(oracle, ("pyr", w, h, seed), frames, pyr_scale=ps, num_levels=nl, **kw)
+    base = _ref(oracle, ("pyr", w, h, seed), frames, **kw)
+    diffs = [float(np.max(np.abs(a - b))) for a, b in zip(ref, base)]
+    print(f"farn pyrScale case {case} {kw}: oracle against the default pyramid, max-abs per pair {diffs}")
+    assert all(np.isfinite(a).all() for a in ref)
+    assert min(diffs) > PYR_DISCRIMINATION, (case, kw, diffs)
+    return frames, ref
+
+
+def _pyr_kw(case, win, iters):
+    ps, nl = PYR_CASES[case][:2]
+    return dict(max_batch=2, farn_pyr_scale=ps, farn_num_levels=nl, farn_win_size=win, farn_num_iters=iters)
+
+
+# win 13: the tuned instantiation; 15: a row-stream instantiation; 25: the generic kernel; iters 1: INIT is a level's only launch
+PYR_RUNS = [(c, win, 3) for c in (1, 2, 3, 4) for win in (13, 15)] + [(1, 25, 3), (1, 13, 1), (1, 15, 1)]
+
+
+@pytest.mark.parametrize("case,win,iters", PYR_RUNS)
+def test_pyr_scale_every_form_matches_the_oracle(dfx, oracle, case, win, iters):
+    from denseflow_amd import engine as E
+
+    ps, nl, w, h, _ = PYR_CASES[case]
+    frames, ref = _pyr_ref(oracle, case, win_size=win, num_iters=iters)
+    levels = _plan_levels(w, h, ps, nl)
+    assert levels == PYR_LEVELS.get(case, levels)
+    kw = _pyr_kw(case, win, iters)
+    for knobs in (dict(), dict(variant=E.VAR_FARN_M_IN_HBM), dict(impl=1)):
+        with dfx.FlowEngine(w, h, "farn", **kw, **knobs) as eng:
+            out = eng.calc_optflows(frames, 1)  # 4 frames, 3 pairs, batches of 2
+            st = eng.stats()
+        assert st.levels == levels, (knobs, st.levels, levels)
+        _same(out, ref, f"pyrScale {ps}, {nl} levels, winSize {win}, {iters} iterations, {knobs}")
+
+
+@pytest.mark.parametrize("win", [13, 15, 25])
+def test_pyr_scale_with_the_gaussian_window(dfx, oracle, win):
+    from denseflow_amd import engine as E
+    from tests import farneback_window_ref as WR
+
+    ps, nl, w, h, seed = PYR_CASES[1]
+    frames = _pyr_frames(w, h, seed)
+
+    def gauss(**kw):
+        key = (("pyr-gauss", w, h, seed), tuple(sorted(kw.items())))
+        if key not in _refs:
+            out = [WR.farneback_flow(oracle, frames[i], frames[i + 1], _params(oracle, **kw), "gaussian") for i in range(3)]
+            for f in out:
+                f.setflags(write=False)
+            _refs[key] = out
+        return _refs[key]
+
+    ref, base = gauss(pyr_scale=ps, num_levels=nl, win_size=win, num_iters=3), gauss(win_size=win, num_iters=3)
+    diffs = [float(np.max(np.abs(a - b))) for a, b in zip(ref, base)]
+    print(f"farn pyrScale case 1, Gaussian winSize {win}: reference against the default pyramid, max-abs per pair {diffs}")
+    assert min(diffs) > PYR_DISCRIMINATION, diffs
+    kw = dict(farn_window=1, **_pyr_kw(1, win, 3))
+    for knobs in (dict(), dict(variant=E.VAR_FARN_M_IN_HBM), dict(impl=1)):
+        with dfx.FlowEngine(w, h, "farn", **kw, **knobs) as eng:
+            _same(eng.calc_optflows(frames, 1), ref, f"Gaussian window, pyrScale {ps}, winSize {win}, {knobs}")
+
+
+def test_pyr_scale_planar_output_is_the_interleaved_output(dfx, oracle):
+    bound = 20.0
+    w, h = PYR_CASES[1][2:4]
+    frames, ref = _pyr_ref(oracle, 1, win_size=13, num_iters=3)
+    with dfx.FlowEngine(w, h, "farn", **_pyr_kw(1, 13, 3)) as eng:
+        inter = eng.calc_optflows(frames, 1)
+        got = eng.calc_optflows_planar(frames, 1, bound=bound)
+    _same(inter, ref, "interleaved against the oracle")
+    want = np.clip(np.stack(inter).transpose(0, 3, 1, 2), -bound, bound).astype(np.float32) / np.float32(bound)
+    assert got.shape == want.shape and got.dtype == np.float32
+    assert np.array_equal(got.view(np.uint32), np.ascontiguousarray(want).view(np.uint32))
+
+
+def test_pyr_scale_set_size_gives_the_bits_of_a_fresh_handle(dfx, oracle):
+    """300x200 -> 97x61 -> 300x200 on one handle at pyrScale 0.8: re-planning follows the handle's pyrScale, every stop
+    computes a fresh handle's (and the oracle's) bits, and the handle holds after the last stop what it held after the first."""
+    kw = dict(max_batch=2, farn_pyr_scale=0.8)
+    sizes = [(300, 200), (97, 61), (300, 200)]
+    seeds = {(300, 200): 6, (97, 61): 9}
+    fresh = {}
+    for (w, h), seed in seeds.items():
+        frames = _pyr_frames(w, h, seed)
+        ref, base = _ref(oracle, ("pyr", w, h, seed), frames, pyr_scale=0.8), _ref(oracle, ("pyr", w, h, seed), frames)
+        assert min(float(np.max(np.abs(a - b))) for a, b in zip(ref, base)) > PYR_DISCRIMINATION
+        with dfx.FlowEngine(w, h, "farn", **kw) as eng:
+            fresh[(w, h)] = eng.calc_optflows(frames, 1)
+            assert eng.stats().levels == _plan_levels(w, h, 0.8, 5)
+        _same(fresh[(w, h)], ref, f"fresh handle at {w}x{h}")
+    held = []
+    with dfx.FlowEngine(*sizes[0], "farn", **kw) as eng:
+        for w, h in sizes:
+            eng.set_size(w, h)
+            _same(eng.calc_optflows(_pyr_frames(w, h, seeds[(w, h)]), 1), fresh[(w, h)], f"after set_size({w}, {h})")
+            assert eng.stats().levels == _plan_levels(w, h, 0.8, 5)
+            held.append(eng.device_bytes())
+    assert held[2] == held[0], held
+
+
+@pytest.mark.parametrize("kw", [dict(farn_pyr_scale=0.0), dict(farn_pyr_scale=1.0), dict(farn_num_levels=16)])
+def test_refused_pyramid_parameters(dfx, kw):
+    with pytest.raises(dfx.DfxError) as e:
+        dfx.FlowEngine(300, 200, "farn", **kw)
+    assert e.value.status == 1  # DFX_ERR_INVALID
