@@ -31,6 +31,7 @@ void default_params(dfx_params *p) {
     p->tvl1_epsilon = 0.01;
     p->tvl1_iterations = 300;
     p->tvl1_scale_step = 0.8;
+    p->tvl1_gamma = 0.0;
     // cv::cuda::FarnebackOpticalFlow::create() defaults
     p->farn_num_levels = 5;
     p->farn_pyr_scale = 0.5;

@@ -5,7 +5,7 @@
 //
 //   frame slot f  : three pyramids  I, Ix, Iy     (Ix/Iy = centred gradient)
 //                   level s lives at element offset lvl_off[s] of the slot, pitch lvl_pitch[s]
-//   pair slot b   : NPLANES work planes sized for level 0, reused by every level with the
+//   pair slot b   : n_planes work planes (16; 22 with tvl1_gamma) sized for level 0, reused by every level with the
 //                   level's own pitch:  u[2 sets][2], p[2 sets][4], I1wx, I1wy, grad, rho_c
 //                   (ping-pong sets: a fused U+dual step reads one set and writes the other)
 //
@@ -21,8 +21,16 @@ enum : int {
     PL_P11_0, PL_P12_0, PL_P21_0, PL_P22_0,                // p set 0
     PL_P11_1, PL_P12_1, PL_P21_1, PL_P22_1,                // p set 1
     PL_I1WX, PL_I1WY, PL_GRAD, PL_RHOC,
-    PL_COUNT
+    PL_COUNT,
+    // dfx_params.tvl1_gamma != 0: the illumination channel u3 and its dual (p31, p32) BEHIND the 16 planes above, whose
+    // indices stay what they are; a pair slot then has PL_COUNT_GAMMA planes (Tvl1LevelCtx::n_planes)
+    PL_U3_0 = PL_COUNT, PL_U3_1,                           // u3 sets 0/1
+    PL_P31_0, PL_P32_0, PL_P31_1, PL_P32_1,                // (p31, p32) sets 0/1
+    PL_COUNT_GAMMA
 };
+// plane of channel ch = 0, 1, 2 (u1, u2, u3) in ping-pong set S: u, and the first of its two dual planes (the second follows it)
+DFX_HD int tvl1_pl_u(int ch, int S) { return ch < 2 ? PL_U1_0 + 2 * S + ch : PL_U3_0 + S; }
+DFX_HD int tvl1_pl_p(int ch, int S) { return ch < 2 ? PL_P11_0 + 4 * S + 2 * ch : PL_P31_0 + 2 * S; }
 
 struct PairDesc {
     int frame_a; // frame slot of I0
@@ -34,6 +42,7 @@ struct Tvl1Consts {
     float taut;  // (float)(tau/theta)
     float theta; // (float)theta
     int hyp;     // hypot reading of the exact arithmetic (tvl1_math.h: TVL1_HYP_*) for the scalar kernel forms
+    float gamma; // (float)tvl1_gamma: weight of the illumination channel u3 (0: no such channel; only the gamma kernels read it)
 };
 
 // Everything a TVL1 kernel needs for one level; passed by value as the kernel argument.
@@ -74,6 +83,9 @@ struct Tvl1LevelCtx {
                     // not write them
     int geom;       // tile geometry of the default step kernel: bit 0 = tile columns start at x = 0, bit 1 = halo as wide
                     // as the step is long (k_tvl1_step_fused; 0 = classic)
+    int n_planes;   // planes of a pair slot: PL_COUNT, or PL_COUNT_GAMMA with the illumination channel (slot_stride = n_planes x
+                    // plane_stride).  No kernel reads it (they address through slot_stride): the launchers of the gamma kernels
+                    // check it, so that none of them is ever started on a 16-plane slot
 };
 
 static inline int dfx_round_up(int v, int m) { return (v + m - 1) / m * m; }

@@ -47,6 +47,7 @@ struct Tvl1Plan {
     int nlevels = 0;
     DfxPlanLevel lv[DFX_LVL_MAX];
     long long frame_elems = 0;                 // floats of one pyramid of a frame slot (three of them: I, Ix, Iy)
+    int n_planes = 0;                          // planes of a pair slot: PL_COUNT, PL_COUNT_GAMMA with tvl1_gamma != 0
     long long plane_stride = 0, slot_stride = 0; // floats between the planes of a pair slot / between pair slots
     int partials_stride = 0;                   // doubles per pair: >= workgroups of any step variant
     int batch = 0;                             // before the free-memory rule
@@ -75,8 +76,10 @@ inline void tvl1_plan(Tvl1Plan &pl, int W, int H, const dfx_params &p) {
         pl.lv[s] = DfxPlanLevel{0, 0, 0, 0};
     pl.frame_elems = off;
     pl.plane_stride = (long long)pl.lv[0].pitch * H;
-    pl.slot_stride = pl.plane_stride * PL_COUNT;
-    // the tile kernels address a pair slot with 32-bit byte offsets behind a buffer descriptor (tvl1_device_common.h)
+    pl.n_planes = p.tvl1_gamma != 0.0 ? (int)PL_COUNT_GAMMA : (int)PL_COUNT; // u3, p31, p32 in both sets (dfx_device.h)
+    pl.slot_stride = pl.plane_stride * pl.n_planes;
+    // the tile kernels address a pair slot with 32-bit byte offsets behind a buffer descriptor (tvl1_device_common.h):
+    // round_up(w, 64) x h x 64 B < 2^32, x 88 B with the 22 planes of a gamma handle
     pl.slot_too_large = (unsigned long long)pl.slot_stride * sizeof(float) >= (1ull << 32);
     pl.partials_stride = ((pl.lv[0].w + 63) / 64) * ((H + 3) / 4) + 64;
     pl.batch = dfx_plan_batch(W, H, p.max_batch);

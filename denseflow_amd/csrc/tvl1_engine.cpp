@@ -11,6 +11,7 @@
 //     groups of identical step launches and only looks at one pinned word per group to learn that
 //     every pair has finished the level.
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 
@@ -47,6 +48,7 @@ class Tvl1Engine final : public AlgoEngine {
     }
     Tvl1LevelCtx level_ctx(int s, int n_pairs) const;
     int steps_per_group(int s, int nb) const;
+    int refuse_if_too_large(const Tvl1Plan &pl);
 
     dfx_context *c;
     int nlevels = 0;
@@ -66,6 +68,8 @@ class Tvl1Engine final : public AlgoEngine {
     int B = 0;
     float *d_planes = nullptr;
     long long plane_stride = 0, slot_stride = 0;
+    int n_planes = PL_COUNT; // planes of a pair slot (the plan's: PL_COUNT_GAMMA with the illumination channel)
+    bool gamma_on = false;   // dfx_params.tvl1_gamma != 0: a pair slot has the planes of u3 / p31 / p32 and their kernels run
     Tvl1State *d_state = nullptr;
     PairDesc *d_pairs = nullptr;
     PairDesc *h_pairs_pinned = nullptr;
@@ -134,14 +138,35 @@ int Tvl1Engine::create() {
         return dfx_fail(c, DFX_ERR_INVALID,
                         "tvl1_math must be 0 (exact), 1 (fast; tuned kernel only), 2 (exact, sqrtf hypot) or 3 (exact, "
                         "libm hypot)");
+    if (!std::isfinite(p.tvl1_gamma))
+        return dfx_fail(c, DFX_ERR_INVALID, "tvl1_gamma must be finite");
+    gamma_on = p.tvl1_gamma != 0.0;
+    if (gamma_on && p.tvl1_math != 0)
+        return dfx_fail(c, DFX_ERR_UNSUPPORTED, "tvl1_gamma != 0 runs the exact arithmetic with the default hypot reading only (tvl1_math 0)");
+    if (gamma_on && p.impl == 2)
+        return dfx_fail(c, DFX_ERR_UNSUPPORTED, "tvl1_gamma != 0 has no scalar tile function (impl 0 or 1)");
+    // The gamma tile kernel has no warp phase: the dedicated warp kernel always runs in front of it.  That kernel has only
+    // ever run with tvl1_iterations > 0 (split_warp below), where a warp always leads into phase ITER; the gamma route
+    // keeps that condition and opens no configuration of it that the default path does not run.  (With zero iterations no
+    // update of A.6 / A.7 would run and the flow would be the gamma = 0 flow: ask for that.)
+    if (gamma_on && p.tvl1_iterations == 0)
+        return dfx_fail(c, DFX_ERR_UNSUPPORTED, "tvl1_gamma != 0 needs tvl1_iterations > 0");
+    {
+        // the size rule before anything is allocated (set_size applies it again to every later size)
+        Tvl1Plan pl;
+        tvl1_plan(pl, c->W, c->H, p);
+        if (const int rc = refuse_if_too_large(pl))
+            return rc;
+    }
     group_override = std::max(0, std::min(p.step_group, 64));
     // the dedicated warp kernel does not write the grad plane: only the packed tile function (impl 0) rebuilds it;
-    // zero iterations: warps inside the step kernel
-    split_warp = p.impl == 0 && p.tvl1_iterations > 0 && !(p.variant & DFX_VAR_TVL1_WARP_IN_STEP);
+    // zero iterations: warps inside the step kernel.  DFX_VAR_TVL1_WARP_IN_STEP names a form the gamma route lacks: ignored there
+    split_warp = p.impl == 0 && p.tvl1_iterations > 0 && (gamma_on || !(p.variant & DFX_VAR_TVL1_WARP_IN_STEP));
     // tile columns from x = 0 (tvl1_ctrl.h) need every warp outside the step kernel (its warp phase tiles classically)
     geom = (p.impl == 0 && split_warp && !(p.variant & DFX_VAR_TVL1_CLASSIC_GEOM)) ? 1 : 0;
     // warp + head of the loop in one launch (round 6): the tuned forms only — every cross-check variant keeps its own kernels
-    warp_head = split_warp && geom == 1 && !(p.variant & (DFX_VAR_TVL1_NO_HEAD | DFX_VAR_TVL1_WARP_GATHER));
+    // (the warp does not read u3: gamma handles take the dedicated warp kernel plus step launches, as NO_HEAD does)
+    warp_head = split_warp && geom == 1 && !gamma_on && !(p.variant & (DFX_VAR_TVL1_NO_HEAD | DFX_VAR_TVL1_WARP_GATHER));
 
     loop.warps = p.tvl1_warps;
     loop.iterations = p.tvl1_iterations;
@@ -153,6 +178,7 @@ int Tvl1Engine::create() {
     kc.taut = (float)(p.tvl1_tau / p.tvl1_theta);
     kc.theta = (float)p.tvl1_theta;
     kc.hyp = p.tvl1_math == 1 ? 0 : p.tvl1_math; // tvl1_math.h: TVL1_HYP_* (the fast mode never reaches a scalar form)
+    kc.gamma = (float)p.tvl1_gamma;              // passed as float (A.6 with gamma)
 
     HIPCHK(c, hipMalloc(&d_level_done, sizeof(unsigned int)));
     HIPCHK(c, hipHostMalloc(&h_done_flag, 64, hipHostMallocMapped));
@@ -175,11 +201,19 @@ size_t Tvl1Engine::device_bytes() const {
 
 // Plan (engine_plan.h: host arithmetic) + ensure capacity.  Nothing of the engine changes before the last allocation has
 // succeeded; the buffers a failed attempt has already grown stay grown.
+int Tvl1Engine::refuse_if_too_large(const Tvl1Plan &pl) {
+    if (!pl.slot_too_large)
+        return DFX_OK;
+    if (pl.n_planes == PL_COUNT_GAMMA)
+        return dfx_fail(c, DFX_ERR_INVALID, "tvl1: frame too large for tvl1_gamma != 0 (a pair's 22 work planes must stay below 4 GiB: round_up(width, 64) x height x 88 B < 2^32)");
+    return dfx_fail(c, DFX_ERR_INVALID, "tvl1: frame too large (a pair's 16 work planes must stay below 4 GiB: round_up(width, 64) x height x 64 B < 2^32)");
+}
+
 int Tvl1Engine::set_size(int W, int H) {
     Tvl1Plan pl;
-    tvl1_plan(pl, W, H, c->prm);
-    if (pl.slot_too_large)
-        return dfx_fail(c, DFX_ERR_INVALID, "tvl1: frame too large (a pair's 16 work planes must stay below 4 GiB: round_up(width, 64) x height x 64 B < 2^32)");
+    tvl1_plan(pl, W, H, c->prm); // with the handle's own plane count (tvl1_gamma is part of its parameters)
+    if (const int rc = refuse_if_too_large(pl))
+        return rc;
     // batch: enough pairs that the coarse levels fill 256 CUs, bounded by memory — by what is free now plus what this
     // engine holds and would give back for a larger allocation
     size_t free_b = 0, total_b = 0;
@@ -237,6 +271,7 @@ int Tvl1Engine::set_size(int W, int H) {
     frame_elems = pl.frame_elems;
     plane_stride = pl.plane_stride;
     slot_stride = pl.slot_stride;
+    n_planes = pl.n_planes;
     partials_stride = pl.partials_stride;
     B = nB;
     n_frame_slots = frame_slots_held(frame_elems);
@@ -345,6 +380,7 @@ Tvl1LevelCtx Tvl1Engine::level_ctx(int s, int n_pairs) const {
     x.warp_lds = (c->prm.variant & DFX_VAR_TVL1_WARP_GATHER) ? 0 : 1;
     x.geom = geom;
     x.head = warp_head ? 1 : 0;
+    x.n_planes = n_planes;
     return x;
 }
 
@@ -376,6 +412,10 @@ int Tvl1Engine::run_pairs(int nb, const PairDesc *h_pairs, float *d_out, long lo
         x.done_token = ++done_token;
         tvl1_launch_level_begin(c->stream, x, s == nlevels - 1);
         c->stats.kernel_launches += (warp_head && s != nlevels - 1) ? 1 : 2;
+        if (gamma_on) {
+            tvl1_launch_level_begin_gamma(c->stream, x, s == nlevels - 1);
+            c->stats.kernel_launches += 1;
+        }
         launched_steps[s] = 0;
         if (loop.warps > 0) {
             const int G = steps_per_group(s, nb);
@@ -387,7 +427,10 @@ int Tvl1Engine::run_pairs(int nb, const PairDesc *h_pairs, float *d_out, long lo
                         tvl1_launch_warp_head(c->stream, x, step_id, math, head_regs);
                     else if (split_warp)
                         tvl1_launch_warp(c->stream, x, step_id);
-                    tvl1_launch_step(c->stream, x, step_id++, impl, math, nbr_lds);
+                    if (gamma_on)
+                        tvl1_launch_step_gamma(c->stream, x, step_id++, impl);
+                    else
+                        tvl1_launch_step(c->stream, x, step_id++, impl, math, nbr_lds);
                 }
                 c->stats.kernel_launches += (uint64_t)G * (split_warp ? 2 : 1);
                 HIPCHK(c, hipEventRecord(ev_group[g & 1], c->stream));
@@ -411,6 +454,10 @@ int Tvl1Engine::run_pairs(int nb, const PairDesc *h_pairs, float *d_out, long lo
             const float ifx = (float)(1.0 / ((double)D.w / (double)S.w));
             const float ify = (float)(1.0 / ((double)D.h / (double)S.h));
             tvl1_launch_upsample_u(c->stream, x, D.w, D.h, D.pitch, ifx, ify, up);
+            if (gamma_on) {
+                tvl1_launch_upsample_u3(c->stream, x, D.w, D.h, D.pitch, ifx, ify);
+                c->stats.kernel_launches += 1;
+            }
         } else if (planar) {
             tvl1_launch_merge_planar(c->stream, x, *planar);
         } else {
@@ -459,8 +506,11 @@ int Tvl1Engine::account(int nb) {
             // lane-iterations the tuned kernels executed: half rows x 32 lanes x tiles (tvl1_ctrl.h: tvl1_step_work)
             st.tvl1_lane_iters += 32.0 * ((double)h_work[(b * DFX_LVL_MAX + s) * 2 + 0] * step_tiles[s] +
                                           (double)h_work[(b * DFX_LVL_MAX + s) * 2 + 1] * head_tiles[s]);
-            st.algorithmic_bytes += px * (64.0 * (double)it + 44.0 * loop.warps + 28.0);
-            st.step_algorithmic_bytes += px * (64.0 * (double)it + 44.0 * loop.warps);
+            // per pixel: an inner iteration reads 10 planes and writes 6 (64 B; with u3, p31, p32: 13 and 9, 88 B), a warp
+            // moves 44 B (it does not read u3), a level 28 B (+ 14 B with gamma: two more planes zeroed, u3 upsampled)
+            const double it_b = gamma_on ? 88.0 : 64.0, lvl_b = gamma_on ? 42.0 : 28.0;
+            st.algorithmic_bytes += px * (it_b * (double)it + 44.0 * loop.warps + lvl_b);
+            st.step_algorithmic_bytes += px * (it_b * (double)it + 44.0 * loop.warps);
         }
         st.pairs += 1;
     }

@@ -27,3 +27,9 @@ void tvl1_launch_upsample_u(hipStream_t s, const Tvl1LevelCtx &c_src, int dw, in
                             float up);
 void tvl1_launch_merge(hipStream_t s, const Tvl1LevelCtx &c0, float *out, long long out_stride);
 void tvl1_launch_merge_planar(hipStream_t s, const Tvl1LevelCtx &c0, const DfxPlanarOut &o); // u and v planes, bounded
+// the illumination channel (dfx_params.tvl1_gamma != 0): p31 = p32 = 0 (and u3 = 0 at the coarsest level) behind
+// tvl1_launch_level_begin; the step with the third channel (impl 0: fused tile kernel behind tvl1_launch_warp, 1: simple
+// kernel); u3's upsample (factor 1) beside tvl1_launch_upsample_u
+void tvl1_launch_level_begin_gamma(hipStream_t s, const Tvl1LevelCtx &c, int first_level);
+void tvl1_launch_step_gamma(hipStream_t s, const Tvl1LevelCtx &c, int step_id, int impl);
+void tvl1_launch_upsample_u3(hipStream_t s, const Tvl1LevelCtx &c_src, int dw, int dh, int dpitch, float ifx, float ify);

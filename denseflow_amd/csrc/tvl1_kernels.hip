@@ -716,6 +716,247 @@ __global__ __launch_bounds__(64 * FT_NW, DFX_FT_WGS) void k_tvl1_step_fused_nbr_
 }
 
 // ------------------------------------------------------------------------------------------------
+// The illumination channel (dfx_params.tvl1_gamma != 0; SURVEY.md Appendix A "with gamma", rated MED): a third unknown u3
+// with its dual (p31, p32) in planes PL_U3_* / PL_P31_* / PL_P32_* behind the 16 of the default slot (dfx_device.h).  The
+// backward warp does not read u3 (A.5 unchanged), the convergence sum does not contain it and merge does not output it, so
+// those kernels, the state machine and the ticket reduction are the default path's.  What follows is what differs:
+// level begin (p31 = p32 = 0, u3 = 0 at the coarsest level), the upsample of u3 (factor 1), the simple step (impl 1) and
+// the fused tile step (impl 0, tvl1_gamma_tile.h).  Exact arithmetic with the default hypot reading only.
+
+#include "tvl1_gamma_tile.h"
+
+// p31 = p32 = 0 once per level, u3 = 0 at the coarsest level; launched behind k_tvl1_level_begin, reads state.cur.
+__global__ __launch_bounds__(256) void k_tvl1_zero_planes_gamma(Tvl1LevelCtx c, int first_level) {
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63);
+    const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x >= c.pitch || y >= c.h)
+        return;
+    const int b = blockIdx.z;
+    const int cur = c.state[b].cur;
+    const long long o = (long long)y * c.pitch + x;
+    pair_plane(c, b, PL_P31_0 + 2 * cur)[o] = 0.0f;
+    pair_plane(c, b, PL_P32_0 + 2 * cur)[o] = 0.0f;
+    if (first_level)
+        pair_plane(c, b, PL_U3_0 + cur)[o] = 0.0f;
+}
+
+// u3(level s-1) = resize(u3(level s), dsize): k_tvl1_upsample_u's resize without the 1/scaleStep factor.
+__global__ __launch_bounds__(256) void k_tvl1_upsample_u3(Tvl1LevelCtx c, int dw, int dh, int dpitch, float ifx, float ify) {
+    const DfxBlockXY blk = dfx_block_xy();
+    const int x = blk.x * 64 + (threadIdx.x & 63);
+    const int y = blk.y * 4 + (threadIdx.x >> 6);
+    if (x >= dw || y >= dh)
+        return;
+    const int b = blockIdx.z;
+    const int cur = c.state[b].cur;
+    pair_plane(c, b, PL_U3_0 + (cur ^ 1))[(long long)y * dpitch + x] =
+        resize_linear_px(pair_plane(c, b, PL_U3_0 + cur), c.w, c.h, c.pitch, x, y, ifx, ify);
+}
+
+// A.6 with gamma for one pixel from planes in global memory (the simple variant's estimate_u_px with the third channel)
+struct PlanesGammaRO {
+    const float *I1wx, *I1wy, *grad, *rho_c, *u[3], *pa[3], *pb[3];
+};
+
+__device__ __forceinline__ void estimate_u_px_gamma(const PlanesGammaRO &P, int pitch, int x, int y, float l_t, float theta,
+                                                    float gamma, float (&un)[3], float (&uo)[3]) {
+    const long long o = (long long)y * pitch + x;
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch)
+        uo[ch] = P.u[ch][o];
+    const float I1wx = P.I1wx[o], I1wy = P.I1wy[o], grad = P.grad[o];
+    const float rho = P.rho_c[o] + ((I1wx * uo[0] + I1wy * uo[1]) + gamma * uo[2]);
+    const float lg = l_t * grad;
+    const float fi = tvl1_div(-rho, grad);
+    const bool c1 = rho < -lg, c2 = rho > lg, c3 = grad > FLT_EPSILON;
+    const float w[3] = {I1wx, I1wy, gamma};
+    const bool hl = x > 0, hu = y > 0;
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+        const float a = l_t * w[ch], bq = fi * w[ch];
+        const float d = c1 ? a : (c2 ? -a : (c3 ? bq : 0.0f));
+        const float pal = hl ? P.pa[ch][o - 1] : 0.0f, pbu = hu ? P.pb[ch][o - pitch] : 0.0f;
+        un[ch] = (uo[ch] + d) + theta * tvl1_divergence(P.pa[ch][o], pal, P.pb[ch][o], pbu, hl, hu);
+    }
+}
+
+// The simple step kernel with the third channel (impl 1: the cross-check form): k_tvl1_step_simple's phases, ticket protocol
+// and error sum; one pixel per thread, one inner iteration per step.
+__global__ __launch_bounds__(256) void k_tvl1_step_simple_gamma(Tvl1LevelCtx c, int step_id) {
+    __shared__ double lds_red[8];
+    __shared__ int lds_flag;
+
+    const int b = blockIdx.z;
+    Tvl1State *st = c.state + b;
+    const int phase = st->phase;
+    if (phase == TVL1_PH_LEVEL_DONE)
+        return;
+
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63);
+    const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    const bool inside = x < c.w && y < c.h;
+    const unsigned nblk = gridDim.x * gridDim.y;
+    const int blk = blockIdx.y * gridDim.x + blockIdx.x;
+    const long long o = (long long)y * c.pitch + x;
+
+    if (phase == TVL1_PH_WARP) { // A.5 unchanged: the warp reads u1, u2 only
+        const int cur = st->cur;
+        if (inside) {
+            const PairDesc pd = c.pairs[b];
+            const float *I0 = c.frame_I + (long long)pd.frame_a * c.frame_stride + c.lvl_off;
+            const long long fb = (long long)pd.frame_b * c.frame_stride + c.lvl_off;
+            const float u1v = pair_plane(c, b, PL_U1_0 + 2 * cur)[o];
+            const float u2v = pair_plane(c, b, PL_U2_0 + 2 * cur)[o];
+            const WarpOut r = warp_backward_px(I0, c.frame_I + fb, c.frame_Ix + fb, c.frame_Iy + fb, c.w, c.h,
+                                               c.pitch, x, y, u1v, u2v);
+            pair_plane(c, b, PL_I1WX)[o] = r.I1wx;
+            pair_plane(c, b, PL_I1WY)[o] = r.I1wy;
+            pair_plane(c, b, PL_GRAD)[o] = r.grad;
+            pair_plane(c, b, PL_RHOC)[o] = r.rho_c;
+        }
+        if (arrive_is_last(st, nblk, &lds_flag) && threadIdx.x == 0) {
+            tvl1_begin_loop(*st, c.loop, step_id);
+            if (st->phase == TVL1_PH_LEVEL_DONE)
+                finish_level(dfx_kernarg_ctx(), b, *st, step_id);
+            __hip_atomic_store(&st->ticket, 0u, __ATOMIC_RELAXED, AGENT);
+        }
+        return;
+    }
+
+    // ---- phase ITER
+    const Tvl1State s0 = *st;
+    const Tvl1StepPlan plan = tvl1_plan_step(s0, c.loop, step_id);
+    if (plan.n_iters <= 0)
+        return;
+    const int S = plan.src, D = S ^ 1;
+    PlanesGammaRO P;
+    P.I1wx = pair_plane(c, b, PL_I1WX);
+    P.I1wy = pair_plane(c, b, PL_I1WY);
+    P.grad = pair_plane(c, b, PL_GRAD);
+    P.rho_c = pair_plane(c, b, PL_RHOC);
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+        P.u[ch] = pair_plane(c, b, tvl1_pl_u(ch, S));
+        P.pa[ch] = pair_plane(c, b, tvl1_pl_p(ch, S));
+        P.pb[ch] = pair_plane(c, b, tvl1_pl_p(ch, S) + 1);
+    }
+
+    double dsum = 0.0;
+    if (inside) {
+        const float l_t = c.k.l_t, theta = c.k.theta, gamma = c.k.gamma;
+        float un[3], uo[3];
+        estimate_u_px_gamma(P, c.pitch, x, y, l_t, theta, gamma, un, uo);
+        // forward differences of the NEW u with clamp (A.7): neighbours are recomputed here
+        float ux[3] = {0.0f, 0.0f, 0.0f}, uy[3] = {0.0f, 0.0f, 0.0f};
+        if (x + 1 < c.w) {
+            float a[3], t[3];
+            estimate_u_px_gamma(P, c.pitch, x + 1, y, l_t, theta, gamma, a, t);
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch)
+                ux[ch] = a[ch] - un[ch];
+        }
+        if (y + 1 < c.h) {
+            float a[3], t[3];
+            estimate_u_px_gamma(P, c.pitch, x, y + 1, l_t, theta, gamma, a, t);
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch)
+                uy[ch] = a[ch] - un[ch];
+        }
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) {
+            float pa = P.pa[ch][o], pb = P.pb[ch][o];
+            tvl1_dual(pa, pb, ux[ch], uy[ch], c.k.taut, c.k.hyp);
+            pair_plane(c, b, tvl1_pl_u(ch, D))[o] = un[ch];
+            pair_plane(c, b, tvl1_pl_p(ch, D))[o] = pa;
+            pair_plane(c, b, tvl1_pl_p(ch, D) + 1)[o] = pb;
+        }
+        if (plan.do_check) {
+            const float e1 = uo[0] - un[0], e2 = uo[1] - un[1];
+            dsum = (double)(e1 * e1 + e2 * e2); // diff(y,x): u3 does not enter it
+        }
+    }
+
+    if (!plan.is_last)
+        return;
+
+    double *partials = c.partials + (long long)b * c.partials_stride;
+    if (plan.do_check) {
+        const double bs = block_reduce_sum_f64(dsum, lds_red);
+        if (threadIdx.x == 0)
+            publish_partial(partials + blk, bs);
+    }
+    if (!arrive_is_last(st, nblk, &lds_flag))
+        return;
+
+    double err = 0.0;
+    if (plan.do_check) {
+        double acc = 0.0;
+        for (unsigned i = threadIdx.x; i < nblk; i += blockDim.x)
+            acc += read_partial(partials + i);
+        err = block_reduce_sum_f64(acc, lds_red);
+    }
+    if (threadIdx.x == 0) {
+        tvl1_end_segment(*st, c.loop, plan, step_id, err);
+        if (st->phase == TVL1_PH_LEVEL_DONE)
+            finish_level(dfx_kernarg_ctx(), b, *st, step_id);
+        __hip_atomic_store(&st->ticket, 0u, __ATOMIC_RELAXED, AGENT);
+    }
+}
+
+template <int TH, int NW, bool INTERIOR>
+__device__ __forceinline__ double fused_tile_iterate_gamma(const Tvl1LevelCtx &c, int b, f2 (*kc)[TH / 2][64],
+                                                           float (*bnd)[2 * NW][64], int S, int n_iters, bool do_check,
+                                                           int K, int x0, int y0, bool own_lo, bool own_hi) {
+    float pf[GPF_PLANES][TH / NW / 2][2];
+    GammaTileState<TH / NW / 2> T;
+    const int role = RowMap<TH, NW>::who();
+    gamma_tile_issue_loads<TH, NW, INTERIOR>(c, b, S, x0, y0, pf);
+    gamma_tile_consume<TH, NW, INTERIOR>(c, x0, y0, pf, T, kc, bnd);
+    __syncthreads();
+    double dsum;
+    if (role * (TH / NW / 2) < K) // only roles that hold halo rows carry the per-float2 skip tests
+        dsum = gamma_tile_iterate<TH, NW, INTERIOR, true>(c, T, kc, bnd, n_iters, do_check, K, x0, y0, role, own_lo, own_hi);
+    else
+        dsum = gamma_tile_iterate<TH, NW, INTERIOR, false>(c, T, kc, bnd, n_iters, do_check, K, x0, y0, role, own_lo, own_hi);
+    gamma_tile_store<TH, NW, INTERIOR>(c, b, S ^ 1, K, x0, y0, T, own_lo, own_hi);
+    return dsum;
+}
+
+// The fused step kernel with the third channel (impl 0): k_tvl1_step_fused's tiles, halo rule, geometry and ticket
+// reduction (end_iter_tile), up to K inner iterations per launch, three waves per SIMD.  The dedicated warp kernel runs in
+// front of every launch (the engine routes gamma handles that way), so phase WARP has nothing to do here.
+__global__ __launch_bounds__(64 * FT_NW, DFX_FT_WGS) void k_tvl1_step_fused_gamma(Tvl1LevelCtx c, int step_id) {
+    constexpr int TW = 64, TH = FT_TH, NW = FT_NW;
+    __shared__ __attribute__((aligned(16))) f2 kc[KC_PLANES][TH / 2][TW];
+    __shared__ float bnd[GB_PLANES][2 * NW][TW];
+    __shared__ double lds_red[8];
+    __shared__ int lds_flag;
+
+    const int b = blockIdx.z;
+    Tvl1State *st = c.state + b;
+    if (st->phase != TVL1_PH_ITER)
+        return;
+    const int K = c.loop.fuse_k;
+    const unsigned nblk = gridDim.x; // = tiles of a step of this geometry (tvl1_step_grid)
+    const Tvl1StepPlan plan = tvl1_plan_step(*st, c.loop, step_id);
+    if (plan.n_iters <= 0)
+        return;
+    const Tvl1StepGeom g = tvl1_step_geom(c.w, c.h, TW, TH, K, c.geom);
+    const Tvl1TilePlace tp = tvl1_tile_place(g, TW, TH, dfx_xcd_tile_index((int)blockIdx.x, (int)nblk));
+    const int xs = tp.x0, ys = tp.y0;
+    const bool interior = xs >= 1 && ys >= 1 && xs + TW + 1 <= c.w && ys + TH + 1 <= c.h;
+    double dsum;
+    if (interior)
+        dsum = fused_tile_iterate_gamma<TH, NW, true>(c, b, kc, bnd, plan.src, plan.n_iters, plan.do_check != 0, K, xs, ys,
+                                                      false, false);
+    else
+        dsum = fused_tile_iterate_gamma<TH, NW, false>(c, b, kc, bnd, plan.src, plan.n_iters, plan.do_check != 0, K, xs, ys,
+                                                       tp.own_lo != 0, tp.own_hi != 0);
+    if (plan.is_last)
+        end_iter_tile(c, b, st, plan, nblk, (int)blockIdx.x, step_id, dsum, lds_red, &lds_flag);
+}
+
+// ------------------------------------------------------------------------------------------------
 // host-callable launchers (the only symbols the control code uses)
 
 static inline dim3 grid_for(int w, int h, int z) { return dim3((w + 63) / 64, (h + 3) / 4, z); }
@@ -748,6 +989,7 @@ void tvl1_launch_level_begin(hipStream_t s, const Tvl1LevelCtx &c, int first_lev
 }
 
 int tvl1_fused_max_k() { return FT_TH / 2 - 4; } // owned region stays >= 8 rows tall
+extern "C" int dfxi_tvl1_fused_max_k() { return tvl1_fused_max_k(); } // test hook, not part of the ABI: the tests sweep up to it
 
 // impl: 0 = packed tile function (math = dfx_params.tvl1_math; the scalar forms take the hypot reading from c.k.hyp), 1 = simple one-pixel-per-thread kernel, 2 = scalar tile
 // function.  nbr_lds: impl 0 in its register form (DFX_VAR_TVL1_STEP_NBR_LDS).  The grid of the fused kernels is the step's
@@ -801,4 +1043,32 @@ void tvl1_launch_merge(hipStream_t s, const Tvl1LevelCtx &c0, float *out, long l
 
 void tvl1_launch_merge_planar(hipStream_t s, const Tvl1LevelCtx &c0, const DfxPlanarOut &o) {
     hipLaunchKernelGGL(k_tvl1_merge_planar, dfx_planar_merge_grid(c0.w, c0.h, c0.n_pairs), dim3(256), 0, s, c0, o);
+}
+
+// ---- the illumination channel (tvl1_gamma != 0)
+static inline void require_gamma_slot(const Tvl1LevelCtx &c) { // planes 16 .. 21 exist only in a 22-plane slot
+    if (c.n_planes != PL_COUNT_GAMMA) {
+        fprintf(stderr, "dfx: a tvl1_gamma kernel was launched on a pair slot of %d planes\n", c.n_planes);
+        abort();
+    }
+}
+
+void tvl1_launch_level_begin_gamma(hipStream_t s, const Tvl1LevelCtx &c, int first_level) {
+    require_gamma_slot(c);
+    hipLaunchKernelGGL(k_tvl1_zero_planes_gamma, grid_for(c.pitch, c.h, c.n_pairs), dim3(256), 0, s, c, first_level);
+}
+
+// impl 0: the fused tile kernel (behind tvl1_launch_warp of the same step id), 1: the simple kernel
+void tvl1_launch_step_gamma(hipStream_t s, const Tvl1LevelCtx &c, int step_id, int impl) {
+    require_gamma_slot(c);
+    if (impl == 1)
+        hipLaunchKernelGGL(k_tvl1_step_simple_gamma, grid_for(c.w, c.h, c.n_pairs), dim3(256), 0, s, c, step_id);
+    else
+        hipLaunchKernelGGL(k_tvl1_step_fused_gamma, dim3(tvl1_step_blocks(c, 0), 1, c.n_pairs), dim3(64 * FT_NW), 0, s, c,
+                           step_id);
+}
+
+void tvl1_launch_upsample_u3(hipStream_t s, const Tvl1LevelCtx &c_src, int dw, int dh, int dpitch, float ifx, float ify) {
+    require_gamma_slot(c_src);
+    hipLaunchKernelGGL(k_tvl1_upsample_u3, grid_for(dw, dh, c_src.n_pairs), dim3(256), 0, s, c_src, dw, dh, dpitch, ifx, ify);
 }

@@ -64,6 +64,7 @@ class DfxParams(C.Structure):
         ("variant", C.c_int),
         ("step_group", C.c_int),
         ("blocking_sync", C.c_int),
+        ("tvl1_gamma", C.c_double),  # last: a library built before it (DFX_LIBRARY A/B) reads the fields it knows
     ]
 
 

@@ -13,7 +13,10 @@ tests/test_opencv_pin.py picks the files up when present: the CPU oracle (-m "no
 must then agree with OpenCV within BASELINE.json's 1e-3 max-abs (TVL1, Farneback) — and the Brox oracle, which today
 DEFINES its algorithm, gets its first external check.  opencv_farn_gaussian.npz is the Gaussian update window
 (dfx_params.farn_window, restated from memory and rated MED): winSize 15 with OPTFLOW_FARNEBACK_GAUSSIAN, picked up by
-tests/test_opencv_pin_farn_gaussian.py.  Nothing here imports the product or the oracle.
+tests/test_opencv_pin_farn_gaussian.py.  opencv_tvl1_gamma.npz is the illumination channel of TVL1 (dfx_params.tvl1_gamma,
+restated from memory and rated MED): cuda.OpticalFlowDual_TVL1_create(gamma=0.4) and gamma=2.0 on the two smallest seeds
+(the file stays below the 1 MiB a committed fixture may have), picked up by tests/test_opencv_pin_tvl1_gamma.py.  Nothing
+here imports the product or the oracle.
 
     python scripts/pin_against_opencv.py [--out tests/golden] [--testdata $OPENCV_TEST_DATA_PATH]
 With --testdata the upstream fixtures SURVEY.md §4 names are added as cases: cv/optflow/RubberWhale1.png / 2.png
@@ -80,6 +83,16 @@ def main():
             blob[name + "_f0"], blob[name + "_f1"], blob[name + "_flow"] = a, b, flow.astype(np.float32)
             print(algo, name, flow.shape, float(np.abs(flow).max()))
         np.savez_compressed(os.path.join(args.out, f"opencv_{algo}.npz"), **blob)
+    # the illumination channel: create(tau, lambda, theta, nscales, warps, epsilon, iterations, scaleStep, gamma, useInitialFlow)
+    blob = {"build_information": np.array(info), "opencv_version": np.array(cv2.__version__)}
+    for name, a, b in pairs[:2]:
+        blob[name + "_f0"], blob[name + "_f1"] = a, b
+        for gamma in (0.4, 2.0):
+            alg = cv2.cuda_OpticalFlowDual_TVL1.create(0.25, 0.15, 0.3, 5, 5, 0.01, 300, 0.8, gamma, False)
+            flow = alg.calc(up(a), up(b), None).download()
+            blob[f"{name}_gamma{gamma}_flow"] = flow.astype(np.float32)
+            print("tvl1_gamma", gamma, name, flow.shape, float(np.abs(flow).max()))
+    np.savez_compressed(os.path.join(args.out, "opencv_tvl1_gamma.npz"), **blob)
     if hasattr(cv2, "optflow") and hasattr(cv2.optflow, "DualTVL1OpticalFlow_create"):  # the CPU comparator
         blob = {"build_information": np.array(info), "opencv_version": np.array(cv2.__version__)}
         for name, a, b in pairs[:3]:
