@@ -26,7 +26,8 @@ class BroxEngine final : public AlgoEngine {
     int frame_slots() const override { return n_frame_slots; }
     int build_frames(const unsigned char *d_src, long long src_frame_stride, long long src_pitch, int n,
                      const int *h_slots) override;
-    int run_pairs(int nb, const PairDesc *h_pairs, float *d_out, long long out_stride, const DfxPlanarOut *planar) override;
+    int run_pairs(int nb, const PairDesc *h_pairs, float *d_out, long long out_stride, const DfxPlanarOut *planar,
+                  const DfxSeedIn *seed) override;
     int account(int nb) override;
 
   private:
@@ -218,7 +219,10 @@ BroxLevelCtx BroxEngine::level_ctx(int l, int nb) const {
     return x;
 }
 
-int BroxEngine::run_pairs(int nb, const PairDesc *h_pairs, float *d_out, long long out_stride, const DfxPlanarOut *planar) {
+int BroxEngine::run_pairs(int nb, const PairDesc *h_pairs, float *d_out, long long out_stride, const DfxPlanarOut *planar,
+                          const DfxSeedIn *seed) {
+    if (seed) // upstream's BroxOpticalFlow takes no initial flow
+        return dfx_fail(c, DFX_ERR_UNSUPPORTED, "brox has no initial flow");
     std::memcpy(h_pairs_pinned, h_pairs, sizeof(PairDesc) * nb);
     HIPCHK(c, hipMemcpyAsync(d_pairs, h_pairs_pinned, sizeof(PairDesc) * nb, hipMemcpyHostToDevice, c->stream));
     const dfx_params &p = c->prm;

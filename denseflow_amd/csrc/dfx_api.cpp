@@ -200,7 +200,7 @@ size_t dfx_device_bytes(dfx_handle h) {
         return 0;
     const auto &j = h->jpeg;
     size_t n = h->engine ? h->engine->device_bytes() : 0;
-    n += 2 * (h->u8_bytes + h->flow_bytes + h->src_bytes + h->img_bytes);
+    n += 2 * (h->u8_bytes + h->flow_bytes + h->src_bytes + h->img_bytes + h->seed_bytes);
     n += h->d_png_scratch ? quant_png_scratch_bytes(h->png_slots) : 0;
     n += (j.d_tab ? sizeof(JpegTables) : 0) + j.blocks_cap * (sizeof(short) + sizeof(unsigned)) + j.planes_cap * 16 +
          (j.d_hdr ? 16 : 0) + 2 * j.capacity;
@@ -478,6 +478,102 @@ int dfx_calc_batch_planar_device(dfx_handle h, const uint8_t *d_frames, size_t p
     out.d_planar = d_out;
     out.d_row_pitch = row_pitch_floats, out.d_plane_stride = plane_stride_floats, out.d_flow_stride = flow_stride_floats;
     return dfx_run_flowbuffer(h, InSpec::device(d_frames, pitch, frame_stride), n_frames, step, out, nullptr);
+}
+
+// ---- caller-supplied initial flows (TVL1's useInitialFlow, Farneback's OPTFLOW_USE_INITIAL_FLOW) ----
+namespace {
+// which handles take a seed: upstream's BroxOpticalFlow has no initial flow, and a DFX_ALGO_FRAMES handle computes no flow
+int refuse_seed(dfx_handle h) {
+    if (h->algo == DFX_ALGO_TVL1 || h->algo == DFX_ALGO_FARN)
+        return DFX_OK;
+    return dfx_fail(h, DFX_ERR_UNSUPPORTED, h->algo == DFX_ALGO_BROX ? "brox has no initial flow (BroxOpticalFlow takes none)"
+                                                                      : "a DFX_ALGO_FRAMES handle computes no flow");
+}
+} // namespace
+
+int dfx_calc_batch_init(dfx_handle h, const uint8_t *const *frames, size_t frame_pitch, int n_frames, int step,
+                        const float *const *init_uv, size_t init_pitch, float *const *flows_uv, size_t out_pitch) {
+    if (!h)
+        return DFX_ERR_INVALID;
+    SegmentsScope seg_scope(h);
+    if (const int rc = refuse_seed(h))
+        return rc;
+    if (!init_uv)
+        return dfx_fail(h, DFX_ERR_INVALID, "NULL initial flows");
+    const int M = std::max(n_frames - abs_step(step), 0);
+    if (M > 0 && (!frames || !flows_uv))
+        return dfx_fail(h, DFX_ERR_INVALID, "NULL frames or flows array");
+    if ((M > 0 && (pitch_too_small(h, frame_pitch) || out_pitch < (size_t)h->W * 8)) || init_pitch < (size_t)h->W * 8)
+        return dfx_fail(h, DFX_ERR_INVALID, "pitch smaller than a row");
+    OutSpec out;
+    out.flows = flows_uv;
+    out.out_pitch = out_pitch;
+    InSpec in = InSpec::host(frames, frame_pitch);
+    in.init = init_uv, in.init_pitch = init_pitch;
+    return dfx_run_flowbuffer(h, in, n_frames, step, out, nullptr);
+}
+
+int dfx_calc_batch_init_device(dfx_handle h, const uint8_t *d_frames, size_t pitch, size_t frame_stride, int n_frames,
+                               int step, const float *d_init, size_t init_stride_floats, float *d_flows,
+                               size_t flow_stride_floats) {
+    if (!h)
+        return DFX_ERR_INVALID;
+    SegmentsScope seg_scope(h);
+    if (const int rc = refuse_seed(h))
+        return rc;
+    if (src_segments_pending(h))
+        return dfx_fail(h, DFX_ERR_UNSUPPORTED, "dfx_next_segments_src applies to host-pointer calls only");
+    if (!d_init)
+        return dfx_fail(h, DFX_ERR_INVALID, "NULL initial flows");
+    const int M = std::max(n_frames - abs_step(step), 0);
+    if (M > 0 && (!d_frames || !d_flows))
+        return dfx_fail(h, DFX_ERR_INVALID, "NULL device frames or flows");
+    if ((M > 0 && (pitch < h->in_row_bytes() || frame_stride < pitch * (size_t)h->in_h() ||
+                   flow_stride_floats < (size_t)h->W * h->H * 2)) ||
+        init_stride_floats < (size_t)h->W * h->H * 2)
+        return dfx_fail(h, DFX_ERR_INVALID, "pitch/stride smaller than a frame");
+    OutSpec out;
+    out.d_flows = d_flows;
+    out.d_flow_stride = flow_stride_floats;
+    InSpec in = InSpec::device(d_frames, pitch, frame_stride);
+    in.d_init = d_init, in.d_init_stride = init_stride_floats;
+    return dfx_run_flowbuffer(h, in, n_frames, step, out, nullptr);
+}
+
+int dfx_calc_batch_planar_init_device(dfx_handle h, const uint8_t *d_frames, size_t pitch, size_t frame_stride,
+                                      int n_frames, int step, double norm_bound, const float *d_init, float *d_out,
+                                      size_t row_pitch_floats, size_t plane_stride_floats, size_t flow_stride_floats) {
+    if (!h)
+        return DFX_ERR_INVALID;
+    SegmentsScope seg_scope(h);
+    if (const int rc = refuse_seed(h))
+        return rc;
+    if (src_segments_pending(h))
+        return dfx_fail(h, DFX_ERR_UNSUPPORTED, "dfx_next_segments_src applies to host-pointer calls only");
+    if (!planar_bound_ok(norm_bound))
+        return dfx_fail(h, DFX_ERR_INVALID, kPlanarBound);
+    if (!d_init)
+        return dfx_fail(h, DFX_ERR_INVALID, "NULL initial flows");
+    const int M = std::max(n_frames - abs_step(step), 0);
+    if (M > 0 && (!d_frames || !d_out))
+        return dfx_fail(h, DFX_ERR_INVALID, "NULL device frames or flow planes");
+    if (M > 0 && (pitch < h->in_row_bytes() || frame_stride < pitch * (size_t)h->in_h()))
+        return dfx_fail(h, DFX_ERR_INVALID, "pitch/stride smaller than a frame");
+    if (M > 0 && (row_pitch_floats < (size_t)h->W || row_pitch_floats > ((size_t)1 << 40) ||
+                  plane_stride_floats < (size_t)h->H * row_pitch_floats || plane_stride_floats > ((size_t)1 << 60) ||
+                  flow_stride_floats < 2 * plane_stride_floats))
+        return dfx_fail(h, DFX_ERR_INVALID,
+                        "planar output: row_pitch_floats >= W, plane_stride_floats >= H * row_pitch_floats and "
+                        "flow_stride_floats >= 2 * plane_stride_floats are required");
+    OutSpec out;
+    out.planar = true;
+    out.norm_bound = (float)norm_bound;
+    out.d_planar = d_out;
+    out.d_row_pitch = row_pitch_floats, out.d_plane_stride = plane_stride_floats, out.d_flow_stride = flow_stride_floats;
+    InSpec in = InSpec::device(d_frames, pitch, frame_stride);
+    in.d_init = d_init, in.init_planar = true; // the seed's planes have the three strides of d_out
+    in.d_init_stride = flow_stride_floats, in.d_init_row_pitch = row_pitch_floats, in.d_init_plane_stride = plane_stride_floats;
+    return dfx_run_flowbuffer(h, in, n_frames, step, out, nullptr);
 }
 
 int dfx_calc_batch_png_device(dfx_handle h, const uint8_t *d_frames, size_t pitch, size_t frame_stride, int n_frames,
@@ -837,6 +933,8 @@ void dfx_destroy(dfx_handle h) {
     for (auto &p : h->d_flow_out)
         dfx_free_dev(p);
     for (auto &p : h->d_img)
+        dfx_free_dev(p);
+    for (auto &p : h->d_seed)
         dfx_free_dev(p);
     for (auto &p : h->d_src)
         dfx_free_dev(p);

@@ -107,6 +107,16 @@ static inline int dfx_planar_vec(const float *base, long long flow_stride, long 
 }
 
 // ------------------------------------------------------------------------------------------------
+// Caller-supplied initial flows (dfx_calc_batch_init*): one W x H field per pair of a launch, raw pixels, in the caller's
+// own layout — interleaved (u, v) rows (step 2, v = u + 1) or two planes (step 1).  Pixel (x, y) of pair i of the launch is
+// u[i * pair_stride + y * row_pitch + x * step] and the same element of v.  The engines only ever read it.
+struct DfxSeedIn {
+    const float *u, *v;               // pixel (0, 0) of the launch's first pair
+    int step;                         // floats between neighbouring pixels of a row: 2 or 1
+    long long row_pitch, pair_stride; // in floats
+};
+
+// ------------------------------------------------------------------------------------------------
 // XCD-aware workgroup -> tile mapping (device code only).  MI355X has 8 XCDs with a private 4 MiB L2 each and the
 // dispatcher is observed to place workgroup b of a launch on XCD b % 8 (MI355X_MICROARCH.md, "Workgroup dispatch"):
 // with the plain blockIdx -> tile mapping the neighbours of a tile — whose halo, box-filter or gather footprint
@@ -121,6 +131,25 @@ DFX_HD int dfx_xcd_tile_index(int lin, int nt) {
     return k * q + (k < rem ? k : rem) + (lin >> 3);
 }
 #if defined(__HIPCC__)
+// Bilinear sample of a strided source at destination pixel (dx, dy): the pyramid resize of both engines (SURVEY.md E.1 —
+// no half-pixel centring, upstream's accumulation order; resize_linear_px / resize_linear_px_f with neighbouring pixels
+// `step` floats apart and rows `spitch` floats).  The one place the seed kernels of both engines take it from: the order of
+// the four rounded multiply-adds is what their bit-exactness rests on.
+__device__ __forceinline__ float dfx_seed_resize_px(const float *src, int sw, int sh, long long spitch, int step, int dx, int dy,
+                                                    float ifx, float ify) {
+    const float sx = (float)dx * ifx;
+    const float sy = (float)dy * ify;
+    const int x1 = (int)floorf(sx), y1 = (int)floorf(sy);
+    const int x2 = x1 + 1, y2 = y1 + 1;
+    const int x2r = min(x2, sw - 1), y2r = min(y2, sh - 1);
+    const int x1r = min(x1, sw - 1), y1r = min(y1, sh - 1);
+    float out = 0.0f;
+    out = out + src[(long long)y1r * spitch + (long long)x1r * step] * (((float)x2 - sx) * ((float)y2 - sy));
+    out = out + src[(long long)y1r * spitch + (long long)x2r * step] * ((sx - (float)x1) * ((float)y2 - sy));
+    out = out + src[(long long)y2r * spitch + (long long)x1r * step] * (((float)x2 - sx) * (sy - (float)y1));
+    out = out + src[(long long)y2r * spitch + (long long)x2r * step] * ((sx - (float)x1) * (sy - (float)y1));
+    return out;
+}
 // One value on its way to a plane of DfxPlanarOut.  b == 0: the value itself, the bits the interleaved output holds.
 // b > 0: the clamped value through ONE IEEE division (no reciprocal), NaN -> 0: float32 np.clip(x, -b, b) / b.
 __device__ __forceinline__ float dfx_planar_value(float x, float b) {

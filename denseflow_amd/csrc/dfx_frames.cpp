@@ -24,7 +24,7 @@ class FramesEngine : public AlgoEngine {
     int ensure_frame_slots(int) override { return refuse(); }
     int frame_slots() const override { return 0; }
     int build_frames(const unsigned char *, long long, long long, int, const int *) override { return refuse(); }
-    int run_pairs(int, const PairDesc *, float *, long long, const DfxPlanarOut *) override { return refuse(); }
+    int run_pairs(int, const PairDesc *, float *, long long, const DfxPlanarOut *, const DfxSeedIn *) override { return refuse(); }
     int account(int) override { return refuse(); }
 
   private:

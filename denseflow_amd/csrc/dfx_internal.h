@@ -46,8 +46,10 @@ class AlgoEngine {
     virtual int build_frames(const unsigned char *d_src, long long src_frame_stride, long long src_pitch, int n,
                              const int *h_slots) = 0;
     // planar != nullptr: the flows go to *planar's u and v planes (dfx_device.h) instead, d_out / out_stride unused
+    // seed != nullptr: the pairs start from the caller's initial flows (DfxSeedIn, dfx_device.h: pair j of the batch is its
+    // pair j) instead of zero — TVL1 and Farneback; Brox has none upstream and returns DFX_ERR_UNSUPPORTED
     virtual int run_pairs(int nb, const PairDesc *h_pairs, float *d_out, long long out_stride,
-                          const DfxPlanarOut *planar = nullptr) = 0;
+                          const DfxPlanarOut *planar = nullptr, const DfxSeedIn *seed = nullptr) = 0;
     virtual int account(int nb) = 0; // reads per-batch event timers; stream is idle
     // dfxi_tvl1_batch_tables (dfx_api.cpp): the per-pair TVL1 tables of the last accounted batch, in pair order
     virtual int batch_tables(int max_pairs, int *iters, int *checks) const {
@@ -119,6 +121,10 @@ struct dfx_context {
     int u8_slots = 0;
     float *d_flow_out[2] = {nullptr, nullptr};   // flow_slots dense H*W*2 flows per set
     int flow_slots = 0;
+    // initial flows of the host-pointer seeded form (dfx_calc_batch_init): dense H*W*2 fields per set, uploaded beside the
+    // frames.  Allocated at the first seeded call: a handle that never seeds holds none (seed_bytes = 0)
+    float *d_seed[2] = {nullptr, nullptr};
+    size_t seed_bytes = 0; // per set
     unsigned char *d_src[2] = {nullptr, nullptr}; // source-format frames before preparation (src_slots per set)
     int src_slots = 0;
     size_t src_frame_bytes = 0;

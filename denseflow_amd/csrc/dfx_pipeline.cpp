@@ -79,6 +79,22 @@ int ensure_staging(dfx_context *c, int u8_need, int flow_need) {
     return rc;
 }
 
+// The staging pair of the host-pointer seeded form: `need` dense initial flows per set, kept by its size in bytes like
+// the others.  First allocated by the first seeded call of a handle.
+int ensure_seed_staging(dfx_context *c, int need) {
+    const size_t bytes = (size_t)need * c->W * c->H * 2 * sizeof(float);
+    if (bytes <= c->seed_bytes)
+        return DFX_OK;
+    size_t held = c->seed_bytes;
+    return dfx_regrow(c, held, bytes, [&]() -> int {
+        c->seed_bytes = 0;
+        const int rc = realloc_pair(c, c->d_seed, bytes);
+        if (rc == DFX_OK)
+            c->seed_bytes = bytes;
+        return rc;
+    });
+}
+
 // One frame / plane between host and device.  Dense rows (pitch == row bytes on both sides) go as ONE linear copy:
 // a 2-D copy of a small frame costs several times the linear one, and a FlowBuffer of 224x224 frames is hundreds
 // of them.
@@ -169,6 +185,8 @@ int FlowRun::prepare(const std::vector<int> &seg) {
         rc = ensure_staging(c, (host_mode || prep) ? F_need : 0, (host_mode || out.quantized) ? B : 0);
     if (rc == DFX_OK && prep && host_mode)
         rc = ensure_src_staging(c, F_need, src_stride);
+    if (rc == DFX_OK && in.init) // host-pointer seeds go up beside the frames
+        rc = ensure_seed_staging(c, B);
     if (rc == DFX_OK && out.quantized && host_mode)
         rc = dfx_ensure_img_staging(c, B);
     if (rc == DFX_OK && out.jpeg)
@@ -237,6 +255,10 @@ int FlowRun::upload(size_t k) { // host frames of batch k -> staging set par(k) 
                                       hipMemcpyHostToDevice, c->copy_stream));
         }
     }
+    if (in.init) // the initial flows of the batch's pairs, dense in staging set q (last read by the compute of batch q-2)
+        for (int j = 0; j < p.nb; ++j)
+            HIPCHK(c, copy_rows_async(c->d_seed[q] + (size_t)j * plane * 2, (size_t)c->W * 8, in.init[p.i0 + j], in.init_pitch,
+                                      (size_t)c->W * 8, c->H, hipMemcpyHostToDevice, c->copy_stream));
     HIPCHK(c, hipEventRecord(c->ev_h2d[q], c->copy_stream));
     return DFX_OK;
 }
@@ -423,6 +445,18 @@ int FlowRun::compute(size_t k) { // batch k on the compute stream, up to its sta
         c->h_pairs[j].frame_a = dfx_pair_a(pairs, i, step) % F;
         c->h_pairs[j].frame_b = dfx_pair_b(pairs, i, step) % F;
     }
+    DfxSeedIn seed{}; // the batch's initial flows: pair j of the batch is pair j of the descriptor
+    if (in.init) {
+        seed.u = c->d_seed[q], seed.step = 2, seed.row_pitch = (long long)c->W * 2, seed.pair_stride = (long long)plane * 2;
+    } else if (in.d_init && in.init_planar) {
+        seed.u = in.d_init + (size_t)p.i0 * in.d_init_stride, seed.step = 1;
+        seed.row_pitch = (long long)in.d_init_row_pitch, seed.pair_stride = (long long)in.d_init_stride;
+    } else if (in.d_init) {
+        seed.u = in.d_init + (size_t)p.i0 * in.d_init_stride, seed.step = 2;
+        seed.row_pitch = (long long)c->W * 2, seed.pair_stride = (long long)in.d_init_stride;
+    }
+    seed.v = seed.u ? seed.u + (seed.step == 2 ? 1 : (long long)in.d_init_plane_stride) : nullptr;
+    const DfxSeedIn *seedp = in.seeded() ? &seed : nullptr;
     const bool staged = host_mode || out.quantized;
     float *dst = staged ? c->d_flow_out[q] : out.planar ? nullptr : out.d_flows + (size_t)p.i0 * out.d_flow_stride;
     const long long dst_stride = staged ? (long long)plane * 2 : (long long)out.d_flow_stride;
@@ -434,9 +468,9 @@ int FlowRun::compute(size_t k) { // batch k on the compute stream, up to its sta
         po.row_pitch = staged ? (long long)c->W : (long long)out.d_row_pitch;
         po.bound = out.norm_bound;
         po.vec = dfx_planar_vec(po.base, po.flow_stride, po.plane_stride, po.row_pitch);
-        rc = E->run_pairs(p.nb, c->h_pairs.data(), nullptr, 0, &po);
+        rc = E->run_pairs(p.nb, c->h_pairs.data(), nullptr, 0, &po, seedp);
     } else {
-        rc = E->run_pairs(p.nb, c->h_pairs.data(), dst, dst_stride);
+        rc = E->run_pairs(p.nb, c->h_pairs.data(), dst, dst_stride, nullptr, seedp);
     }
     if (rc != DFX_OK)
         return rc;

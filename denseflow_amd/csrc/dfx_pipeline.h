@@ -9,6 +9,16 @@ struct InSpec {
     size_t frame_pitch = 0;
     const uint8_t *d_frames = nullptr; // device mode: frame i at d_frames + i * d_frame_stride, d_pitch bytes per row
     size_t d_pitch = 0, d_frame_stride = 0;
+    // Caller-supplied initial flows (dfx_calc_batch_init*), one per output flow in output order; all unset: none.
+    //   host mode  : init[i] = rows of interleaved (u, v) floats, init_pitch bytes per row
+    //   device mode: d_init + i * d_init_stride, interleaved dense rows — or (init_planar) a u plane there and a v plane
+    //                d_init_plane_stride behind it, rows d_init_row_pitch apart (all in floats)
+    const float *const *init = nullptr;
+    size_t init_pitch = 0;
+    const float *d_init = nullptr;
+    size_t d_init_stride = 0, d_init_row_pitch = 0, d_init_plane_stride = 0;
+    bool init_planar = false;
+    bool seeded() const { return init != nullptr || d_init != nullptr; }
     static InSpec host(const uint8_t *const *frames, size_t frame_pitch) {
         InSpec in;
         in.frames = frames, in.frame_pitch = frame_pitch;

@@ -78,7 +78,8 @@ class FarnebackEngine final : public AlgoEngine {
     int frame_slots() const override { return n_frame_slots; }
     int build_frames(const unsigned char *d_src, long long src_frame_stride, long long src_pitch, int n,
                      const int *h_slots) override;
-    int run_pairs(int nb, const PairDesc *h_pairs, float *d_out, long long out_stride, const DfxPlanarOut *planar) override;
+    int run_pairs(int nb, const PairDesc *h_pairs, float *d_out, long long out_stride, const DfxPlanarOut *planar,
+                  const DfxSeedIn *seed) override;
     int account(int nb) override;
 
   private:
@@ -105,6 +106,7 @@ class FarnebackEngine final : public AlgoEngine {
     float *d_f32 = nullptr, *d_tmpv = nullptr, *d_pyr = nullptr;
     int skip_zero_weights = 1, polyexp_rows = 16; // frame-preparation forms, fixed when the engine is created
     bool m_on_chip = true;                        // the default iteration kernel (M recomputed, never in HBM)
+    double seed_bytes_pair = 0;                   // bytes per pair the seed's resize of the batch in flight read (0: no seed)
     bool gauss_window = false;                    // dfx_params.farn_window: Gaussian taps in place of the box filter
     FarnWinTaps win_taps{};
 
@@ -306,7 +308,8 @@ int FarnebackEngine::build_frames(const unsigned char *d_src, long long src_fram
     return DFX_OK;
 }
 
-int FarnebackEngine::run_pairs(int nb, const PairDesc *h_pairs, float *d_out, long long out_stride, const DfxPlanarOut *planar) {
+int FarnebackEngine::run_pairs(int nb, const PairDesc *h_pairs, float *d_out, long long out_stride, const DfxPlanarOut *planar,
+                               const DfxSeedIn *seed) {
     std::memcpy(h_pairs_pinned, h_pairs, sizeof(PairDesc) * nb);
     HIPCHK(c, hipMemcpyAsync(d_pairs, h_pairs_pinned, sizeof(PairDesc) * nb, hipMemcpyHostToDevice, c->stream));
     const dfx_params &p = c->prm;
@@ -314,6 +317,14 @@ int FarnebackEngine::run_pairs(int nb, const PairDesc *h_pairs, float *d_out, lo
     const float box_inv = 1.f / (float)((1 + 2 * half) * (1 + 2 * half));
     const float up = (float)(1. / p.farn_pyr_scale);
     const FarnWinTaps *gauss = gauss_window ? &win_taps : nullptr; // nullptr: the box kernels, as before
+    // A caller-supplied initial flow enters at the coarsest level k = nlev - 1 only: resize_linear(seed, w_k, h_k) times
+    // (float)scale_k, scale_k the double that farneback_calc accumulates (pyrScale multiplied k times; 1 for one level).
+    double seed_scale = 1.0;
+    for (int k = 0; k < nlev - 1; ++k)
+        seed_scale *= p.farn_pyr_scale;
+    const FarnLevelGeom &T = lv[nlev - 1].g;
+    const float seed_ifx = (float)(1.0 / ((double)T.w / (double)c->W)), seed_ify = (float)(1.0 / ((double)T.h / (double)c->H));
+    seed_bytes_pair = seed ? 32.0 * T.w * T.h : 0.0; // four taps per pixel and channel
     FarnPairCtx x;
     std::memset(&x, 0, sizeof x);
     x.frame_R = d_R;
@@ -341,7 +352,16 @@ int FarnebackEngine::run_pairs(int nb, const PairDesc *h_pairs, float *d_out, lo
             for (int it = 0; it < p.farn_num_iters; ++it) {
                 const bool last = k == 0 && it == p.farn_num_iters - 1;
                 float *merged = last && !planar ? d_out : nullptr;
-                if (last && planar && it > 0)
+                if (seed && top && it == 0) {
+                    // the seed is this launch's input flow; it may be the very buffer the flows go to, so a launch that
+                    // is also the last one (one level, one iteration) leaves the caller's rows to the merge kernel
+                    farn_launch_iter_stream_seed(c->stream, x, half, cur ^ 1, box_inv, nullptr, 0, *seed, c->W, c->H, seed_ifx, seed_ify,
+                                                 (float)seed_scale, gauss);
+                    if (last && !planar) {
+                        farn_launch_merge(c->stream, x, cur ^ 1, d_out, out_stride);
+                        c->stats.kernel_launches += 1;
+                    }
+                } else if (last && planar && it > 0)
                     farn_launch_iter_stream_planar(c->stream, x, half, cur, cur ^ 1, box_inv, *planar, gauss);
                 else if (it == 0)
                     farn_launch_iter_stream_init(c->stream, x, half, cur, cur ^ 1, box_inv, merged, out_stride, P.w, P.h, P.pitch, ifx,
@@ -362,7 +382,9 @@ int FarnebackEngine::run_pairs(int nb, const PairDesc *h_pairs, float *d_out, lo
     int set = (nlev - 1) & 1; // flow set the level's iterations run in (the previous level ended in the other one)
     for (int k = nlev - 1; k >= 0; --k) {
         x.L = lv[k].g;
-        if (k == nlev - 1) {
+        if (k == nlev - 1 && seed) {
+            farn_launch_init_flow_seed(c->stream, x, set, *seed, c->W, c->H, seed_ifx, seed_ify, (float)seed_scale);
+        } else if (k == nlev - 1) {
             farn_launch_init_flow(c->stream, x, set, 0, 0, 0, 0.f, 0.f, 0.f, 1);
         } else {
             const FarnLevelGeom &P = lv[k + 1].g;
@@ -412,7 +434,7 @@ int FarnebackEngine::account(int nb) {
         st.step_launches += (uint64_t)p.farn_num_iters;
         st.level_launches[k] += (uint64_t)p.farn_num_iters;
     }
-    st.algorithmic_bytes += bytes * nb;
+    st.algorithmic_bytes += (bytes + seed_bytes_pair) * nb;
     st.step_algorithmic_bytes += it_bytes * nb;
     st.pairs += (uint64_t)nb;
     st.levels = nlev;

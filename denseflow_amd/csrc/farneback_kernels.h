@@ -81,6 +81,14 @@ void farn_launch_iter_stream(hipStream_t s, const FarnPairCtx &c, int half, int 
 void farn_launch_iter_stream_init(hipStream_t s, const FarnPairCtx &c, int half, int prev_set, int flow_out, float box_inv,
                                   float *merged, long long merged_stride, int prev_w, int prev_h, int prev_pitch, float ifx,
                                   float ify, float up, int zero, const FarnWinTaps *gauss);
+// A caller-supplied initial flow (OPTFLOW_USE_INITIAL_FLOW; DfxSeedIn, dfx_device.h) at the coarsest level:
+// flow = resize_linear(seed, w_k, h_k, ifx, ify) * mul, the seed sw x sh pixels.  The generic path's init launch, and the
+// row-stream path's first iteration with the seed as its input flow (no init launch, no extra plane).
+void farn_launch_init_flow_seed(hipStream_t s, const FarnPairCtx &c, int cur_set, const DfxSeedIn &seed, int sw, int sh,
+                                float ifx, float ify, float mul);
+void farn_launch_iter_stream_seed(hipStream_t s, const FarnPairCtx &c, int half, int flow_out, float box_inv, float *merged,
+                                  long long merged_stride, const DfxSeedIn &seed, int sw, int sh, float ifx, float ify, float mul,
+                                  const FarnWinTaps *gauss);
 void farn_launch_merge(hipStream_t s, const FarnPairCtx &c, int flow_set, float *out, long long out_stride);
 // Planar output (DfxPlanarOut, dfx_device.h).  The last iteration of level 0 in the row-stream form, when it is not also
 // the level's first: the new flow goes to the caller's u and v planes, bounded.

@@ -349,6 +349,24 @@ __global__ __launch_bounds__(256) void k_farn_init_flow(FarnPairCtx c, int cur_s
     }
 }
 
+// k_farn_init_flow's third source (OPTFLOW_USE_INITIAL_FLOW, the coarsest level only): the caller's W x H initial flow,
+// flow = resize_linear(seed, w_k, h_k, ifx, ify) * (float)scale_k.  A kernel of its own, so that k_farn_init_flow stays
+// the code it was for calls without a seed.
+__global__ __launch_bounds__(256) void k_farn_init_flow_seed(FarnPairCtx c, int cur_set, DfxSeedIn seed, int sw, int sh,
+                                                             float ifx, float ify, float mul) {
+    const DfxBlockXY blk = dfx_block_xy();
+    const int x = blk.x * 64 + (threadIdx.x & 63);
+    const int y = blk.y * 4 + (threadIdx.x >> 6);
+    if (x >= c.L.w || y >= c.L.h)
+        return;
+    const int b = blockIdx.z;
+    const long long o = (long long)y * c.L.pitch + x, pb = (long long)b * seed.pair_stride;
+    farn_plane(c, b, FARN_PL_FX0 + 2 * cur_set)[o] =
+        dfx_seed_resize_px(seed.u + pb, sw, sh, seed.row_pitch, seed.step, x, y, ifx, ify) * mul;
+    farn_plane(c, b, FARN_PL_FY0 + 2 * cur_set)[o] =
+        dfx_seed_resize_px(seed.v + pb, sw, sh, seed.row_pitch, seed.step, x, y, ifx, ify) * mul;
+}
+
 __constant__ float c_farn_border[6] = {0.14f, 0.14f, 0.4472f, 0.4472f, 0.4472f, 1.f};
 
 // 8-byte load with 4-byte alignment: the two horizontal taps of a bilinear sample
@@ -915,10 +933,13 @@ constexpr int farn_stream_wps(int half, bool planar) { return (half <= 6 || (!pl
 // ring, the warm-up passes, the work split and the segments are the box form's.  The body is shared; the box kernels
 // (k_farn_iter_stream) and the Gaussian kernels (k_farn_gauss_stream) are separate __global__ functions, so the box
 // kernels stay the code they were.
-template <int HALF, bool INIT, bool PLANAR, bool GAUSS>
+// SEED (with INIT, the coarsest level of a seeded call): the input flow is the caller's initial flow through
+// resize_linear_px_f's expression with the seed's strides, times (float)scale_k (init.up; init.prev_w x prev_h = the
+// seed's W x H) — no extra launch, no extra plane.  Instantiations of their own (k_farn_seed_stream, k_farn_gauss_seed_stream).
+template <int HALF, bool INIT, bool PLANAR, bool GAUSS, bool SEED = false>
 __device__ __forceinline__ void farn_stream_body(const FarnPairCtx &c, int flow_in, int flow_out, float box_inv, int seg_rows,
                                                  float *merged, long long merged_stride, const FarnInit &init,
-                                                 const DfxPlanarOut &po, const FarnWinTaps &wt) {
+                                                 const DfxPlanarOut &po, const FarnWinTaps &wt, const DfxSeedIn *seed = nullptr) {
     // WARM: rows of the window above its first output row and below its last; NP: column pairs per row (38 at HALF 6)
     constexpr int TW = 64, IW = TW + 2 * HALF, RB = 6, WARM = 2 * HALF, RING = RB + WARM, NP = IW / 2;
     static_assert(HALF >= 3 && HALF <= 10 && RB * NP <= 256 && IW <= 96 && 2 * 96 + NP <= 256 && RB * (TW / 2) <= 256,
@@ -958,7 +979,14 @@ __device__ __forceinline__ void farn_stream_body(const FarnPairCtx &c, int flow_
             return farn_ld2u(base, byte_off);
     };
     auto load_flow = [&](int gy, f2 &dx, f2 &dy) {
-        if (INIT) {
+        if constexpr (SEED) {
+            const long long pb = (long long)b * seed->pair_stride;
+            const float *su = seed->u + pb, *sv = seed->v + pb;
+            dx = farn_f2(dfx_seed_resize_px(su, init.prev_w, init.prev_h, seed->row_pitch, seed->step, gx[0], gy, init.ifx, init.ify) * init.up,
+                         dfx_seed_resize_px(su, init.prev_w, init.prev_h, seed->row_pitch, seed->step, gx[1], gy, init.ifx, init.ify) * init.up);
+            dy = farn_f2(dfx_seed_resize_px(sv, init.prev_w, init.prev_h, seed->row_pitch, seed->step, gx[0], gy, init.ifx, init.ify) * init.up,
+                         dfx_seed_resize_px(sv, init.prev_w, init.prev_h, seed->row_pitch, seed->step, gx[1], gy, init.ifx, init.ify) * init.up);
+        } else if (INIT) {
             if (init.zero) {
                 dx = dy = farn_f2(0.f, 0.f);
             } else {
@@ -1226,6 +1254,24 @@ __global__ __launch_bounds__(256, farn_gauss_wps(HALF, PLANAR)) void k_farn_gaus
     farn_stream_body<HALF, INIT, PLANAR, true>(c, flow_in, flow_out, 0.f, seg_rows, merged, merged_stride, init, po, wt);
 }
 
+// The coarsest level's first iteration of a seeded call (SEED above): the box and the Gaussian window.
+// Three waves per SIMD for every window, as a choice: the launch runs once per call on the smallest level, so occupancy
+// buys nothing, and the 168-register budget leaves the strided taps room beside INIT's state (no scratch in any window).
+template <int HALF>
+__global__ __launch_bounds__(256, 3) void k_farn_seed_stream(FarnPairCtx c, int flow_out, float box_inv, int seg_rows,
+                                                                                float *merged, long long merged_stride, FarnInit init,
+                                                                                DfxSeedIn seed) {
+    farn_stream_body<HALF, true, false, false, true>(c, flow_out ^ 1, flow_out, box_inv, seg_rows, merged, merged_stride, init,
+                                                     DfxPlanarOut{}, FarnWinTaps{}, &seed);
+}
+template <int HALF>
+__global__ __launch_bounds__(256, 3) void k_farn_gauss_seed_stream(FarnPairCtx c, int flow_out, int seg_rows, float *merged,
+                                                                                     long long merged_stride, FarnInit init,
+                                                                                     DfxSeedIn seed, FarnWinTaps wt) {
+    farn_stream_body<HALF, true, false, true, true>(c, flow_out ^ 1, flow_out, 0.f, seg_rows, merged, merged_stride, init,
+                                                    DfxPlanarOut{}, wt, &seed);
+}
+
 __global__ __launch_bounds__(256) void k_farn_merge(FarnPairCtx c, int flow_set, float *out, long long out_stride) {
     const int x = blockIdx.x * 64 + (threadIdx.x & 63);
     const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
@@ -1382,6 +1428,50 @@ void farn_launch_iter_stream_init(hipStream_t s, const FarnPairCtx &c, int half,
     FarnInit in;
     in.zero = zero, in.prev_w = prev_w, in.prev_h = prev_h, in.prev_pitch = prev_pitch, in.ifx = ifx, in.ify = ify, in.up = up;
     farn_stream_launch<true, false>(s, c, half, prev_set, flow_out, box_inv, merged, merged_stride, in, DfxPlanarOut{}, gauss);
+}
+
+void farn_launch_init_flow_seed(hipStream_t s, const FarnPairCtx &c, int cur_set, const DfxSeedIn &seed, int sw, int sh,
+                                float ifx, float ify, float mul) {
+    hipLaunchKernelGGL(k_farn_init_flow_seed, grid64x4(c.L.w, c.L.h, c.n_pairs), dim3(256), 0, s, c, cur_set, seed, sw, sh, ifx,
+                       ify, mul);
+}
+
+void farn_launch_iter_stream_seed(hipStream_t s, const FarnPairCtx &c, int half, int flow_out, float box_inv, float *merged,
+                                  long long merged_stride, const DfxSeedIn &seed, int sw, int sh, float ifx, float ify, float mul,
+                                  const FarnWinTaps *gauss) {
+    FarnInit in;
+    in.zero = 0, in.prev_w = sw, in.prev_h = sh, in.prev_pitch = 0, in.ifx = ifx, in.ify = ify, in.up = mul;
+    const int seg_rows = farn_stream_seg_rows(c.L.w, c.L.h, c.n_pairs, half);
+    const dim3 grid((c.L.w + 63) / 64, (c.L.h + seg_rows - 1) / seg_rows, c.n_pairs);
+    if (gauss) {
+        void (*g)(FarnPairCtx, int, int, float *, long long, FarnInit, DfxSeedIn, FarnWinTaps) = nullptr;
+        switch (half) {
+        case 3: g = k_farn_gauss_seed_stream<3>; break;
+        case 4: g = k_farn_gauss_seed_stream<4>; break;
+        case 5: g = k_farn_gauss_seed_stream<5>; break;
+        case 6: g = k_farn_gauss_seed_stream<6>; break;
+        case 7: g = k_farn_gauss_seed_stream<7>; break;
+        case 8: g = k_farn_gauss_seed_stream<8>; break;
+        case 9: g = k_farn_gauss_seed_stream<9>; break;
+        case 10: g = k_farn_gauss_seed_stream<10>; break;
+        default: std::abort();
+        }
+        hipLaunchKernelGGL(g, grid, dim3(256), 0, s, c, flow_out, seg_rows, merged, merged_stride, in, seed, *gauss);
+        return;
+    }
+    void (*k)(FarnPairCtx, int, float, int, float *, long long, FarnInit, DfxSeedIn) = nullptr;
+    switch (half) {
+    case 3: k = k_farn_seed_stream<3>; break;
+    case 4: k = k_farn_seed_stream<4>; break;
+    case 5: k = k_farn_seed_stream<5>; break;
+    case 6: k = k_farn_seed_stream<6>; break;
+    case 7: k = k_farn_seed_stream<7>; break;
+    case 8: k = k_farn_seed_stream<8>; break;
+    case 9: k = k_farn_seed_stream<9>; break;
+    case 10: k = k_farn_seed_stream<10>; break;
+    default: std::abort();
+    }
+    hipLaunchKernelGGL(k, grid, dim3(256), 0, s, c, flow_out, box_inv, seg_rows, merged, merged_stride, in, seed);
 }
 
 void farn_launch_merge(hipStream_t s, const FarnPairCtx &c, int flow_set, float *out, long long out_stride) {

@@ -35,7 +35,8 @@ class Tvl1Engine final : public AlgoEngine {
     int frame_slots() const override { return n_frame_slots; }
     int build_frames(const unsigned char *d_src, long long src_frame_stride, long long src_pitch, int n,
                      const int *h_slots) override;
-    int run_pairs(int nb, const PairDesc *h_pairs, float *d_out, long long out_stride, const DfxPlanarOut *planar) override;
+    int run_pairs(int nb, const PairDesc *h_pairs, float *d_out, long long out_stride, const DfxPlanarOut *planar,
+                  const DfxSeedIn *seed) override;
     int account(int nb) override;
     int batch_tables(int max_pairs, int *iters, int *checks) const override;
 
@@ -90,6 +91,7 @@ class Tvl1Engine final : public AlgoEngine {
     bool warp_head = false;  // the warp kernel also runs the head of the loop it starts (k_tvl1_warp_head)
     int launched_steps[DFX_LVL_MAX] = {0};
     int last_nb = 0; // pairs of the batch whose read-backs h_iters / h_checks hold (set by account)
+    double seed_bytes_pair = 0; // bytes per pair the seed chain of the batch in flight moved (0: no seed; folded in by account)
 
     Tvl1LoopCfg loop{};
     Tvl1Consts kc{};
@@ -397,8 +399,10 @@ int Tvl1Engine::steps_per_group(int s, int nb) const {
     return std::max(min_group, std::min(16, g));
 }
 
-int Tvl1Engine::run_pairs(int nb, const PairDesc *h_pairs, float *d_out, long long out_stride, const DfxPlanarOut *planar) {
+int Tvl1Engine::run_pairs(int nb, const PairDesc *h_pairs, float *d_out, long long out_stride, const DfxPlanarOut *planar,
+                          const DfxSeedIn *seed) {
     last_nb = 0; // the read-backs below overwrite the last batch's tables
+    seed_bytes_pair = 0;
     std::memcpy(h_pairs_pinned, h_pairs, sizeof(PairDesc) * nb);
     HIPCHK(c, hipMemcpyAsync(d_pairs, h_pairs_pinned, sizeof(PairDesc) * nb, hipMemcpyHostToDevice, c->stream));
     const int impl = c->prm.impl, math = c->prm.tvl1_math;
@@ -407,11 +411,40 @@ int Tvl1Engine::run_pairs(int nb, const PairDesc *h_pairs, float *d_out, long lo
     const float up = (float)(1.0 / c->prm.tvl1_scale_step);
     const int hard_limit = loop.warps * (loop.iterations + 2) + 64;
 
+    if (seed) {
+        // The caller's initial flows down to the coarsest level (tvl1_seed_kernels.hip): one launch per pyramid step, the
+        // first one reading the caller's rows, the others ping-ponging between the u plane sets so that the last one
+        // writes set 0.  One level: the seed as it is.
+        Tvl1SeedStep q;
+        std::memset(&q, 0, sizeof q);
+        if (nlevels == 1) {
+            q.src = *seed, q.sw = lv[0].w, q.sh = lv[0].h, q.dst_set = 0, q.copy = 1;
+            tvl1_launch_seed_step(c->stream, level_ctx(0, nb), q);
+            seed_bytes_pair += 16.0 * lv[0].w * lv[0].h;
+        }
+        for (int s = 1; s < nlevels; ++s) {
+            const Level &S = lv[s - 1], &D = lv[s];
+            const Tvl1LevelCtx xd = level_ctx(s, nb);
+            q.dst_set = (nlevels - 1 - s) & 1;
+            q.src = s == 1 ? *seed : tvl1_seed_from_planes(xd, q.dst_set ^ 1, S.pitch);
+            q.sw = S.w, q.sh = S.h;
+            q.ifx = (float)(1.0 / ((double)D.w / (double)S.w));
+            q.ify = (float)(1.0 / ((double)D.h / (double)S.h));
+            q.mul = (float)c->prm.tvl1_scale_step;
+            tvl1_launch_seed_step(c->stream, xd, q);
+            seed_bytes_pair += 40.0 * D.w * D.h; // per pixel and channel: four taps read, one value written
+        }
+        c->stats.kernel_launches += (uint64_t)std::max(1, nlevels - 1);
+    }
     for (int s = nlevels - 1; s >= 0; --s) {
         Tvl1LevelCtx x = level_ctx(s, nb);
         x.done_token = ++done_token;
-        tvl1_launch_level_begin(c->stream, x, s == nlevels - 1);
-        c->stats.kernel_launches += (warp_head && s != nlevels - 1) ? 1 : 2;
+        const bool first = s == nlevels - 1;
+        if (first && seed)
+            tvl1_launch_level_begin_seeded(c->stream, x); // u is the chain's, in set 0
+        else
+            tvl1_launch_level_begin(c->stream, x, first);
+        c->stats.kernel_launches += (warp_head && !(first && !seed)) ? 1 : 2;
         if (gamma_on) {
             tvl1_launch_level_begin_gamma(c->stream, x, s == nlevels - 1);
             c->stats.kernel_launches += 1;
@@ -512,6 +545,7 @@ int Tvl1Engine::account(int nb) {
             st.algorithmic_bytes += px * (it_b * (double)it + 44.0 * loop.warps + lvl_b);
             st.step_algorithmic_bytes += px * (it_b * (double)it + 44.0 * loop.warps);
         }
+        st.algorithmic_bytes += seed_bytes_pair;
         st.pairs += 1;
     }
     last_nb = nb;

@@ -15,6 +15,21 @@ void tvl1_launch_centered_gradient(hipStream_t s, const float *frame_I, float *f
                                    long long frame_stride, const int *frame_slots, int n_frames, long long off, int w,
                                    int h, int pitch);
 void tvl1_launch_level_begin(hipStream_t s, const Tvl1LevelCtx &c, int first_level);
+// A caller-supplied initial flow (tvl1_seed_kernels.hip): one step of the chain that carries it to the coarsest level.
+// The launch's context describes the destination level; u1 / u2 of plane set dst_set = resize_linear(src, ifx, ify) * mul,
+// or (copy: a one-level pyramid) the source as it is.
+struct Tvl1SeedStep {
+    DfxSeedIn src; // the caller's seed (first step) or the finer level's u planes (tvl1_seed_from_planes)
+    int sw, sh;    // geometry of the source
+    int dst_set;
+    float ifx, ify, mul;
+    int copy;
+};
+void tvl1_launch_seed_step(hipStream_t s, const Tvl1LevelCtx &c_dst, const Tvl1SeedStep &q);
+DfxSeedIn tvl1_seed_from_planes(const Tvl1LevelCtx &c, int set, int pitch);
+// tvl1_launch_level_begin of the coarsest level when the seed chain has left u in plane set 0: the state machine is armed
+// on that set and u is not zeroed (p is, unless the warp-and-head kernel takes it as zero)
+void tvl1_launch_level_begin_seeded(hipStream_t s, const Tvl1LevelCtx &c);
 void tvl1_launch_warp(hipStream_t s, const Tvl1LevelCtx &c, int step_id); // dedicated backward-warp kernel of a step
 // the warp AND the head of the loop it starts (tvl1_head_kernels.hip), in place of tvl1_launch_warp
 // (regs: its register form of round 6, DFX_VAR_TVL1_HEAD_NBR_LDS)

@@ -988,6 +988,17 @@ void tvl1_launch_level_begin(hipStream_t s, const Tvl1LevelCtx &c, int first_lev
         hipLaunchKernelGGL(k_tvl1_zero_planes, grid_for(c.pitch, c.h, c.n_pairs), dim3(256), 0, s, c, first_level);
 }
 
+// The coarsest level behind a seed chain (tvl1_seed_kernels.hip), which ends in plane set 0: cur = 0 as at any first level,
+// u stays what the chain wrote, and only p is zeroed (first_level = 0 for k_tvl1_zero_planes; nothing with c.head).
+// The chain writes columns x < w only: the u planes' padding columns (w <= x < pitch) hold what earlier launches left there,
+// as they do at every finer level behind k_tvl1_upsample_u — unlike the unseeded first level, where k_tvl1_zero_planes
+// clears them.  No kernel reads them as data; nothing may come to rely on zeroed padding at the first level.
+void tvl1_launch_level_begin_seeded(hipStream_t s, const Tvl1LevelCtx &c) {
+    hipLaunchKernelGGL(k_tvl1_level_begin, dim3((c.n_pairs + 63) / 64), dim3(64), 0, s, c, 1);
+    if (!c.head)
+        hipLaunchKernelGGL(k_tvl1_zero_planes, grid_for(c.pitch, c.h, c.n_pairs), dim3(256), 0, s, c, 0);
+}
+
 int tvl1_fused_max_k() { return FT_TH / 2 - 4; } // owned region stays >= 8 rows tall
 extern "C" int dfxi_tvl1_fused_max_k() { return tvl1_fused_max_k(); } // test hook, not part of the ABI: the tests sweep up to it
 

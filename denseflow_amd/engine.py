@@ -182,6 +182,13 @@ def load_library():
         L.dfx_calc_batch_planar.restype = i
         L.dfx_calc_batch_planar_device.argtypes = [vp, vp, sz, sz, i, i, C.c_double, vp, sz, sz, sz]
         L.dfx_calc_batch_planar_device.restype = i
+    if hasattr(L, "dfx_calc_batch_init"):  # a library built before the initial flows (DFX_LIBRARY A/B) still loads
+        L.dfx_calc_batch_init.argtypes = [vp, C.POINTER(vp), sz, i, i, C.POINTER(vp), sz, C.POINTER(vp), sz]
+        L.dfx_calc_batch_init.restype = i
+        L.dfx_calc_batch_init_device.argtypes = [vp, vp, sz, sz, i, i, vp, sz, vp, sz]
+        L.dfx_calc_batch_init_device.restype = i
+        L.dfx_calc_batch_planar_init_device.argtypes = [vp, vp, sz, sz, i, i, C.c_double, vp, vp, sz, sz, sz]
+        L.dfx_calc_batch_planar_init_device.restype = i
     L.dfx_calc_batch_u8.argtypes = [vp, C.POINTER(vp), sz, i, i, C.c_double, C.c_double, C.POINTER(vp), C.POINTER(vp), sz]
     L.dfx_calc_batch_u8.restype = i
     L.dfx_submit_batch.argtypes = [vp, C.POINTER(vp), sz, i, i, C.POINTER(vp), sz, C.POINTER(C.c_uint64)]
@@ -461,8 +468,28 @@ class FlowEngine:
                                                   (C.c_size_t * cnt)(*pitches), len(seg), ch))
 
     # -- the hot path ------------------------------------------------------------------------
-    def calc(self, frame_a: np.ndarray, frame_b: np.ndarray) -> np.ndarray:
-        """alg->calc(a, b): one (H, W, 2) float32 flow, channel 0 = u (x), 1 = v (y)."""
+    def _seeds_in(self, init, m: int):
+        """The initial flows of a host-pointer call: m (H, W, 2) float32 arrays with dense pixels and one common row pitch
+        (views with padded rows are taken as they are).  Returns (arrays, pitch in bytes)."""
+        seeds = []
+        for s in init:
+            s = np.asarray(s)
+            ok = s.dtype == np.float32 and s.shape == (self.height, self.width, 2) and s.strides[1:] == (8, 4)
+            seeds.append(s if ok else np.ascontiguousarray(s, dtype=np.float32))
+        if len(seeds) != m or any(s.shape != (self.height, self.width, 2) for s in seeds):
+            raise ValueError("init must hold one (H, W, 2) float32 flow per output flow")
+        pitch = seeds[0].strides[0] if seeds and self.height > 1 else self.width * 8
+        if any(self.height > 1 and s.strides[0] != pitch for s in seeds):
+            seeds = [np.ascontiguousarray(s) for s in seeds]
+            pitch = self.width * 8
+        return seeds, pitch
+
+    def calc(self, frame_a: np.ndarray, frame_b: np.ndarray, init: np.ndarray | None = None) -> np.ndarray:
+        """alg->calc(a, b): one (H, W, 2) float32 flow, channel 0 = u (x), 1 = v (y).
+        init: an (H, W, 2) float32 flow in pixels to start from (TVL1's useInitialFlow, Farneback's
+        OPTFLOW_USE_INITIAL_FLOW; dfx_calc_batch_init with the two frames) instead of zero."""
+        if init is not None:
+            return self.calc_optflows([frame_a, frame_b], 1, init=[init])[0]
         a = np.ascontiguousarray(frame_a, dtype=np.uint8)
         b = np.ascontiguousarray(frame_b, dtype=np.uint8)
         if a.shape != self._frame_shape() or b.shape != a.shape:
@@ -472,8 +499,9 @@ class FlowEngine:
                                      out.ctypes.data, out.strides[0]))
         return out
 
-    def calc_optflows(self, frames_gray, step: int):
-        """The loop of DenseFlow::calc_optflows_imp (src/denseflow_gpu.cpp:307-342) for one FlowBuffer."""
+    def calc_optflows(self, frames_gray, step: int, init=None):
+        """The loop of DenseFlow::calc_optflows_imp (src/denseflow_gpu.cpp:307-342) for one FlowBuffer.
+        init: one (H, W, 2) float32 initial flow per output flow, in output order (dfx_calc_batch_init)."""
         frames = self._frames_in(frames_gray)
         n = len(frames)
         m = self._num_pairs(n, step)
@@ -483,6 +511,17 @@ class FlowEngine:
         self._check_shapes(frames)
         fp = (C.c_void_p * n)(*[f.ctypes.data for f in frames])
         op = (C.c_void_p * m)(*[f.ctypes.data for f in flows])
+        if init is not None:
+            try:
+                seeds, ipitch = self._seeds_in(init, m)
+            except ValueError:
+                self._armed_seg = self._armed_src = None
+                raise
+            ip = (C.c_void_p * m)(*[s.ctypes.data for s in seeds])
+            self._arm()
+            self._check(self._L.dfx_calc_batch_init(self._h, fp, frames[0].strides[0], n, int(step), ip, ipitch, op,
+                                                    self.width * 8))
+            return flows
         self._arm()
         self._check(self._L.dfx_calc_batch(self._h, fp, frames[0].strides[0], n, int(step), op, self.width * 8))
         return flows
@@ -518,10 +557,20 @@ class FlowEngine:
         self._check(self._L.dfx_wait(self._h, int(ticket)))
 
     def calc_optflows_device(self, d_frames_ptr: int, pitch: int, frame_stride: int, n_frames: int, step: int,
-                             d_flows_ptr: int, flow_stride_floats: int):
-        """Frames and flows already resident in HBM (raw device pointers, e.g. torch .data_ptr())."""
+                             d_flows_ptr: int, flow_stride_floats: int, init: int | None = None,
+                             init_stride_floats: int | None = None):
+        """Frames and flows already resident in HBM (raw device pointers, e.g. torch .data_ptr()).
+        init: device pointer of the initial flows, in the layout of the flows (dfx_calc_batch_init_device), flow i at
+        init + i * init_stride_floats (default: flow_stride_floats); it may be d_flows_ptr itself with the same stride —
+        refinement in place."""
         self._num_pairs(n_frames, step)
         self._arm()
+        if init is not None:
+            self._check(self._L.dfx_calc_batch_init_device(
+                self._h, d_frames_ptr, pitch, frame_stride, n_frames, int(step), init,
+                flow_stride_floats if init_stride_floats is None else int(init_stride_floats), d_flows_ptr,
+                flow_stride_floats))
+            return
         self._check(self._L.dfx_calc_batch_device(self._h, d_frames_ptr, pitch, frame_stride, n_frames, int(step),
                                                   d_flows_ptr, flow_stride_floats))
 
@@ -555,7 +604,7 @@ class FlowEngine:
                                                          0.0 if bound is None else float(bound), d_out_ptr,
                                                          row_pitch_floats, plane_stride_floats, flow_stride_floats))
 
-    def flow_tensor(self, frames, step: int, bound: float | None = None, out=None):
+    def flow_tensor(self, frames, step: int, bound: float | None = None, out=None, init=None):
         """Flows of a FlowBuffer of torch frames as an (M, 2, H, W) float32 torch tensor on the same device, the layout
         (and, with bound, the [-1, 1] scaling) a two-stream / TSN / I3D network takes: no pointer handling, no permute
         pass, no clamp-and-divide pass.
@@ -566,6 +615,10 @@ class FlowEngine:
         out: optional (M, 2, H, W) float32 tensor on that device to write into, any strides with a contiguous innermost
         dimension that do not make rows, planes or flows overlap; otherwise the result is allocated.
         bound None: raw flow values, bit for bit those of calc_optflows; bound > 0: clamp(x, -bound, bound) / bound.
+        init: optional (M, 2, H, W) float32 tensor on that device, the initial flow of every output flow in raw pixels
+        (whatever bound is; dfx_calc_batch_planar_init_device).  The library reads it with the strides of `out`: without
+        `out` any strides are accepted (a contiguous copy is made if needed); with `out` it must have out's strides, and it
+        may be `out` itself (refinement in place).
 
         Streams: torch's current stream on that device is synchronised before the call, so frames produced on it just
         before are complete; the library call returns with all its device work complete, so the result may be used on
@@ -606,6 +659,15 @@ class FlowEngine:
                 raise ValueError("out: the innermost dimension must be contiguous and rows, planes and flows must not overlap")
         if dev.type != "cuda" or (dev.index is not None and dev.index != getattr(self, "_device", dev.index)):
             raise ValueError("frames must be on this handle's device")
+        if init is not None:
+            if not isinstance(init, torch.Tensor) or init.dtype != torch.float32 or init.device != dev:
+                raise ValueError("init must be a torch.float32 tensor on the frames' device")
+            if tuple(init.shape) != want:
+                raise ValueError(f"init must have shape {want}")
+            if out is None:
+                init = init.contiguous()
+            elif init.stride() != out.stride():
+                raise ValueError("init must have the strides of out")
         if out is None:
             out = torch.empty(want, dtype=torch.float32, device=dev)
             row_pitch, plane_stride = self.width, self.height * self.width
@@ -613,6 +675,12 @@ class FlowEngine:
         self._num_pairs(n, step)
         torch.cuda.current_stream(dev).synchronize()
         self._arm()
+        if init is not None and m:  # (no output flow: nothing to seed)
+            self._check(self._L.dfx_calc_batch_planar_init_device(
+                self._h, frames.data_ptr() if n else None, pitch, frame_stride, n, int(step),
+                0.0 if bound is None else float(bound), init.data_ptr(), out.data_ptr() if m else None, row_pitch,
+                plane_stride, flow_stride))
+            return out
         self._check(self._L.dfx_calc_batch_planar_device(self._h, frames.data_ptr() if n else None, pitch, frame_stride, n,
                                                          int(step), 0.0 if bound is None else float(bound),
                                                          out.data_ptr() if m else None, row_pitch, plane_stride,

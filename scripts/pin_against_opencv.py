@@ -15,8 +15,11 @@ DEFINES its algorithm, gets its first external check.  opencv_farn_gaussian.npz 
 (dfx_params.farn_window, restated from memory and rated MED): winSize 15 with OPTFLOW_FARNEBACK_GAUSSIAN, picked up by
 tests/test_opencv_pin_farn_gaussian.py.  opencv_tvl1_gamma.npz is the illumination channel of TVL1 (dfx_params.tvl1_gamma,
 restated from memory and rated MED): cuda.OpticalFlowDual_TVL1_create(gamma=0.4) and gamma=2.0 on the two smallest seeds
-(the file stays below the 1 MiB a committed fixture may have), picked up by tests/test_opencv_pin_tvl1_gamma.py.  Nothing
-here imports the product or the oracle.
+(the file stays below the 1 MiB a committed fixture may have), picked up by tests/test_opencv_pin_tvl1_gamma.py.
+opencv_tvl1_init.npz / opencv_farn_init.npz are the caller-supplied initial flows (dfx_calc_batch_init*, restated from memory
+and rated MED): OpticalFlowDual_TVL1 with useInitialFlow = true and FarnebackOpticalFlow with OPTFLOW_USE_INITIAL_FLOW on
+the two smallest seeds, each seeded with that case's own unseeded OpenCV flow scaled by 0.5 (stored beside the result),
+picked up by tests/test_opencv_pin_initial_flow.py.  Nothing here imports the product or the oracle.
 
     python scripts/pin_against_opencv.py [--out tests/golden] [--testdata $OPENCV_TEST_DATA_PATH]
 With --testdata the upstream fixtures SURVEY.md §4 names are added as cases: cv/optflow/RubberWhale1.png / 2.png
@@ -93,6 +96,20 @@ def main():
             blob[f"{name}_gamma{gamma}_flow"] = flow.astype(np.float32)
             print("tvl1_gamma", gamma, name, flow.shape, float(np.abs(flow).max()))
     np.savez_compressed(os.path.join(args.out, "opencv_tvl1_gamma.npz"), **blob)
+    # caller-supplied initial flows: the flow argument of calc is read as the seed (and overwritten with the result)
+    seeded = {
+        "tvl1": lambda: cv2.cuda_OpticalFlowDual_TVL1.create(0.25, 0.15, 0.3, 5, 5, 0.01, 300, 0.8, 0.0, True),
+        "farn": lambda: cv2.cuda_FarnebackOpticalFlow.create(5, 0.5, False, 13, 10, 5, 1.1, cv2.OPTFLOW_USE_INITIAL_FLOW),
+    }
+    for algo, make in seeded.items():
+        blob = {"build_information": np.array(info), "opencv_version": np.array(cv2.__version__)}
+        for name, a, b in pairs[:2]:
+            seed = (algos[algo](a, b).astype(np.float32) * np.float32(0.5)).astype(np.float32)
+            flow = make().calc(up(a), up(b), up(seed.copy())).download()
+            blob[name + "_f0"], blob[name + "_f1"] = a, b
+            blob[name + "_seed"], blob[name + "_flow"] = seed, flow.astype(np.float32)
+            print(algo + "_init", name, flow.shape, float(np.abs(flow).max()))
+        np.savez_compressed(os.path.join(args.out, f"opencv_{algo}_init.npz"), **blob)
     if hasattr(cv2, "optflow") and hasattr(cv2.optflow, "DualTVL1OpticalFlow_create"):  # the CPU comparator
         blob = {"build_information": np.array(info), "opencv_version": np.array(cv2.__version__)}
         for name, a, b in pairs[:3]:
