@@ -41,6 +41,7 @@ void default_params(dfx_params *p) {
     p->farn_poly_sigma = 1.1;
     p->farn_flags = 0;
     p->farn_window = DFX_FARN_WINDOW_BOX;
+    p->farn_fast_pyramids = 0;
     // cuda::BroxOpticalFlow::create(0.197f, 50.0f, 0.8f, 10, 77, 10): src/denseflow_gpu.cpp:303
     p->brox_alpha = 0.197f;
     p->brox_gamma = 50.0f;

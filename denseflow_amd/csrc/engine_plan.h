@@ -107,6 +107,11 @@ struct FarnPlan {
     int batch = 0;
     size_t per_pair = 0;
     bool bad_kernel = false; // a level's Gaussian kernel size is not odd and positive
+    // dfx_params.farn_fast_pyramids: a level below the coarsest has an odd width or height (upstream's pyrUp of the level
+    // above it is then not this level's size: no result defined); fast_max_levels = the largest farn_num_levels this size
+    // accepts
+    bool odd_level = false;
+    int fast_max_levels = 0;
 };
 
 // B.6: cv::getGaussianKernel(ksize, sigma, CV_32F); returns taps centre-first (k[0] = centre)
@@ -163,6 +168,16 @@ inline bool farn_window_taps(int win_size, FarnWinTaps &out) {
     return true;
 }
 
+// dfx_params.farn_fast_pyramids: level k is pyrDown of level k - 1, ((w + 1) / 2, (h + 1) / 2) of its size,
+// and the flow climbs by pyrUp, which doubles a size: every level below the coarsest must be even both ways.  Returns the
+// number of leading levels (from level 0) with even width and height — the largest level count a size accepts.
+inline int farn_fast_even_levels(int W, int H) {
+    int n = 0;
+    for (int w = W, h = H; n < DFX_LVL_MAX && !(w & 1) && !(h & 1); w = (w + 1) / 2, h = (h + 1) / 2)
+        ++n;
+    return n;
+}
+
 // planes_per_slot: float planes of a pair slot (4 with M on chip, FARN_PL_COUNT otherwise: farneback_kernels.h)
 inline void farn_plan(FarnPlan &pl, int W, int H, const dfx_params &p, int planes_per_slot) {
     pl = FarnPlan();
@@ -181,27 +196,37 @@ inline void farn_plan(FarnPlan &pl, int W, int H, const dfx_params &p, int plane
     long long off = 0;
     for (int k = 0; k < DFX_LVL_MAX; ++k)
         pl.lv[k] = FarnPlanLevel{0, 0, 0, 0, 0.0, 0, 0, 0.f, 0.f};
+    if (p.farn_fast_pyramids) {
+        pl.fast_max_levels = farn_fast_even_levels(W, H);
+        pl.odd_level = cropped > pl.fast_max_levels;
+    }
+    int fw = W, fh = H; // the (n + 1) / 2 chain of farn_fast_pyramids
     for (int k = 0; k < pl.nlev; ++k) {
-        scale = 1;
-        for (int i = 0; i < k; i++)
-            scale *= p.farn_pyr_scale;
         FarnPlanLevel &L = pl.lv[k];
-        L.sigma = (1. / scale - 1) * 0.5;
-        int smooth = dfx_plan_round(L.sigma * 5) | 1;
-        smooth = std::max(smooth, 3);
-        L.half = smooth / 2;
-        L.w = dfx_plan_round(W * scale);
-        L.h = dfx_plan_round(H * scale);
+        if (p.farn_fast_pyramids) { // level k is pyrDown of level k - 1; no Gaussian pre-blur, hence no sigma, smoothSize or taps
+            L.w = fw, L.h = fh;
+            fw = (fw + 1) / 2, fh = (fh + 1) / 2;
+        } else {
+            scale = 1;
+            for (int i = 0; i < k; i++)
+                scale *= p.farn_pyr_scale;
+            L.sigma = (1. / scale - 1) * 0.5;
+            int smooth = dfx_plan_round(L.sigma * 5) | 1;
+            smooth = std::max(smooth, 3);
+            L.half = smooth / 2;
+            L.w = dfx_plan_round(W * scale);
+            L.h = dfx_plan_round(H * scale);
+            std::vector<float> taps;
+            if (!farn_gaussian_taps(smooth, L.sigma, taps))
+                pl.bad_kernel = true;
+            L.ker_off = (int)pl.taps.size();
+            pl.taps.insert(pl.taps.end(), taps.begin(), taps.end());
+        }
         L.pitch = dfx_round_up(L.w, 64);
         L.r_off = off;
         off += 5LL * L.pitch * L.h;
         L.ifx = (float)(1.0 / ((double)L.w / (double)W)); // dsize given (E.1)
         L.ify = (float)(1.0 / ((double)L.h / (double)H));
-        std::vector<float> taps;
-        if (!farn_gaussian_taps(smooth, L.sigma, taps))
-            pl.bad_kernel = true;
-        L.ker_off = (int)pl.taps.size();
-        pl.taps.insert(pl.taps.end(), taps.begin(), taps.end());
     }
     pl.frame_elems = off;
     pl.plane_stride = (long long)pl.pitch0 * H;

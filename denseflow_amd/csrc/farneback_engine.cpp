@@ -108,6 +108,7 @@ class FarnebackEngine final : public AlgoEngine {
     bool m_on_chip = true;                        // the default iteration kernel (M recomputed, never in HBM)
     double seed_bytes_pair = 0;                   // bytes per pair the seed's resize of the batch in flight read (0: no seed)
     bool gauss_window = false;                    // dfx_params.farn_window: Gaussian taps in place of the box filter
+    bool fast_pyr = false;                        // dfx_params.farn_fast_pyramids: pyrDown frame pyramids, pyrUp flows (B.13)
     FarnWinTaps win_taps{};
 
     int B = 0;
@@ -155,6 +156,11 @@ int FarnebackEngine::create() {
     if (p.farn_num_levels < 0 || p.farn_num_levels >= DFX_LVL_MAX || p.farn_num_iters < 1 ||
         !(p.farn_pyr_scale > 0.0 && p.farn_pyr_scale < 1.0))
         return dfx_fail(c, DFX_ERR_INVALID, "invalid Farneback parameters");
+    if (p.farn_fast_pyramids != 0 && p.farn_fast_pyramids != 1)
+        return dfx_fail(c, DFX_ERR_INVALID, "Farneback: farn_fast_pyramids must be 0 or 1");
+    fast_pyr = p.farn_fast_pyramids == 1;
+    if (fast_pyr && p.farn_pyr_scale != 0.5)
+        return dfx_fail(c, DFX_ERR_INVALID, "Farneback: farn_fast_pyramids needs farn_pyr_scale = 0.5 (pyrDown halves a level)");
 
     prepare_poly(p.farn_poly_n, p.farn_poly_sigma, &pc);
     // the Gaussian update window's taps follow from the parameters alone: set_size leaves them alone
@@ -184,6 +190,14 @@ int FarnebackEngine::set_size(int W, int H) {
     farn_plan(pl, W, H, c->prm, m_on_chip ? (int)FARN_PL_M0 : (int)FARN_PL_COUNT);
     if (pl.bad_kernel)
         return dfx_fail(c, DFX_ERR_INVALID, "Farneback: bad Gaussian kernel size");
+    if (pl.odd_level) { // refused before anything is allocated: the handle stays at the size it had
+        char msg[256];
+        snprintf(msg, sizeof msg,
+                 "Farneback: farn_fast_pyramids needs even level sizes below the coarsest level (pyrUp doubles a size); "
+                 "%d x %d accepts farn_num_levels up to %d",
+                 W, H, pl.fast_max_levels);
+        return dfx_fail(c, DFX_ERR_UNSUPPORTED, msg);
+    }
     size_t free_b = 0, total_b = 0;
     HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
     int nB = dfx_plan_fit_batch(pl.batch, pl.per_pair, free_b + device_bytes());
@@ -216,7 +230,8 @@ int FarnebackEngine::set_size(int W, int H) {
         return rc;
     }
     // the context is idle: the taps of the previous size are no longer read
-    HIPCHK(c, hipMemcpy(d_gker, pl.taps.data(), sizeof(float) * pl.taps.size(), hipMemcpyHostToDevice));
+    if (!pl.taps.empty()) // a fast-pyramids handle has none
+        HIPCHK(c, hipMemcpy(d_gker, pl.taps.data(), sizeof(float) * pl.taps.size(), hipMemcpyHostToDevice));
     nlev = pl.nlev;
     for (int k = 0; k < DFX_LVL_MAX; ++k) {
         const FarnPlanLevel &P = pl.lv[k];
@@ -286,6 +301,25 @@ int FarnebackEngine::build_frames(const unsigned char *d_src, long long src_fram
     std::memcpy(h_slots_pinned, h_slots, sizeof(int) * n);
     HIPCHK(c, hipMemcpyAsync(d_frame_slots, h_slots_pinned, sizeof(int) * n, hipMemcpyHostToDevice, c->stream));
     const int W = c->W, H = c->H;
+    if (fast_pyr) {
+        // B.13, walking UP the pyramid: level 0 is the frame as float, level k one pyrDown of level k - 1.  The levels
+        // alternate between d_pyr and the first plane of a frame's d_tmpv pair; level 1 reads the 8-bit frame itself.
+        farn_launch_u8_to_f32(c->stream, d_src, src_frame_stride, src_pitch, n, d_pyr, plane_stride, W, H, pitch0);
+        for (int k = 0; k < nlev; ++k) {
+            const FLevel &L = lv[k];
+            float *cur = (k & 1) ? d_tmpv : d_pyr;
+            const long long cur_stride = (k & 1) ? plane_stride * 2 : plane_stride;
+            if (k == 1)
+                farn_launch_pyrdown_u8(c->stream, d_src, src_frame_stride, src_pitch, n, W, H, cur, cur_stride, L.g.pitch);
+            else if (k > 1)
+                farn_launch_pyrdown(c->stream, (k & 1) ? d_pyr : d_tmpv, (k & 1) ? plane_stride : plane_stride * 2,
+                                    lv[k - 1].g.pitch, n, lv[k - 1].g.w, lv[k - 1].g.h, cur, cur_stride, L.g.pitch);
+            farn_launch_polyexp(c->stream, cur, cur_stride, n, d_frame_slots, d_R, frame_elems, L.g, pc, polyexp_rows,
+                                c->prm.farn_poly_n);
+        }
+        c->stats.kernel_launches += 2 * nlev; // u8 -> f32, nlev - 1 pyrDown, nlev expansions
+        return DFX_OK;
+    }
     // The vertical blur reads the 8-bit frames themselves unless the cross-check form is asked for
     // (DFX_VAR_FARN_EVAL_ZERO_TAPS: the round-1 chain with its separate convertTo pass; same bits either way).
     const bool from_u8 = skip_zero_weights != 0;
@@ -348,6 +382,14 @@ int FarnebackEngine::run_pairs(int nb, const PairDesc *h_pairs, float *d_out, lo
             const FarnLevelGeom P = top ? lv[k].g : lv[k + 1].g;
             const float ifx = top ? 0.f : (float)(1.0 / ((double)x.L.w / (double)P.w));
             const float ify = top ? 0.f : (float)(1.0 / ((double)x.L.h / (double)P.h));
+            // fast pyramids: the coarser level's flow climbs by pyrUp into the other plane set, and the level's first
+            // iteration is a plain launch (or the planar one) on it
+            const bool climbed = fast_pyr && !top;
+            if (climbed) {
+                farn_launch_pyrup_flow(c->stream, x, cur, cur ^ 1, P.w, P.h, P.pitch, up);
+                c->stats.kernel_launches += 1;
+                cur ^= 1;
+            }
             HIPCHK(c, hipEventRecord(ev_it[k][0], c->stream));
             for (int it = 0; it < p.farn_num_iters; ++it) {
                 const bool last = k == 0 && it == p.farn_num_iters - 1;
@@ -361,9 +403,9 @@ int FarnebackEngine::run_pairs(int nb, const PairDesc *h_pairs, float *d_out, lo
                         farn_launch_merge(c->stream, x, cur ^ 1, d_out, out_stride);
                         c->stats.kernel_launches += 1;
                     }
-                } else if (last && planar && it > 0)
+                } else if (last && planar && (it > 0 || climbed))
                     farn_launch_iter_stream_planar(c->stream, x, half, cur, cur ^ 1, box_inv, *planar, gauss);
-                else if (it == 0)
+                else if (it == 0 && !climbed)
                     farn_launch_iter_stream_init(c->stream, x, half, cur, cur ^ 1, box_inv, merged, out_stride, P.w, P.h, P.pitch, ifx,
                                                  ify, up, top ? 1 : 0, gauss);
                 else
@@ -373,7 +415,8 @@ int FarnebackEngine::run_pairs(int nb, const PairDesc *h_pairs, float *d_out, lo
             HIPCHK(c, hipEventRecord(ev_it[k][1], c->stream));
             c->stats.kernel_launches += p.farn_num_iters;
         }
-        if (planar && p.farn_num_iters == 1) { // level 0's only iteration wrote plane set `cur`
+        // level 0's only iteration wrote plane set `cur` — unless it ran on a pyrUp'd flow, as the planar launch itself
+        if (planar && p.farn_num_iters == 1 && !(fast_pyr && nlev > 1)) {
             farn_launch_merge_planar(c->stream, x, cur, *planar);
             c->stats.kernel_launches += 1;
         }
@@ -386,6 +429,9 @@ int FarnebackEngine::run_pairs(int nb, const PairDesc *h_pairs, float *d_out, lo
             farn_launch_init_flow_seed(c->stream, x, set, *seed, c->W, c->H, seed_ifx, seed_ify, (float)seed_scale);
         } else if (k == nlev - 1) {
             farn_launch_init_flow(c->stream, x, set, 0, 0, 0, 0.f, 0.f, 0.f, 1);
+        } else if (fast_pyr) {
+            const FarnLevelGeom &P = lv[k + 1].g;
+            farn_launch_pyrup_flow(c->stream, x, set ^ 1, set, P.w, P.h, P.pitch, up);
         } else {
             const FarnLevelGeom &P = lv[k + 1].g;
             const float ifx = (float)(1.0 / ((double)x.L.w / (double)P.w));
@@ -422,7 +468,10 @@ int FarnebackEngine::account(int nb) {
     double bytes = 34.0 * N0, it_bytes = 0;
     for (int k = 0; k < nlev; ++k) {
         const double Nk = (double)lv[k].g.w * lv[k].g.h;
-        bytes += 2.0 * (8.0 * N0 + 4.0 * std::min(N0, 4.0 * Nk) + 4.0 * Nk + 24.0 * Nk);
+        if (fast_pyr) // per frame: pyrDown reads the level below and writes this one (level 0 is the converted frame), + expansion
+            bytes += 2.0 * ((k > 0 ? 4.0 * lv[k - 1].g.w * lv[k - 1].g.h + 4.0 * Nk : 0.0) + 24.0 * Nk);
+        else
+            bytes += 2.0 * (8.0 * N0 + 4.0 * std::min(N0, 4.0 * Nk) + 4.0 * Nk + 24.0 * Nk);
         bytes += 68.0 * Nk + 16.0 * Nk;
         const double itb = p.farn_num_iters * (40.0 + 28.0) * Nk + (p.farn_num_iters - 1) * 68.0 * Nk;
         bytes += itb;

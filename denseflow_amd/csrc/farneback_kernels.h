@@ -95,3 +95,14 @@ void farn_launch_merge(hipStream_t s, const FarnPairCtx &c, int flow_set, float 
 void farn_launch_iter_stream_planar(hipStream_t s, const FarnPairCtx &c, int half, int flow_in, int flow_out, float box_inv,
                                     const DfxPlanarOut &o, const FarnWinTaps *gauss);
 void farn_launch_merge_planar(hipStream_t s, const FarnPairCtx &c, int flow_set, const DfxPlanarOut &o);
+
+// dfx_params.farn_fast_pyramids (farneback_pyramid_kernels.hip)
+// dst = pyrDown(src) for n_frames planes: sw x sh -> (sw + 1) / 2 x (sh + 1) / 2; float planes of pitch src_pitch, or the
+// caller's 8-bit frames themselves
+void farn_launch_pyrdown(hipStream_t s, const float *src, long long src_frame_stride, int src_pitch, int n_frames, int sw,
+                         int sh, float *dst, long long dst_frame_stride, int dst_pitch);
+void farn_launch_pyrdown_u8(hipStream_t s, const unsigned char *src, long long src_frame_stride, long long src_pitch,
+                            int n_frames, int sw, int sh, float *dst, long long dst_frame_stride, int dst_pitch);
+// flow set dst_set of level c.L (2 * prev_w x 2 * prev_h) = pyrUp(flow set src_set of the coarser level) * up
+void farn_launch_pyrup_flow(hipStream_t s, const FarnPairCtx &c, int src_set, int dst_set, int prev_w, int prev_h,
+                            int prev_pitch, float up);

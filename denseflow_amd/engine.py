@@ -64,13 +64,16 @@ class DfxParams(C.Structure):
         ("variant", C.c_int),
         ("step_group", C.c_int),
         ("blocking_sync", C.c_int),
-        ("tvl1_gamma", C.c_double),  # last: a library built before it (DFX_LIBRARY A/B) reads the fields it knows
+        ("tvl1_gamma", C.c_double),
+        ("farn_fast_pyramids", C.c_int),  # last: a library built before it (DFX_LIBRARY A/B) reads the fields it knows
     ]
 
 
 # dfx_params.farn_window (include/dfx.h): FlowEngine(..., "farn", farn_window=FARN_WINDOW_GAUSSIAN) is how upstream's
 # OPTFLOW_FARNEBACK_GAUSSIAN is requested; farn_flags stays refused unless 0
 FARN_WINDOW_BOX, FARN_WINDOW_GAUSSIAN = 0, 1
+# dfx_params.farn_fast_pyramids: FlowEngine(..., "farn", farn_fast_pyramids=1) is upstream's fastPyramids (pyrDown frame pyramids,
+# pyrUp flows); it needs farn_pyr_scale = 0.5 and even level sizes below the coarsest level (DfxError otherwise)
 
 # dfx_params.variant bits (include/dfx.h): cross-check / measurement forms of the tuned kernels, all bit-identical
 VAR_TVL1_CLASSIC_GEOM, VAR_TVL1_WARP_IN_STEP = 0x01, 0x02

@@ -19,7 +19,10 @@ restated from memory and rated MED): cuda.OpticalFlowDual_TVL1_create(gamma=0.4)
 opencv_tvl1_init.npz / opencv_farn_init.npz are the caller-supplied initial flows (dfx_calc_batch_init*, restated from memory
 and rated MED): OpticalFlowDual_TVL1 with useInitialFlow = true and FarnebackOpticalFlow with OPTFLOW_USE_INITIAL_FLOW on
 the two smallest seeds, each seeded with that case's own unseeded OpenCV flow scaled by 0.5 (stored beside the result),
-picked up by tests/test_opencv_pin_initial_flow.py.  Nothing here imports the product or the oracle.
+picked up by tests/test_opencv_pin_initial_flow.py.  opencv_farn_fast_pyramids.npz is fastPyramids
+(dfx_params.farn_fast_pyramids, restated from memory and rated MED): create(3, 0.5, True, 13, 10, 5, 1.1, 0) on the two smallest
+seeds — sizes whose levels below the coarsest are even, the only ones upstream defines a result for — picked up by
+tests/test_opencv_pin_farn_fast_pyramids.py.  Nothing here imports the product or the oracle.
 
     python scripts/pin_against_opencv.py [--out tests/golden] [--testdata $OPENCV_TEST_DATA_PATH]
 With --testdata the upstream fixtures SURVEY.md §4 names are added as cases: cv/optflow/RubberWhale1.png / 2.png
@@ -110,6 +113,26 @@ def main():
             blob[name + "_seed"], blob[name + "_flow"] = seed, flow.astype(np.float32)
             print(algo + "_init", name, flow.shape, float(np.abs(flow).max()))
         np.savez_compressed(os.path.join(args.out, f"opencv_{algo}_init.npz"), **blob)
+    # fastPyramids: pyrDown frame pyramids, pyrUp flows; only sizes whose levels below the coarsest are even both ways
+    def fast_ok(w, h, levels):
+        k, scale = 0, 1.0
+        while k < levels and w * scale * 0.5 >= 32 and h * scale * 0.5 >= 32:  # numLevelsCropped
+            scale *= 0.5
+            k += 1
+        for _ in range(k):
+            if w & 1 or h & 1:
+                return False
+            w, h = (w + 1) // 2, (h + 1) // 2
+        return True
+
+    blob = {"build_information": np.array(info), "opencv_version": np.array(cv2.__version__)}
+    for name, a, b in pairs[:2]:
+        if not fast_ok(a.shape[1], a.shape[0], 3):
+            continue
+        flow = cv2.cuda_FarnebackOpticalFlow.create(3, 0.5, True, 13, 10, 5, 1.1, 0).calc(up(a), up(b), None).download()
+        blob[name + "_f0"], blob[name + "_f1"], blob[name + "_flow"] = a, b, flow.astype(np.float32)
+        print("farn_fast_pyramids", name, flow.shape, float(np.abs(flow).max()))
+    np.savez_compressed(os.path.join(args.out, "opencv_farn_fast_pyramids.npz"), **blob)
     if hasattr(cv2, "optflow") and hasattr(cv2.optflow, "DualTVL1OpticalFlow_create"):  # the CPU comparator
         blob = {"build_information": np.array(info), "opencv_version": np.array(cv2.__version__)}
         for name, a, b in pairs[:3]:
