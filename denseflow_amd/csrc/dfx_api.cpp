@@ -191,8 +191,7 @@ int dfx_set_size(dfx_handle h, int width, int height) {
     h->H = height;
     dfx_pipeline_resized(h);
     dfx_colour_resized(h);
-    h->src_w = h->src_h = 0;
-    h->src_ch = 1;
+    h->default_source();
     return DFX_OK;
 }
 
@@ -228,6 +227,14 @@ inline int abs_step(int step) { return step == INT_MIN ? INT_MAX : std::abs(step
 // is pending (every clip then has its own pitch, checked when it was declared, and the call's is ignored)
 inline bool pitch_too_small(dfx_handle h, size_t frame_pitch) {
     return h->next_seg_fmt.empty() && frame_pitch < h->in_row_bytes();
+}
+// pitch / frame_stride of a device-resident call against the handle's input frames (for a channels-first source: the row
+// pitch of one plane, and three planes src_plane_stride apart that must not overlap)
+inline bool device_frames_too_small(dfx_handle h, size_t pitch, size_t frame_stride) {
+    if (pitch < h->in_row_bytes())
+        return true;
+    const size_t span = h->in_frame_span(pitch);
+    return span == 0 || frame_stride < span;
 }
 // the device-resident forms have one format for the whole array
 inline bool src_segments_pending(dfx_handle h) { return !h->next_seg_fmt.empty(); }
@@ -411,7 +418,7 @@ int dfx_calc_batch_device(dfx_handle h, const uint8_t *d_frames, size_t pitch, s
     const int M = std::max(n_frames - abs_step(step), 0);
     if (M > 0 && (!d_frames || !d_flows))
         return dfx_fail(h, DFX_ERR_INVALID, "NULL device frames or flows");
-    if (M > 0 && (pitch < h->in_row_bytes() || frame_stride < pitch * (size_t)h->in_h() ||
+    if (M > 0 && (device_frames_too_small(h, pitch, frame_stride) ||
                   flow_stride_floats < (size_t)h->W * h->H * 2))
         return dfx_fail(h, DFX_ERR_INVALID, "pitch/stride smaller than a frame");
     OutSpec out;
@@ -429,34 +436,51 @@ bool planar_bound_ok(double norm_bound) {
     return std::isfinite(norm_bound) && norm_bound > 0.0 && std::isfinite(b) && b > 0.0f;
 }
 const char *const kPlanarBound = "norm_bound must be 0 (raw values) or a positive finite float";
-} // namespace
+const char *const kPlanarDtype = "dtype must be DFX_PLANAR_F32, DFX_PLANAR_F16 or DFX_PLANAR_BF16";
+inline bool planar_dtype_ok(int dtype) { return dtype >= DFX_PLANAR_F32 && dtype <= DFX_PLANAR_BF16; }
+// the stride rules of the device-resident planar forms, in elements.  The products cannot overflow: W, H <= 32768, and a
+// stride that passes the check before it is what the next one multiplies
+inline bool planar_strides_bad(dfx_handle h, size_t row_pitch, size_t plane_stride, size_t flow_stride) {
+    return row_pitch < (size_t)h->W || row_pitch > ((size_t)1 << 40) || plane_stride < (size_t)h->H * row_pitch ||
+           plane_stride > ((size_t)1 << 60) || flow_stride < 2 * plane_stride;
+}
+const char *const kPlanarStrides = "planar output: row_pitch_floats >= W, plane_stride_floats >= H * row_pitch_floats and "
+                                   "flow_stride_floats >= 2 * plane_stride_floats are required";
+const char *const kPlanarStridesAs = "planar output: row_pitch >= W, plane_stride >= H * row_pitch and flow_stride >= 2 * "
+                                     "plane_stride (in elements of dtype) are required";
 
-int dfx_calc_batch_planar(dfx_handle h, const uint8_t *const *frames, size_t frame_pitch, int n_frames, int step,
-                          double norm_bound, float *const *flows_u, float *const *flows_v, size_t out_pitch) {
+// the three planar forms behind their float32 and typed entry points; `typed` only chooses the text of a stride refusal
+int planar_host(dfx_handle h, const uint8_t *const *frames, size_t frame_pitch, int n_frames, int step, double norm_bound,
+                int dtype, void *const *flows_u, void *const *flows_v, size_t out_pitch) {
     if (!h)
         return DFX_ERR_INVALID;
     SegmentsScope seg_scope(h);
+    if (!planar_dtype_ok(dtype))
+        return dfx_fail(h, DFX_ERR_INVALID, kPlanarDtype);
     if (!planar_bound_ok(norm_bound))
         return dfx_fail(h, DFX_ERR_INVALID, kPlanarBound);
     const int M = std::max(n_frames - abs_step(step), 0);
     if (M > 0 && (!frames || !flows_u || !flows_v))
         return dfx_fail(h, DFX_ERR_INVALID, "NULL frames or flow plane arrays");
-    if (M > 0 && (pitch_too_small(h, frame_pitch) || out_pitch < (size_t)h->W * 4))
+    if (M > 0 && (pitch_too_small(h, frame_pitch) || out_pitch < (size_t)h->W * dfx_elem_bytes(dtype)))
         return dfx_fail(h, DFX_ERR_INVALID, "pitch smaller than a row");
     OutSpec out;
     out.planar = true;
     out.norm_bound = (float)norm_bound;
+    out.elem = dtype;
     out.flows_u = flows_u, out.flows_v = flows_v;
     out.out_pitch = out_pitch;
     return dfx_run_flowbuffer(h, InSpec::host(frames, frame_pitch), n_frames, step, out, nullptr);
 }
 
-int dfx_calc_batch_planar_device(dfx_handle h, const uint8_t *d_frames, size_t pitch, size_t frame_stride, int n_frames,
-                                 int step, double norm_bound, float *d_out, size_t row_pitch_floats,
-                                 size_t plane_stride_floats, size_t flow_stride_floats) {
+int planar_device(dfx_handle h, const uint8_t *d_frames, size_t pitch, size_t frame_stride, int n_frames, int step,
+                  double norm_bound, int dtype, bool typed, void *d_out, size_t row_pitch, size_t plane_stride,
+                  size_t flow_stride) {
     if (!h)
         return DFX_ERR_INVALID;
     SegmentsScope seg_scope(h);
+    if (!planar_dtype_ok(dtype))
+        return dfx_fail(h, DFX_ERR_INVALID, kPlanarDtype);
     if (src_segments_pending(h))
         return dfx_fail(h, DFX_ERR_UNSUPPORTED, "dfx_next_segments_src applies to host-pointer calls only");
     if (!planar_bound_ok(norm_bound))
@@ -464,21 +488,43 @@ int dfx_calc_batch_planar_device(dfx_handle h, const uint8_t *d_frames, size_t p
     const int M = std::max(n_frames - abs_step(step), 0);
     if (M > 0 && (!d_frames || !d_out))
         return dfx_fail(h, DFX_ERR_INVALID, "NULL device frames or flow planes");
-    if (M > 0 && (pitch < h->in_row_bytes() || frame_stride < pitch * (size_t)h->in_h()))
+    if (M > 0 && device_frames_too_small(h, pitch, frame_stride))
         return dfx_fail(h, DFX_ERR_INVALID, "pitch/stride smaller than a frame");
-    // the products cannot overflow: W, H <= 32768, and a stride that passes the check before it is what the next one multiplies
-    if (M > 0 && (row_pitch_floats < (size_t)h->W || row_pitch_floats > ((size_t)1 << 40) ||
-                  plane_stride_floats < (size_t)h->H * row_pitch_floats || plane_stride_floats > ((size_t)1 << 60) ||
-                  flow_stride_floats < 2 * plane_stride_floats))
-        return dfx_fail(h, DFX_ERR_INVALID,
-                        "planar output: row_pitch_floats >= W, plane_stride_floats >= H * row_pitch_floats and "
-                        "flow_stride_floats >= 2 * plane_stride_floats are required");
+    if (M > 0 && planar_strides_bad(h, row_pitch, plane_stride, flow_stride))
+        return dfx_fail(h, DFX_ERR_INVALID, typed ? kPlanarStridesAs : kPlanarStrides);
     OutSpec out;
     out.planar = true;
     out.norm_bound = (float)norm_bound;
+    out.elem = dtype;
     out.d_planar = d_out;
-    out.d_row_pitch = row_pitch_floats, out.d_plane_stride = plane_stride_floats, out.d_flow_stride = flow_stride_floats;
+    out.d_row_pitch = row_pitch, out.d_plane_stride = plane_stride, out.d_flow_stride = flow_stride;
     return dfx_run_flowbuffer(h, InSpec::device(d_frames, pitch, frame_stride), n_frames, step, out, nullptr);
+}
+} // namespace
+
+int dfx_calc_batch_planar(dfx_handle h, const uint8_t *const *frames, size_t frame_pitch, int n_frames, int step,
+                          double norm_bound, float *const *flows_u, float *const *flows_v, size_t out_pitch) {
+    return planar_host(h, frames, frame_pitch, n_frames, step, norm_bound, DFX_PLANAR_F32, (void *const *)flows_u,
+                       (void *const *)flows_v, out_pitch);
+}
+
+int dfx_calc_batch_planar_as(dfx_handle h, const uint8_t *const *frames, size_t frame_pitch, int n_frames, int step,
+                             double norm_bound, int dtype, void *const *flows_u, void *const *flows_v, size_t out_pitch) {
+    return planar_host(h, frames, frame_pitch, n_frames, step, norm_bound, dtype, flows_u, flows_v, out_pitch);
+}
+
+int dfx_calc_batch_planar_device(dfx_handle h, const uint8_t *d_frames, size_t pitch, size_t frame_stride, int n_frames,
+                                 int step, double norm_bound, float *d_out, size_t row_pitch_floats,
+                                 size_t plane_stride_floats, size_t flow_stride_floats) {
+    return planar_device(h, d_frames, pitch, frame_stride, n_frames, step, norm_bound, DFX_PLANAR_F32, false, d_out,
+                         row_pitch_floats, plane_stride_floats, flow_stride_floats);
+}
+
+int dfx_calc_batch_planar_as_device(dfx_handle h, const uint8_t *d_frames, size_t pitch, size_t frame_stride, int n_frames,
+                                    int step, double norm_bound, int dtype, void *d_out, size_t row_pitch,
+                                    size_t plane_stride, size_t flow_stride) {
+    return planar_device(h, d_frames, pitch, frame_stride, n_frames, step, norm_bound, dtype, true, d_out, row_pitch,
+                         plane_stride, flow_stride);
 }
 
 // ---- caller-supplied initial flows (TVL1's useInitialFlow, Farneback's OPTFLOW_USE_INITIAL_FLOW) ----
@@ -529,7 +575,7 @@ int dfx_calc_batch_init_device(dfx_handle h, const uint8_t *d_frames, size_t pit
     const int M = std::max(n_frames - abs_step(step), 0);
     if (M > 0 && (!d_frames || !d_flows))
         return dfx_fail(h, DFX_ERR_INVALID, "NULL device frames or flows");
-    if ((M > 0 && (pitch < h->in_row_bytes() || frame_stride < pitch * (size_t)h->in_h() ||
+    if ((M > 0 && (device_frames_too_small(h, pitch, frame_stride) ||
                    flow_stride_floats < (size_t)h->W * h->H * 2)) ||
         init_stride_floats < (size_t)h->W * h->H * 2)
         return dfx_fail(h, DFX_ERR_INVALID, "pitch/stride smaller than a frame");
@@ -541,12 +587,16 @@ int dfx_calc_batch_init_device(dfx_handle h, const uint8_t *d_frames, size_t pit
     return dfx_run_flowbuffer(h, in, n_frames, step, out, nullptr);
 }
 
-int dfx_calc_batch_planar_init_device(dfx_handle h, const uint8_t *d_frames, size_t pitch, size_t frame_stride,
-                                      int n_frames, int step, double norm_bound, const float *d_init, float *d_out,
-                                      size_t row_pitch_floats, size_t plane_stride_floats, size_t flow_stride_floats) {
+namespace {
+int planar_init_device(dfx_handle h, const uint8_t *d_frames, size_t pitch, size_t frame_stride, int n_frames, int step,
+                       double norm_bound, int dtype, bool typed, const float *d_init, size_t init_row_pitch,
+                       size_t init_plane_stride, size_t init_flow_stride, void *d_out, size_t row_pitch, size_t plane_stride,
+                       size_t flow_stride) {
     if (!h)
         return DFX_ERR_INVALID;
     SegmentsScope seg_scope(h);
+    if (!planar_dtype_ok(dtype))
+        return dfx_fail(h, DFX_ERR_INVALID, kPlanarDtype);
     if (const int rc = refuse_seed(h))
         return rc;
     if (src_segments_pending(h))
@@ -558,23 +608,43 @@ int dfx_calc_batch_planar_init_device(dfx_handle h, const uint8_t *d_frames, siz
     const int M = std::max(n_frames - abs_step(step), 0);
     if (M > 0 && (!d_frames || !d_out))
         return dfx_fail(h, DFX_ERR_INVALID, "NULL device frames or flow planes");
-    if (M > 0 && (pitch < h->in_row_bytes() || frame_stride < pitch * (size_t)h->in_h()))
+    if (M > 0 && device_frames_too_small(h, pitch, frame_stride))
         return dfx_fail(h, DFX_ERR_INVALID, "pitch/stride smaller than a frame");
-    if (M > 0 && (row_pitch_floats < (size_t)h->W || row_pitch_floats > ((size_t)1 << 40) ||
-                  plane_stride_floats < (size_t)h->H * row_pitch_floats || plane_stride_floats > ((size_t)1 << 60) ||
-                  flow_stride_floats < 2 * plane_stride_floats))
+    if (M > 0 && planar_strides_bad(h, row_pitch, plane_stride, flow_stride))
+        return dfx_fail(h, DFX_ERR_INVALID, typed ? kPlanarStridesAs : kPlanarStrides);
+    if (M > 0 && planar_strides_bad(h, init_row_pitch, init_plane_stride, init_flow_stride))
         return dfx_fail(h, DFX_ERR_INVALID,
-                        "planar output: row_pitch_floats >= W, plane_stride_floats >= H * row_pitch_floats and "
-                        "flow_stride_floats >= 2 * plane_stride_floats are required");
+                        "initial flows: init_row_pitch >= W, init_plane_stride >= H * init_row_pitch and init_flow_stride >= "
+                        "2 * init_plane_stride (in floats) are required");
     OutSpec out;
     out.planar = true;
     out.norm_bound = (float)norm_bound;
+    out.elem = dtype;
     out.d_planar = d_out;
-    out.d_row_pitch = row_pitch_floats, out.d_plane_stride = plane_stride_floats, out.d_flow_stride = flow_stride_floats;
+    out.d_row_pitch = row_pitch, out.d_plane_stride = plane_stride, out.d_flow_stride = flow_stride;
     InSpec in = InSpec::device(d_frames, pitch, frame_stride);
-    in.d_init = d_init, in.init_planar = true; // the seed's planes have the three strides of d_out
-    in.d_init_stride = flow_stride_floats, in.d_init_row_pitch = row_pitch_floats, in.d_init_plane_stride = plane_stride_floats;
+    in.d_init = d_init, in.init_planar = true;
+    in.d_init_stride = init_flow_stride, in.d_init_row_pitch = init_row_pitch, in.d_init_plane_stride = init_plane_stride;
     return dfx_run_flowbuffer(h, in, n_frames, step, out, nullptr);
+}
+} // namespace
+
+int dfx_calc_batch_planar_init_device(dfx_handle h, const uint8_t *d_frames, size_t pitch, size_t frame_stride,
+                                      int n_frames, int step, double norm_bound, const float *d_init, float *d_out,
+                                      size_t row_pitch_floats, size_t plane_stride_floats, size_t flow_stride_floats) {
+    // the seed's planes have the three strides of d_out
+    return planar_init_device(h, d_frames, pitch, frame_stride, n_frames, step, norm_bound, DFX_PLANAR_F32, false, d_init,
+                              row_pitch_floats, plane_stride_floats, flow_stride_floats, d_out, row_pitch_floats,
+                              plane_stride_floats, flow_stride_floats);
+}
+
+int dfx_calc_batch_planar_as_init_device(dfx_handle h, const uint8_t *d_frames, size_t pitch, size_t frame_stride,
+                                         int n_frames, int step, double norm_bound, int dtype, const float *d_init,
+                                         size_t init_row_pitch, size_t init_plane_stride, size_t init_flow_stride,
+                                         void *d_out, size_t row_pitch, size_t plane_stride, size_t flow_stride) {
+    return planar_init_device(h, d_frames, pitch, frame_stride, n_frames, step, norm_bound, dtype, true, d_init,
+                              init_row_pitch, init_plane_stride, init_flow_stride, d_out, row_pitch, plane_stride,
+                              flow_stride);
 }
 
 int dfx_calc_batch_png_device(dfx_handle h, const uint8_t *d_frames, size_t pitch, size_t frame_stride, int n_frames,
@@ -588,7 +658,7 @@ int dfx_calc_batch_png_device(dfx_handle h, const uint8_t *d_frames, size_t pitc
     const int M = std::max(n_frames - abs_step(step), 0);
     if (M > 0 && (!d_frames || !d_img_x || !d_img_y || !d_bounds_xy))
         return dfx_fail(h, DFX_ERR_INVALID, "NULL device frames, image planes or bounds");
-    if (M > 0 && (pitch < h->in_row_bytes() || frame_stride < pitch * (size_t)h->in_h() || img_pitch < (size_t)h->W ||
+    if (M > 0 && (device_frames_too_small(h, pitch, frame_stride) || img_pitch < (size_t)h->W ||
                   img_stride < img_pitch * (size_t)h->H))
         return dfx_fail(h, DFX_ERR_INVALID, "pitch/stride smaller than a frame");
     OutSpec out;
@@ -725,7 +795,7 @@ int dfx_calc_batch_u8_device(dfx_handle h, const uint8_t *d_frames, size_t pitch
     const int M = std::max(n_frames - abs_step(step), 0);
     if (M > 0 && (!d_frames || !d_img_x || !d_img_y))
         return dfx_fail(h, DFX_ERR_INVALID, "NULL device frames or image planes");
-    if (M > 0 && (pitch < h->in_row_bytes() || frame_stride < pitch * (size_t)h->in_h() || img_pitch < (size_t)h->W ||
+    if (M > 0 && (device_frames_too_small(h, pitch, frame_stride) || img_pitch < (size_t)h->W ||
                   img_stride < img_pitch * (size_t)h->H))
         return dfx_fail(h, DFX_ERR_INVALID, "pitch/stride smaller than a frame");
     OutSpec out;
@@ -787,32 +857,54 @@ int dfx_flow_to_png_device(dfx_handle h, const float *d_flows, size_t flow_strid
     return DFX_OK;
 }
 
-int dfx_set_source_format(dfx_handle h, int src_width, int src_height, int channels) {
+namespace {
+// order / layout of a colour source (DFX_SRC_*); a gray source has neither
+const char *source_layout_error(int channels, int order, int layout, size_t plane_stride) {
+    if ((order != DFX_SRC_BGR && order != DFX_SRC_RGB) || (layout != DFX_SRC_INTERLEAVED && layout != DFX_SRC_PLANAR))
+        return "order must be DFX_SRC_BGR or DFX_SRC_RGB, layout DFX_SRC_INTERLEAVED or DFX_SRC_PLANAR";
+    if (channels == 1 && (order != 0 || layout != 0 || plane_stride != 0))
+        return "a gray source (channels = 1) has no channel order, layout or plane_stride";
+    if (layout != DFX_SRC_PLANAR && plane_stride != 0)
+        return "plane_stride applies to DFX_SRC_PLANAR only";
+    return nullptr;
+}
+} // namespace
+
+int dfx_set_source_format_ex(dfx_handle h, int src_width, int src_height, int channels, int order, int layout,
+                             size_t plane_stride) {
     if (!h)
         return DFX_ERR_INVALID;
     if (src_width == 0 && src_height == 0) { // back to the default: W x H gray frames
-        h->src_w = h->src_h = 0;
-        h->src_ch = 1;
+        h->default_source();
         return DFX_OK;
     }
     if (src_width < 1 || src_height < 1 || src_width > 32768 || src_height > 32768)
         return dfx_fail(h, DFX_ERR_INVALID, "invalid source frame size");
     if (channels != 1 && channels != 3)
         return dfx_fail(h, DFX_ERR_INVALID, "channels must be 1 (gray) or 3 (BGR)");
+    if (const char *why = source_layout_error(channels, order, layout, plane_stride))
+        return dfx_fail(h, DFX_ERR_INVALID, why);
+    if (plane_stride != 0 && plane_stride < (size_t)src_width * src_height)
+        return dfx_fail(h, DFX_ERR_INVALID, "plane_stride smaller than a plane");
     if (src_width == h->W && src_height == h->H && channels == 1) {
-        h->src_w = h->src_h = 0;
-        h->src_ch = 1;
+        h->default_source();
         return DFX_OK;
     }
     h->src_w = src_width;
     h->src_h = src_height;
     h->src_ch = channels;
+    h->src_rgb = order == DFX_SRC_RGB, h->src_planar = layout == DFX_SRC_PLANAR;
+    h->src_plane_stride = plane_stride;
     return DFX_OK;
 }
 
-int dfx_prepare_frames_device(dfx_handle h, const uint8_t *d_src, size_t src_pitch, size_t src_frame_stride,
-                              int src_width, int src_height, int channels, int n, uint8_t *d_gray, size_t gray_pitch,
-                              size_t gray_frame_stride) {
+int dfx_set_source_format(dfx_handle h, int src_width, int src_height, int channels) {
+    return dfx_set_source_format_ex(h, src_width, src_height, channels, DFX_SRC_BGR, DFX_SRC_INTERLEAVED, 0);
+}
+
+int dfx_prepare_frames_layout_device(dfx_handle h, const uint8_t *d_src, size_t src_pitch, size_t src_frame_stride,
+                                     size_t plane_stride, int src_width, int src_height, int channels, int order,
+                                     int layout, int n, uint8_t *d_gray, size_t gray_pitch, size_t gray_frame_stride) {
     if (!h)
         return DFX_ERR_INVALID;
     (void)dfx_finish_tails(h, 0, -1);
@@ -824,19 +916,32 @@ int dfx_prepare_frames_device(dfx_handle h, const uint8_t *d_src, size_t src_pit
         return dfx_fail(h, DFX_ERR_INVALID, "NULL device frames");
     if (src_width < 1 || src_height < 1 || (channels != 1 && channels != 3))
         return dfx_fail(h, DFX_ERR_INVALID, "invalid source format");
-    if (src_pitch < (size_t)src_width * channels || src_frame_stride < src_pitch * (size_t)src_height ||
-        gray_pitch < (size_t)h->W || gray_frame_stride < gray_pitch * (size_t)h->H)
+    if (const char *why = source_layout_error(channels, order, layout, plane_stride))
+        return dfx_fail(h, DFX_ERR_INVALID, why);
+    const bool planar = layout == DFX_SRC_PLANAR;
+    const size_t one = src_pitch * (size_t)src_height, ps = plane_stride ? plane_stride : one;
+    if (src_pitch < (size_t)src_width * (planar ? 1 : channels) || (planar && ps < one) ||
+        src_frame_stride < (planar ? 2 * ps + one : one) || gray_pitch < (size_t)h->W ||
+        gray_frame_stride < gray_pitch * (size_t)h->H)
         return dfx_fail(h, DFX_ERR_INVALID, "pitch/stride smaller than a frame");
     HIPCHK(h, hipSetDevice(h->device));
     prepare_launch(h->stream, d_src, (long long)src_pitch, (long long)src_frame_stride, src_width, src_height, channels,
-                   n, d_gray, (long long)gray_pitch, (long long)gray_frame_stride, h->W, h->H);
+                   n, d_gray, (long long)gray_pitch, (long long)gray_frame_stride, h->W, h->H, order == DFX_SRC_RGB, planar,
+                   (long long)ps);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return DFX_OK;
 }
 
-int dfx_prepare_frames(dfx_handle h, const uint8_t *const *src, size_t src_pitch, int src_width, int src_height,
-                       int channels, int n, uint8_t *const *gray, size_t gray_pitch) {
+int dfx_prepare_frames_device(dfx_handle h, const uint8_t *d_src, size_t src_pitch, size_t src_frame_stride,
+                              int src_width, int src_height, int channels, int n, uint8_t *d_gray, size_t gray_pitch,
+                              size_t gray_frame_stride) {
+    return dfx_prepare_frames_layout_device(h, d_src, src_pitch, src_frame_stride, 0, src_width, src_height, channels,
+                                            DFX_SRC_BGR, DFX_SRC_INTERLEAVED, n, d_gray, gray_pitch, gray_frame_stride);
+}
+
+int dfx_prepare_frames_layout(dfx_handle h, const uint8_t *const *src, size_t src_pitch, int src_width, int src_height,
+                              int channels, int order, int layout, int n, uint8_t *const *gray, size_t gray_pitch) {
     if (!h)
         return DFX_ERR_INVALID;
     (void)dfx_finish_tails(h, 0, -1);
@@ -848,7 +953,12 @@ int dfx_prepare_frames(dfx_handle h, const uint8_t *const *src, size_t src_pitch
         return dfx_fail(h, DFX_ERR_INVALID, "NULL frame arrays");
     if (src_width < 1 || src_height < 1 || (channels != 1 && channels != 3))
         return dfx_fail(h, DFX_ERR_INVALID, "invalid source format");
-    const size_t rb = (size_t)src_width * channels, fb = rb * src_height, plane = (size_t)h->W * h->H;
+    if (const char *why = source_layout_error(channels, order, layout, 0))
+        return dfx_fail(h, DFX_ERR_INVALID, why);
+    // a channels-first frame goes up as 3 * src_height dense rows of src_width bytes
+    const bool planar = layout == DFX_SRC_PLANAR;
+    const int rows = planar ? 3 * src_height : src_height;
+    const size_t rb = (size_t)src_width * (planar ? 1 : channels), fb = rb * rows, plane = (size_t)h->W * h->H;
     if (src_pitch < rb || gray_pitch < (size_t)h->W)
         return dfx_fail(h, DFX_ERR_INVALID, "pitch smaller than a row");
     HIPCHK(h, hipSetDevice(h->device));
@@ -860,10 +970,10 @@ int dfx_prepare_frames(dfx_handle h, const uint8_t *const *src, size_t src_pitch
         for (int i0 = 0; i0 < n; i0 += chunk) {
             const int m = std::min(chunk, n - i0);
             for (int j = 0; j < m; ++j)
-                HIPCHK(h, hipMemcpy2DAsync(d_in + (size_t)j * fb, rb, src[i0 + j], src_pitch, rb, src_height,
+                HIPCHK(h, hipMemcpy2DAsync(d_in + (size_t)j * fb, rb, src[i0 + j], src_pitch, rb, rows,
                                            hipMemcpyHostToDevice, h->stream));
             prepare_launch(h->stream, d_in, (long long)rb, (long long)fb, src_width, src_height, channels, m, d_out,
-                           h->W, (long long)plane, h->W, h->H);
+                           h->W, (long long)plane, h->W, h->H, order == DFX_SRC_RGB, planar, 0);
             HIPCHK(h, hipGetLastError());
             for (int j = 0; j < m; ++j)
                 HIPCHK(h, hipMemcpy2DAsync(gray[i0 + j], gray_pitch, d_out + (size_t)j * plane, h->W, h->W, h->H,
@@ -876,6 +986,12 @@ int dfx_prepare_frames(dfx_handle h, const uint8_t *const *src, size_t src_pitch
     dfx_free_dev(d_in);
     dfx_free_dev(d_out);
     return rc;
+}
+
+int dfx_prepare_frames(dfx_handle h, const uint8_t *const *src, size_t src_pitch, int src_width, int src_height,
+                       int channels, int n, uint8_t *const *gray, size_t gray_pitch) {
+    return dfx_prepare_frames_layout(h, src, src_pitch, src_width, src_height, channels, DFX_SRC_BGR, DFX_SRC_INTERLEAVED,
+                                     n, gray, gray_pitch);
 }
 
 int dfx_get_stats(dfx_handle h, dfx_stats *out) {

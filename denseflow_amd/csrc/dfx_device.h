@@ -91,19 +91,26 @@ struct Tvl1LevelCtx {
 static inline int dfx_round_up(int v, int m) { return (v + m - 1) / m * m; }
 
 // ------------------------------------------------------------------------------------------------
-// Planar float output (dfx_calc_batch_planar*): flow i of a launch is a u plane at base + i * flow_stride and a v plane
-// plane_stride floats behind it, rows row_pitch floats apart — the [M, 2, H, W] layout of a tensor consumer.  Every
-// engine's last writer stores both planes itself (dfx_planar_store*), the bound applied in the same store.
+// Planar output (dfx_calc_batch_planar*): flow i of a launch is a u plane at base + i * flow_stride and a v plane
+// plane_stride elements behind it, rows row_pitch elements apart — the [M, 2, H, W] layout of a tensor consumer.  Every
+// engine's last writer stores both planes itself (dfx_planar_store*), the bound applied in the same store.  The elements
+// are float32, or (dfx_calc_batch_planar_as*) float16 / bfloat16: the float32 value converted once in that store.
+enum : int { DFX_ELEM_F32 = 0, DFX_ELEM_F16 = 1, DFX_ELEM_BF16 = 2 }; // = DFX_PLANAR_F32 / _F16 / _BF16 of include/dfx.h
+DFX_HD int dfx_elem_bytes(int elem) { return elem == DFX_ELEM_F32 ? 4 : 2; }
 struct DfxPlanarOut {
-    float *base;                                    // u plane of the launch's first flow
-    long long flow_stride, plane_stride, row_pitch; // in floats
+    void *base;                                     // u plane of the launch's first flow
+    long long flow_stride, plane_stride, row_pitch; // in elements
     float bound;                                    // 0: raw values; b > 0: clamp(x, -b, b) / b
-    int vec;                                        // floats per store that base and all three strides keep aligned: 4, 2 or 1
+    int vec;                                        // elements per store that base and all three strides keep aligned: 4, 2 or 1
+    int elem;                                       // DFX_ELEM_*: one value per launch, so every branch on it is wave-uniform
 };
-static inline int dfx_planar_vec(const float *base, long long flow_stride, long long plane_stride, long long row_pitch) {
-    const unsigned long long bits = (unsigned long long)(size_t)base | ((unsigned long long)flow_stride * 4) |
-                                    ((unsigned long long)plane_stride * 4) | ((unsigned long long)row_pitch * 4);
-    return (bits & 15) == 0 ? 4 : (bits & 7) == 0 ? 2 : 1;
+// 4 elements in one store (16 bytes of float32, 8 bytes of a half type), 2 (8 / 4 bytes), or single elements
+static inline int dfx_planar_vec(const void *base, long long flow_stride, long long plane_stride, long long row_pitch,
+                                 int elem_bytes = 4) {
+    const unsigned long long e = (unsigned long long)elem_bytes;
+    const unsigned long long bits = (unsigned long long)(size_t)base | ((unsigned long long)flow_stride * e) |
+                                    ((unsigned long long)plane_stride * e) | ((unsigned long long)row_pitch * e);
+    return (bits & (4 * e - 1)) == 0 ? 4 : (bits & (2 * e - 1)) == 0 ? 2 : 1;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -131,6 +138,7 @@ DFX_HD int dfx_xcd_tile_index(int lin, int nt) {
     return k * q + (k < rem ? k : rem) + (lin >> 3);
 }
 #if defined(__HIPCC__)
+#include <hip/hip_bf16.h>
 // Bilinear sample of a strided source at destination pixel (dx, dy): the pyramid resize of both engines (SURVEY.md E.1 —
 // no half-pixel centring, upstream's accumulation order; resize_linear_px / resize_linear_px_f with neighbouring pixels
 // `step` floats apart and rows `spitch` floats).  The one place the seed kernels of both engines take it from: the order of
@@ -157,16 +165,58 @@ __device__ __forceinline__ float dfx_planar_value(float x, float b) {
         x = x != x ? 0.0f : __builtin_fminf(__builtin_fmaxf(x, -b), b) / b;
     return x;
 }
+// The 16 bits a half plane holds for the float32 value y: ONE conversion, round to nearest even — float16 with
+// subnormals, +-inf from 65520 on and signed zeros; bfloat16 the rounded upper half of y, a carry may reach inf.  Plain
+// casts: the compiler selects the conversion instructions.
+__device__ __forceinline__ unsigned short dfx_planar_half_bits(float y, int elem) {
+    if (elem == DFX_ELEM_F16) {
+        const _Float16 hv = (_Float16)y;
+        return __builtin_bit_cast(unsigned short, hv);
+    }
+    const __hip_bfloat16 bv = __float2bfloat16(y);
+    return __builtin_bit_cast(unsigned short, bv);
+}
+// n = 1..4 values that are already dfx_planar_value()s to elements p .. p + n - 1 of a half plane (p at a multiple of 4
+// elements of its row): one 8-byte store, 4-byte stores for aligned pairs, single elements otherwise.
+__device__ __forceinline__ void dfx_planar_put_half(unsigned short *p, int vec, int n, const float (&a)[4], int elem) {
+    unsigned short q[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        q[k] = dfx_planar_half_bits(a[k], elem);
+    if (vec == 4 && n == 4) {
+        *reinterpret_cast<uint2 *>(p) = make_uint2((unsigned)q[0] | ((unsigned)q[1] << 16), (unsigned)q[2] | ((unsigned)q[3] << 16));
+        return;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; k += 2) {
+        if (vec >= 2 && k + 1 < n) {
+            *reinterpret_cast<unsigned *>(p + k) = (unsigned)q[k] | ((unsigned)q[k + 1] << 16);
+        } else {
+            if (k < n)
+                p[k] = q[k];
+            if (k + 1 < n)
+                p[k + 1] = q[k + 1];
+        }
+    }
+}
 // Pixels x .. x + n - 1 (x a multiple of 4, n = 1..4) of row y of flow i, u and v each to its plane: one 16-byte store per
-// plane where o.vec and n allow, 8-byte stores for aligned pairs, single floats otherwise (odd widths, unaligned pitches).
+// plane where o.vec and n allow, 8-byte stores for aligned pairs, single floats otherwise (odd widths, unaligned pitches);
+// the half types the same at half the bytes.
 __device__ __forceinline__ void dfx_planar_store4(const DfxPlanarOut &o, int i, int x, int y, int n, const float (&u)[4],
                                                   const float (&v)[4]) {
-    float *du = o.base + (long long)i * o.flow_stride + (long long)y * o.row_pitch + x;
-    float *dv = du + o.plane_stride;
+    const long long at = (long long)i * o.flow_stride + (long long)y * o.row_pitch + x;
     float a[4], c[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k)
         a[k] = dfx_planar_value(u[k], o.bound), c[k] = dfx_planar_value(v[k], o.bound);
+    if (o.elem != DFX_ELEM_F32) {
+        unsigned short *hu = static_cast<unsigned short *>(o.base) + at;
+        dfx_planar_put_half(hu, o.vec, n, a, o.elem);
+        dfx_planar_put_half(hu + o.plane_stride, o.vec, n, c, o.elem);
+        return;
+    }
+    float *du = static_cast<float *>(o.base) + at;
+    float *dv = du + o.plane_stride;
     if (o.vec == 4 && n == 4) {
         *reinterpret_cast<float4 *>(du) = make_float4(a[0], a[1], a[2], a[3]);
         *reinterpret_cast<float4 *>(dv) = make_float4(c[0], c[1], c[2], c[3]);
@@ -188,10 +238,26 @@ __device__ __forceinline__ void dfx_planar_store4(const DfxPlanarOut &o, int i, 
 // The same for a lane that holds two pixels (x even, n = 1 or 2).
 __device__ __forceinline__ void dfx_planar_store2(const DfxPlanarOut &o, int i, int x, int y, int n, float u0, float u1,
                                                   float v0, float v1) {
-    float *du = o.base + (long long)i * o.flow_stride + (long long)y * o.row_pitch + x;
-    float *dv = du + o.plane_stride;
+    const long long at = (long long)i * o.flow_stride + (long long)y * o.row_pitch + x;
     const float a0 = dfx_planar_value(u0, o.bound), a1 = dfx_planar_value(u1, o.bound);
     const float c0 = dfx_planar_value(v0, o.bound), c1 = dfx_planar_value(v1, o.bound);
+    if (o.elem != DFX_ELEM_F32) {
+        unsigned short *hu = static_cast<unsigned short *>(o.base) + at;
+        unsigned short *hv = hu + o.plane_stride;
+        const unsigned short p0 = dfx_planar_half_bits(a0, o.elem), p1 = dfx_planar_half_bits(a1, o.elem);
+        const unsigned short q0 = dfx_planar_half_bits(c0, o.elem), q1 = dfx_planar_half_bits(c1, o.elem);
+        if (o.vec >= 2 && n == 2) {
+            *reinterpret_cast<unsigned *>(hu) = (unsigned)p0 | ((unsigned)p1 << 16);
+            *reinterpret_cast<unsigned *>(hv) = (unsigned)q0 | ((unsigned)q1 << 16);
+            return;
+        }
+        hu[0] = p0, hv[0] = q0;
+        if (n == 2)
+            hu[1] = p1, hv[1] = q1;
+        return;
+    }
+    float *du = static_cast<float *>(o.base) + at;
+    float *dv = du + o.plane_stride;
     if (o.vec >= 2 && n == 2) {
         *reinterpret_cast<float2 *>(du) = make_float2(a0, a1);
         *reinterpret_cast<float2 *>(dv) = make_float2(c0, c1);

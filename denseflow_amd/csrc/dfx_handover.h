@@ -25,9 +25,11 @@ struct DfxCodedPlane { // what the device reports per coded plane / frame
 struct DfxHandover {
     // rows: dst_a.size() pairs in `block` (null: none).  Float: pair j is H rows of W (u, v) pairs at j * W * H * 8 -> dst_a[j].
     // Two u8 planes: x plane j at j * W * H -> dst_a[j], y plane j at (pairs + j) * W * H -> dst_b[j].
-    // Float planes: u plane of pair j at j * W * H * 8 -> dst_a[j], its v plane W * H * 4 bytes behind -> dst_b[j].
+    // Float planes: u plane of pair j at j * W * H * 2 * elem_bytes -> dst_a[j], its v plane W * H * elem_bytes behind ->
+    // dst_b[j] (elem_bytes: 4, or 2 for float16 / bfloat16 planes).
     const unsigned char *block = nullptr;
     bool two_planes = false, float_planes = false;
+    size_t elem_bytes = 4;
     int W = 0, H = 0;
     size_t pitch = 0; // bytes per destination row
     std::vector<void *> dst_a, dst_b;
@@ -64,8 +66,9 @@ inline int dfx_hand_over(const DfxHandover &h, std::string *err) {
     const size_t plane = (size_t)h.W * h.H, nb = h.dst_a.size();
     for (size_t j = 0; h.block && j < nb; ++j) {
         if (h.float_planes) {
-            dfx_copy_rows(h.dst_a[j], h.pitch, h.block + j * plane * 8, (size_t)h.W * 4, (size_t)h.W * 4, h.H);
-            dfx_copy_rows(h.dst_b[j], h.pitch, h.block + j * plane * 8 + plane * 4, (size_t)h.W * 4, (size_t)h.W * 4, h.H);
+            const size_t e = h.elem_bytes, rb = (size_t)h.W * e;
+            dfx_copy_rows(h.dst_a[j], h.pitch, h.block + j * plane * 2 * e, rb, rb, h.H);
+            dfx_copy_rows(h.dst_b[j], h.pitch, h.block + j * plane * 2 * e + plane * e, rb, rb, h.H);
         } else if (h.two_planes) {
             dfx_copy_rows(h.dst_a[j], h.pitch, h.block + j * plane, (size_t)h.W, (size_t)h.W, h.H);
             dfx_copy_rows(h.dst_b[j], h.pitch, h.block + (nb + j) * plane, (size_t)h.W, (size_t)h.W, h.H);

@@ -97,10 +97,25 @@ struct dfx_context {
     }
     // format of the frames handed to the calc entry points (dfx_set_source_format); 0 = the handle's own W x H gray
     int src_w = 0, src_h = 0, src_ch = 1;
+    // a colour source's channel order and layout (dfx_set_source_format_ex): R, G, B instead of B, G, R; three byte planes
+    // src_plane_stride bytes apart (0: pitch * src_h, the only value the host-pointer forms take) instead of interleaved
+    int src_rgb = 0, src_planar = 0;
+    size_t src_plane_stride = 0;
+    void default_source() {
+        src_w = src_h = 0, src_ch = 1;
+        src_rgb = src_planar = 0, src_plane_stride = 0;
+    }
     bool prepares() const { return src_w > 0; }
-    int in_w() const { return prepares() ? src_w : W; }   // width / height / bytes per row of an input frame
-    int in_h() const { return prepares() ? src_h : H; }
-    size_t in_row_bytes() const { return (size_t)in_w() * (prepares() ? src_ch : 1); }
+    int in_w() const { return prepares() ? src_w : W; }   // width / rows / bytes per row of an input frame as it is uploaded:
+    int in_h() const { return prepares() ? src_h * (src_planar ? 3 : 1) : H; } // a channels-first frame is 3 * src_h rows
+    size_t in_row_bytes() const { return (size_t)in_w() * (prepares() && !src_planar ? src_ch : 1); }
+    // bytes from a device frame's first byte to the end of its last row, rows `pitch` bytes apart; 0: the planes overlap
+    size_t in_frame_span(size_t pitch) const {
+        if (!prepares() || !src_planar)
+            return pitch * (size_t)in_h();
+        const size_t one = pitch * (size_t)src_h, ps = src_plane_stride ? src_plane_stride : one;
+        return ps < one ? 0 : 2 * ps + one;
+    }
 
     hipStream_t stream = nullptr;      // compute
     hipStream_t copy_stream = nullptr; // host -> device copies of the host-pointer entry points

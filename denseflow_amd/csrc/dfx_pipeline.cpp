@@ -142,6 +142,8 @@ struct FlowRun {
     ~FlowRun() { (void)c->helper.finish(); }
     // batch k uses staging set / bounce buffer / events of this parity
     int par(size_t k) const { return (int)((seq0 + k) & 1ull); }
+    // bytes of one value of a float flow on its way out: 4, or 2 for the half planes of dfx_calc_batch_planar_as*
+    size_t out_elem_bytes() const { return out.planar ? (size_t)dfx_elem_bytes(out.elem) : 4; }
     int prepare(const std::vector<int> &seg);
     int run(uint64_t *ticket);
     int upload(size_t k);
@@ -172,7 +174,8 @@ int FlowRun::prepare(const std::vector<int> &seg) {
     // or only feed the bounding kernel
     // inputs are source-format frames: convert / resize them on the device first
     prep = c->prepares() || !clip_fmt.empty();
-    src_ch = !clip_fmt.empty() ? seg_ch : c->prepares() ? c->src_ch : 1;
+    // (bytes per pixel of an uploaded row: a channels-first frame goes up as 3 * src_h rows of one byte per pixel)
+    src_ch = !clip_fmt.empty() ? seg_ch : c->prepares() && !c->src_planar ? c->src_ch : 1;
     src_stride = c->in_row_bytes() * c->in_h();
     if (!clip_fmt.empty()) {
         src_stride = 0;
@@ -201,7 +204,7 @@ int FlowRun::prepare(const std::vector<int> &seg) {
     // bounce buffers instead: the host gathers / scatters the frames with memcpy and the copy stream moves one block
     // per batch and direction.
     const size_t in_fb = src_stride;
-    const size_t out_pb = out.quantized ? 2 * plane : plane * 8; // bytes per pair leaving the device
+    const size_t out_pb = out.quantized ? 2 * plane : plane * 2 * out_elem_bytes(); // bytes per pair leaving the device
     // Decided per direction: a 224x224 frame is 50 KB (gathered), but its float flow is 401 KB — one direct copy per
     // flow (~10 us of driver time) is cheaper than a second pass of host memcpy over 120 MB per clip.
     bounce_in = host_mode && in_fb <= (256u << 10) && (size_t)F_need * in_fb <= (256u << 20);
@@ -289,7 +292,7 @@ int FlowRun::download(size_t k) { // results of batch k: staging set par(k) -> h
             HIPCHK(c, hipMemcpyAsync(hb + (size_t)p.nb * plane, c->d_img[q] + (size_t)c->img_slots * plane,
                                      (size_t)p.nb * plane, hipMemcpyDeviceToHost, c->d2h_stream));
         } else {
-            HIPCHK(c, hipMemcpyAsync(hb, c->d_flow_out[q], (size_t)p.nb * plane * 8, hipMemcpyDeviceToHost,
+            HIPCHK(c, hipMemcpyAsync(hb, c->d_flow_out[q], (size_t)p.nb * plane * 2 * out_elem_bytes(), hipMemcpyDeviceToHost,
                                      c->d2h_stream));
         }
     } else {
@@ -301,12 +304,13 @@ int FlowRun::download(size_t k) { // results of batch k: staging set par(k) -> h
                                           hipMemcpyDeviceToHost, c->d2h_stream));
                 HIPCHK(c, copy_rows_async(out.img_y[p.i0 + j], out.img_pitch, sy, c->W, c->W, c->H,
                                           hipMemcpyDeviceToHost, c->d2h_stream));
-            } else if (out.planar) { // staged dense: the u plane of flow j, then its v plane
-                const float *su = c->d_flow_out[q] + (size_t)j * plane * 2;
-                HIPCHK(c, copy_rows_async(out.flows_u[p.i0 + j], out.out_pitch, su, (size_t)c->W * 4, (size_t)c->W * 4, c->H,
+            } else if (out.planar) { // staged dense: the u plane of flow j, then its v plane (W * elem bytes per row)
+                const size_t e = out_elem_bytes(), rb = (size_t)c->W * e;
+                const unsigned char *su = reinterpret_cast<const unsigned char *>(c->d_flow_out[q]) + (size_t)j * plane * 2 * e;
+                HIPCHK(c, copy_rows_async(out.flows_u[p.i0 + j], out.out_pitch, su, rb, rb, c->H, hipMemcpyDeviceToHost,
+                                          c->d2h_stream));
+                HIPCHK(c, copy_rows_async(out.flows_v[p.i0 + j], out.out_pitch, su + plane * e, rb, rb, c->H,
                                           hipMemcpyDeviceToHost, c->d2h_stream));
-                HIPCHK(c, copy_rows_async(out.flows_v[p.i0 + j], out.out_pitch, su + plane, (size_t)c->W * 4, (size_t)c->W * 4,
-                                          c->H, hipMemcpyDeviceToHost, c->d2h_stream));
             } else {
                 HIPCHK(c, copy_rows_async(out.flows[p.i0 + j], out.out_pitch, c->d_flow_out[q] + (size_t)j * plane * 2,
                                           (size_t)c->W * 8, (size_t)c->W * 8, c->H, hipMemcpyDeviceToHost,
@@ -339,6 +343,7 @@ DfxHandover FlowRun::describe(size_t k) const {
         h.block = c->h_out[par(k)];
         h.two_planes = out.quantized;
         h.float_planes = out.planar;
+        h.elem_bytes = out_elem_bytes();
         h.W = c->W, h.H = c->H;
         h.pitch = out.quantized ? out.img_pitch : out.out_pitch;
         for (int j = 0; j < p.nb; ++j) {
@@ -418,7 +423,8 @@ int FlowRun::compute(size_t k) { // batch k on the compute stream, up to its sta
         long long stride = !host_mode ? (long long)in.d_frame_stride : prep ? (long long)src_stride : (long long)plane;
         if (prep && clip_fmt.empty()) { // cvtColor + cv::resize of load_frames_batch (src/denseflow_gpu.cpp:163, :169), on the device
             prepare_launch(c->stream, src, pitch, stride, c->src_w, c->src_h, c->src_ch, p.n_new, c->d_u8[q], c->W,
-                           (long long)plane, c->W, c->H);
+                           (long long)plane, c->W, c->H, c->src_rgb, c->src_planar,
+                           host_mode ? 0 : (long long)c->src_plane_stride); // (staged planes are dense)
             HIPCHK(c, hipGetLastError());
             c->stats.kernel_launches += 1;
             src = c->d_u8[q], pitch = c->W, stride = (long long)plane;
@@ -462,12 +468,14 @@ int FlowRun::compute(size_t k) { // batch k on the compute stream, up to its sta
     const long long dst_stride = staged ? (long long)plane * 2 : (long long)out.d_flow_stride;
     if (out.planar) { // the engine's last kernel writes the planes: the caller's (device mode) or dense ones in staging set q
         DfxPlanarOut po;
-        po.base = staged ? dst : out.d_planar + (size_t)p.i0 * out.d_flow_stride;
+        po.elem = out.elem;
+        po.base = staged ? (void *)dst
+                         : (void *)(static_cast<unsigned char *>(out.d_planar) + (size_t)p.i0 * out.d_flow_stride * out_elem_bytes());
         po.flow_stride = dst_stride;
         po.plane_stride = staged ? (long long)plane : (long long)out.d_plane_stride;
         po.row_pitch = staged ? (long long)c->W : (long long)out.d_row_pitch;
         po.bound = out.norm_bound;
-        po.vec = dfx_planar_vec(po.base, po.flow_stride, po.plane_stride, po.row_pitch);
+        po.vec = dfx_planar_vec(po.base, po.flow_stride, po.plane_stride, po.row_pitch, (int)out_elem_bytes());
         rc = E->run_pairs(p.nb, c->h_pairs.data(), nullptr, 0, &po, seedp);
     } else {
         rc = E->run_pairs(p.nb, c->h_pairs.data(), dst, dst_stride, nullptr, seedp);
@@ -584,6 +592,9 @@ int flowbuffer_body(dfx_context *c, const InSpec &in, int n_frames, int step, co
         return dfx_fail(c, DFX_ERR_INVALID, "dfx_next_segments: the clip lengths do not add up to n_frames");
     if (!seg_fmt.empty() && !in.frames)
         return dfx_fail(c, DFX_ERR_UNSUPPORTED, "dfx_next_segments_src applies to host-pointer calls only");
+    if (in.frames && seg_fmt.empty() && c->prepares() && c->src_planar && c->src_plane_stride != 0)
+        return dfx_fail(c, DFX_ERR_INVALID,
+                        "a non-zero plane_stride applies to the device-resident forms only: host frames hold dense planes");
     FlowRun run(c, in, out, step);
     run.clip_fmt.swap(seg_fmt); // one per clip (dfx_next_segments_src), or none
     run.seg_ch = seg_ch;

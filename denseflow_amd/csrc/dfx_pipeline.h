@@ -44,9 +44,10 @@ struct OutSpec {
     // (norm_bound = 0) or clamped to +-norm_bound and divided by it
     bool planar = false;
     float norm_bound = 0.f;
-    float *const *flows_u = nullptr, *const *flows_v = nullptr; // host mode: one pointer per plane, out_pitch bytes per row
-    float *d_planar = nullptr; // device mode: u plane of flow i at d_planar + i*d_flow_stride, v plane d_plane_stride behind
-    size_t d_row_pitch = 0, d_plane_stride = 0; // it, rows d_row_pitch floats apart (all in floats)
+    int elem = 0; // DFX_ELEM_* (dfx_device.h): float32 planes, or float16 / bfloat16 ones (dfx_calc_batch_planar_as*)
+    void *const *flows_u = nullptr, *const *flows_v = nullptr; // host mode: one pointer per plane, out_pitch bytes per row
+    void *d_planar = nullptr; // device mode: u plane of flow i at d_planar + i*d_flow_stride, v plane d_plane_stride behind
+    size_t d_row_pitch = 0, d_plane_stride = 0; // it, rows d_row_pitch apart (all in elements of `elem`)
     // 8-bit output
     uint8_t *const *img_x = nullptr, *const *img_y = nullptr; // host mode: one pointer per plane
     size_t img_pitch = 0;                                     // bytes per row (host and device mode)

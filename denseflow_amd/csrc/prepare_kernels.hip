@@ -9,17 +9,29 @@
 //   * resize INTER_LINEAR: source coordinate (float)((d + 0.5)*scale - 0.5), weights rounded to 11-bit
 //     fixed point (x2048), horizontal pass in int, vertical pass ((b0*(S0>>4))>>16) + ((b1*(S1>>4))>>16),
 //     +2 >> 2; an exact 2x2 decimation is what cv::resize turns into INTER_AREA: (a+b+c+d+2) >> 2.
+// A colour source may also be R, G, B (COLOR_RGB2GRAY: the same sum with the outer weights exchanged) and channels-first
+// (three byte planes): gray_at, a template on the format, reads the three bytes where the format puts them; everything behind
+// it is unchanged, and the B, G, R interleaved instantiation is the kernel as it was.
 // One thread per destination pixel; the four taps of a pixel are byte gathers served by L2 (a frame is
 // read once per destination pixel, 1-3 B/px of source + 1 B/px written: HBM-bound, tiny next to the flow).
 #include "prepare_kernels.h"
 
 namespace {
 
-__device__ __forceinline__ int gray_at(const unsigned char *row, int x, int channels) {
+// gray value of pixel x of a row.  The source format is a template parameter, so that the B, G, R interleaved form stays the
+// code it was: RGB (COLOR_RGB2GRAY) exchanges the outer weights, PLANAR reads the three bytes from byte planes `ch` bytes
+// apart (row: the row of the first plane) instead of from one 3-byte pixel.
+template <bool RGB, bool PLANAR> __device__ __forceinline__ int gray_at(const unsigned char *row, int x, int channels, long long ch) {
     if (channels == 1)
         return row[x];
-    const unsigned char *p = row + 3 * x; // B, G, R
-    return (p[0] * 3735 + p[1] * 19235 + p[2] * 9798 + (1 << 14)) >> 15;
+    int c0, c1, c2;
+    if (PLANAR) {
+        c0 = row[x], c1 = row[x + ch], c2 = row[x + 2 * ch];
+    } else {
+        const unsigned char *p = row + 3 * x;
+        c0 = p[0], c1 = p[1], c2 = p[2];
+    }
+    return ((RGB ? c2 : c0) * 3735 + c1 * 19235 + (RGB ? c0 : c2) * 9798 + (1 << 14)) >> 15;
 }
 
 // cv::resize's coefficient tables (resize.cpp, INTER_LINEAR, 8-bit): the source coordinate is evaluated in
@@ -52,9 +64,10 @@ __device__ __forceinline__ void linear_coeff_y(int d, double scale, int ssize, i
     w1 = (int)rintf(f * 2048.f);
 }
 
+template <bool RGB, bool PLANAR>
 __global__ __launch_bounds__(256) void k_prepare_frames(const unsigned char *src, long long src_pitch,
                                                          long long src_frame_stride, int sw, int sh, int channels,
-                                                         unsigned char *dst, long long dst_pitch,
+                                                         long long ch, unsigned char *dst, long long dst_pitch,
                                                          long long dst_frame_stride, int dw, int dh, double scale_x,
                                                          double scale_y, int mode) {
     const int dx = blockIdx.x * 64 + (threadIdx.x & 63);
@@ -63,21 +76,21 @@ __global__ __launch_bounds__(256) void k_prepare_frames(const unsigned char *src
         return;
     const unsigned char *S = src + (long long)blockIdx.z * src_frame_stride;
     unsigned char *D = dst + (long long)blockIdx.z * dst_frame_stride;
+    auto gray = [&](const unsigned char *row, int x) { return gray_at<RGB, PLANAR>(row, x, channels, ch); };
     int out;
     if (mode == 0) { // same size: colour conversion only
-        out = gray_at(S + (long long)dy * src_pitch, dx, channels);
+        out = gray(S + (long long)dy * src_pitch, dx);
     } else if (mode == 1) { // exact 2x decimation: INTER_AREA fast path
         const unsigned char *r0 = S + (long long)(2 * dy) * src_pitch, *r1 = r0 + src_pitch;
-        out = (gray_at(r0, 2 * dx, channels) + gray_at(r0, 2 * dx + 1, channels) + gray_at(r1, 2 * dx, channels) +
-               gray_at(r1, 2 * dx + 1, channels) + 2) >> 2;
+        out = (gray(r0, 2 * dx) + gray(r0, 2 * dx + 1) + gray(r1, 2 * dx) + gray(r1, 2 * dx + 1) + 2) >> 2;
     } else {
         int sx, a0, a1, sy0, sy1, b0, b1;
         linear_coeff_x(dx, scale_x, sw, sx, a0, a1);
         linear_coeff_y(dy, scale_y, sh, sy0, sy1, b0, b1);
         const int sx1 = min(sx + 1, sw - 1); // weight 0 whenever this clamps
         const unsigned char *r0 = S + (long long)sy0 * src_pitch, *r1 = S + (long long)sy1 * src_pitch;
-        const int h0 = gray_at(r0, sx, channels) * a0 + gray_at(r0, sx1, channels) * a1; // HResizeLinear, int
-        const int h1 = gray_at(r1, sx, channels) * a0 + gray_at(r1, sx1, channels) * a1;
+        const int h0 = gray(r0, sx) * a0 + gray(r0, sx1) * a1; // HResizeLinear, int
+        const int h1 = gray(r1, sx) * a0 + gray(r1, sx1) * a1;
         out = (((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2) >> 2; // VResizeLinear<uchar, int, short>
     }
     D[(long long)dy * dst_pitch + dx] = (unsigned char)out;
@@ -168,14 +181,19 @@ int prepare_mode(int sw, int sh, int dw, int dh) {
 
 void prepare_launch(hipStream_t s, const unsigned char *d_src, long long src_pitch, long long src_frame_stride, int sw,
                     int sh, int channels, int n, unsigned char *d_dst, long long dst_pitch, long long dst_frame_stride,
-                    int dw, int dh) {
+                    int dw, int dh, int rgb, int planar, long long plane_stride) {
     if (n <= 0)
         return;
     // cv::resize: inv_scale = dsize / ssize (double), scale = 1 / inv_scale
     const double scale_x = 1.0 / ((double)dw / (double)sw), scale_y = 1.0 / ((double)dh / (double)sh);
     const dim3 grid((dw + 63) / 64, (dh + 3) / 4, n);
-    hipLaunchKernelGGL(k_prepare_frames, grid, dim3(256), 0, s, d_src, src_pitch, src_frame_stride, sw, sh, channels,
-                       d_dst, dst_pitch, dst_frame_stride, dw, dh, scale_x, scale_y, prepare_mode(sw, sh, dw, dh));
+    const int mode = prepare_mode(sw, sh, dw, dh);
+    const bool swap = channels == 3 && rgb, pl = channels == 3 && planar;
+    const long long ch = pl ? (plane_stride ? plane_stride : src_pitch * sh) : 1;
+    auto k = pl ? (swap ? k_prepare_frames<true, true> : k_prepare_frames<false, true>)
+                : (swap ? k_prepare_frames<true, false> : k_prepare_frames<false, false>);
+    hipLaunchKernelGGL(k, grid, dim3(256), 0, s, d_src, src_pitch, src_frame_stride, sw, sh, channels, ch, d_dst, dst_pitch,
+                       dst_frame_stride, dw, dh, scale_x, scale_y, mode);
 }
 
 void prepare_bgr_launch(hipStream_t s, const unsigned char *d_src, long long src_pitch, long long src_frame_stride, int sw,

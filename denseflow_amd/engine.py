@@ -185,6 +185,22 @@ def load_library():
         L.dfx_calc_batch_planar.restype = i
         L.dfx_calc_batch_planar_device.argtypes = [vp, vp, sz, sz, i, i, C.c_double, vp, sz, sz, sz]
         L.dfx_calc_batch_planar_device.restype = i
+    if hasattr(L, "dfx_calc_batch_planar_as"):  # a library built before the typed planes / source layouts still loads
+        L.dfx_calc_batch_planar_as.argtypes = [vp, C.POINTER(vp), sz, i, i, C.c_double, i, C.POINTER(vp), C.POINTER(vp), sz]
+        L.dfx_calc_batch_planar_as.restype = i
+        L.dfx_calc_batch_planar_as_device.argtypes = [vp, vp, sz, sz, i, i, C.c_double, i, vp, sz, sz, sz]
+        L.dfx_calc_batch_planar_as_device.restype = i
+        L.dfx_calc_batch_planar_as_init_device.argtypes = [vp, vp, sz, sz, i, i, C.c_double, i, vp, sz, sz, sz, vp, sz, sz, sz]
+        L.dfx_calc_batch_planar_as_init_device.restype = i
+        L.dfx_set_source_format_ex.argtypes = [vp, i, i, i, i, i, sz]
+        L.dfx_set_source_format_ex.restype = i
+        L.dfx_prepare_frames_layout.argtypes = [vp, C.POINTER(vp), sz, i, i, i, i, i, i, C.POINTER(vp), sz]
+        L.dfx_prepare_frames_layout.restype = i
+        L.dfx_prepare_frames_layout_device.argtypes = [vp, vp, sz, sz, sz, i, i, i, i, i, i, vp, sz, sz]
+        L.dfx_prepare_frames_layout_device.restype = i
+    if hasattr(L, "dfxi_probe_planar_value_as"):  # test hook (selftest.hip)
+        L.dfxi_probe_planar_value_as.argtypes = [i, i, vp, C.c_float, vp, sz]
+        L.dfxi_probe_planar_value_as.restype = i
     if hasattr(L, "dfx_calc_batch_init"):  # a library built before the initial flows (DFX_LIBRARY A/B) still loads
         L.dfx_calc_batch_init.argtypes = [vp, C.POINTER(vp), sz, i, i, C.POINTER(vp), sz, C.POINTER(vp), sz]
         L.dfx_calc_batch_init.restype = i
@@ -301,6 +317,40 @@ def default_params() -> DfxParams:
     return p
 
 
+PLANAR_F32, PLANAR_F16, PLANAR_BF16 = 0, 1, 2  # DFX_PLANAR_* of include/dfx.h
+SRC_ORDERS = {"bgr": 0, "rgb": 1}   # DFX_SRC_BGR / DFX_SRC_RGB
+SRC_LAYOUTS = {"hwc": 0, "chw": 1}  # DFX_SRC_INTERLEAVED / DFX_SRC_PLANAR
+
+
+def _planar_dtype(dtype):
+    """(DFX_PLANAR_* code, numpy dtype of the array that holds the planes) for np.float32, np.float16 or "bfloat16" (which
+    numpy has no type for: its planes come back as np.uint16 bit patterns)."""
+    if isinstance(dtype, str):
+        if dtype == "bfloat16":
+            return PLANAR_BF16, np.dtype(np.uint16)
+        if dtype not in ("float32", "float16"):
+            raise ValueError('dtype must be np.float32, np.float16 or "bfloat16"')
+    try:
+        dt = np.dtype(dtype)
+    except TypeError:
+        raise ValueError('dtype must be np.float32, np.float16 or "bfloat16"') from None
+    if dt == np.float32:
+        return PLANAR_F32, dt
+    if dt == np.float16:
+        return PLANAR_F16, dt
+    raise ValueError('dtype must be np.float32, np.float16 or "bfloat16"')
+
+
+def _source_codes(channels, order, layout):
+    if order not in SRC_ORDERS:
+        raise ValueError('order must be "bgr" or "rgb"')
+    if layout not in SRC_LAYOUTS:
+        raise ValueError('layout must be "hwc" or "chw"')
+    if channels != 3 and (SRC_ORDERS[order] or SRC_LAYOUTS[layout]):
+        raise ValueError("order and layout apply to a 3-channel source only")
+    return SRC_ORDERS[order], SRC_LAYOUTS[layout]
+
+
 class FlowEngine:
     """One handle = one device + one private stream set (not thread-safe), sized for width x height (set_size re-plans it
     for another size inside its allocations)."""
@@ -356,37 +406,80 @@ class FlowEngine:
         self._pending_seg = self._armed_seg = self._pending_src = self._armed_src = None
         self._check(self._L.dfx_set_size(self._h, int(width), int(height)))
         self.width, self.height = int(width), int(height)
-        self._src = None
+        self._src = self._src_fmt = None
+        self._src_chw = False
 
     def device_bytes(self) -> int:
         """Device memory this handle holds right now, all kinds together."""
         return int(self._L.dfx_device_bytes(self._h))
 
     # -- frame preparation on the device (reference: cvtColor + cv::resize in load_frames_batch) ----------
-    def set_source_format(self, src_width: int = 0, src_height: int = 0, channels: int = 1):
-        """Frames passed to calc / calc_optflows* are src_width x src_height with 1 (gray) or 3 (BGR) channels
-        from now on and are converted / resized to the engine's size on the device.  () restores the default."""
-        self._check(self._L.dfx_set_source_format(self._h, int(src_width), int(src_height), int(channels)))
-        self._src = (int(src_height), int(src_width)) + ((3,) if channels == 3 else ()) if src_width else None
+    def set_source_format(self, src_width: int = 0, src_height: int = 0, channels: int = 1, order: str = "bgr",
+                          layout: str = "hwc"):
+        """Frames passed to calc / calc_optflows* are src_width x src_height with 1 (gray) or 3 channels from now on and are
+        converted / resized to the engine's size on the device.  () restores the default.
+        order "bgr" | "rgb": the channel order of a colour source.  layout "hwc": interleaved (Hs, Ws, 3) frames; "chw":
+        channels-first (3, Hs, Ws) frames, three byte planes (dfx_set_source_format_ex)."""
+        o, l = _source_codes(int(channels), order, layout) if src_width else (0, 0)
+        if o or l:
+            self._check(self._L.dfx_set_source_format_ex(self._h, int(src_width), int(src_height), int(channels), o, l, 0))
+        else:
+            self._check(self._L.dfx_set_source_format(self._h, int(src_width), int(src_height), int(channels)))
+        self._src_chw = bool(l)
+        if not src_width:
+            self._src = None
+        elif l:
+            self._src = (3, int(src_height), int(src_width))
+        else:
+            self._src = (int(src_height), int(src_width)) + ((3,) if channels == 3 else ())
+        self._src_fmt = (int(src_width), int(src_height), int(channels), o, l) if src_width else None
+
+    def _host_pitch(self, frame) -> int:
+        """Bytes per row of a host frame as the library counts them: for a channels-first frame the row pitch of one plane."""
+        return frame.strides[1] if getattr(self, "_src_chw", False) and frame.ndim == 3 else frame.strides[0]
 
     def _frame_shape(self):
         return getattr(self, "_src", None) or (self.height, self.width)
 
-    def prepare_frames(self, frames):
-        """cvtColor(BGR2GRAY) + cv::resize to the engine's size for a list of (h, w) or (h, w, 3) uint8 frames."""
+    def prepare_frames(self, frames, order: str = "bgr", layout: str = "hwc"):
+        """cvtColor(BGR2GRAY) + cv::resize to the engine's size for a list of (h, w) or (h, w, 3) uint8 frames.
+        order "rgb": the colour frames are R, G, B; layout "chw": they are (3, h, w)."""
         src = [np.ascontiguousarray(f, dtype=np.uint8) for f in frames]
         n = len(src)
         out = [np.empty((self.height, self.width), np.uint8) for _ in range(n)]
+        if order not in SRC_ORDERS or layout not in SRC_LAYOUTS:
+            _source_codes(3, order, layout)
+        chw = layout == "chw"
         if n == 0:
             return out
         shp = src[0].shape
-        if any(f.shape != shp for f in src) or len(shp) not in (2, 3) or (len(shp) == 3 and shp[2] != 3):
-            raise ValueError("frames must share one (h, w) or (h, w, 3) shape")
-        ch = 1 if len(shp) == 2 else 3
+        if chw:
+            if any(f.shape != shp for f in src) or len(shp) != 3 or shp[0] != 3:
+                raise ValueError("frames must share one (3, h, w) shape")
+            sh, sw, ch = shp[1], shp[2], 3
+        else:
+            if any(f.shape != shp for f in src) or len(shp) not in (2, 3) or (len(shp) == 3 and shp[2] != 3):
+                raise ValueError("frames must share one (h, w) or (h, w, 3) shape")
+            sh, sw, ch = shp[0], shp[1], 1 if len(shp) == 2 else 3
+        o, l = _source_codes(ch, order, layout)
         sp = (C.c_void_p * n)(*[f.ctypes.data for f in src])
         op = (C.c_void_p * n)(*[f.ctypes.data for f in out])
-        self._check(self._L.dfx_prepare_frames(self._h, sp, shp[1] * ch, shp[1], shp[0], ch, n, op, self.width))
+        if o or l:
+            self._check(self._L.dfx_prepare_frames_layout(self._h, sp, sw if chw else sw * ch, sw, sh, ch, o, l, n, op,
+                                                          self.width))
+        else:
+            self._check(self._L.dfx_prepare_frames(self._h, sp, sw * ch, sw, sh, ch, n, op, self.width))
         return out
+
+    def prepare_frames_layout_device(self, d_src_ptr: int, src_pitch: int, src_frame_stride: int, plane_stride: int,
+                                     src_width: int, src_height: int, channels: int, order: str, layout: str, n: int,
+                                     d_gray_ptr: int, gray_pitch: int, gray_frame_stride: int):
+        """prepare_frames_device for a source of the given order and layout; layout "chw": src_pitch is the row pitch of one
+        plane and plane c of a frame starts c * plane_stride bytes behind it (0: src_pitch * src_height)."""
+        o, l = _source_codes(int(channels), order, layout)
+        self._check(self._L.dfx_prepare_frames_layout_device(self._h, d_src_ptr, src_pitch, src_frame_stride, plane_stride,
+                                                             int(src_width), int(src_height), int(channels), o, l, int(n),
+                                                             d_gray_ptr, gray_pitch, gray_frame_stride))
 
     def prepare_frames_device(self, d_src_ptr: int, src_pitch: int, src_frame_stride: int, src_width: int,
                               src_height: int, channels: int, n: int, d_gray_ptr: int, gray_pitch: int,
@@ -498,7 +591,7 @@ class FlowEngine:
         if a.shape != self._frame_shape() or b.shape != a.shape:
             raise ValueError("frame shape does not match the engine")
         out = np.empty((self.height, self.width, 2), dtype=np.float32)
-        self._check(self._L.dfx_calc(self._h, a.ctypes.data, a.strides[0], b.ctypes.data, b.strides[0],
+        self._check(self._L.dfx_calc(self._h, a.ctypes.data, self._host_pitch(a), b.ctypes.data, self._host_pitch(b),
                                      out.ctypes.data, out.strides[0]))
         return out
 
@@ -522,11 +615,11 @@ class FlowEngine:
                 raise
             ip = (C.c_void_p * m)(*[s.ctypes.data for s in seeds])
             self._arm()
-            self._check(self._L.dfx_calc_batch_init(self._h, fp, frames[0].strides[0], n, int(step), ip, ipitch, op,
+            self._check(self._L.dfx_calc_batch_init(self._h, fp, self._host_pitch(frames[0]), n, int(step), ip, ipitch, op,
                                                     self.width * 8))
             return flows
         self._arm()
-        self._check(self._L.dfx_calc_batch(self._h, fp, frames[0].strides[0], n, int(step), op, self.width * 8))
+        self._check(self._L.dfx_calc_batch(self._h, fp, self._host_pitch(frames[0]), n, int(step), op, self.width * 8))
         return flows
 
     # -- asynchronous FlowBuffers (dfx_submit_batch* / dfx_wait) -----------------------------------------------
@@ -540,7 +633,7 @@ class FlowEngine:
         self._check_shapes(frames)
         t = C.c_uint64(0)
         fp = (C.c_void_p * max(n, 1))(*[f.ctypes.data for f in frames])
-        pitch = frames[0].strides[0] if n else self.width
+        pitch = self._host_pitch(frames[0]) if n else self.width
         if bound is None:
             flows = [np.empty((self.height, self.width, 2), dtype=np.float32) for _ in range(m)]
             op = (C.c_void_p * max(m, 1))(*[f.ctypes.data for f in flows])
@@ -578,87 +671,132 @@ class FlowEngine:
                                                   d_flows_ptr, flow_stride_floats))
 
     # -- planar float flows for tensor consumers (dfx_calc_batch_planar*) --------------------------------------
-    def calc_optflows_planar(self, frames_gray, step: int, bound: float | None = None) -> np.ndarray:
-        """calc_optflows as one (M, 2, H, W) float32 array: channel 0 = u, 1 = v, written as planes by the engine's last
-        kernel.  bound None: the raw flow values; bound > 0: clamp(x, -bound, bound) / bound in float32, NaN -> 0."""
+    def calc_optflows_planar(self, frames_gray, step: int, bound: float | None = None, dtype=np.float32) -> np.ndarray:
+        """calc_optflows as one (M, 2, H, W) array: channel 0 = u, 1 = v, written as planes by the engine's last kernel.
+        bound None: the raw flow values; bound > 0: clamp(x, -bound, bound) / bound in float32, NaN -> 0.
+        dtype: np.float32, or np.float16 / "bfloat16" — the float32 value rounded once (to nearest even) in the same store
+        (dfx_calc_batch_planar_as); bfloat16 planes come back as an np.uint16 array of bit patterns."""
+        code, np_dt = _planar_dtype(dtype)
         frames = self._frames_in(frames_gray)
         n = len(frames)
         m = self._num_pairs(n, step)
-        out = np.empty((m, 2, self.height, self.width), dtype=np.float32)
+        out = np.empty((m, 2, self.height, self.width), dtype=np_dt)
         if m == 0:
             return out
         self._check_shapes(frames)
         fp = (C.c_void_p * n)(*[f.ctypes.data for f in frames])
         up = (C.c_void_p * m)(*[out[k, 0].ctypes.data for k in range(m)])
         vp = (C.c_void_p * m)(*[out[k, 1].ctypes.data for k in range(m)])
+        pitch = self._host_pitch(frames[0])
         self._arm()
-        self._check(self._L.dfx_calc_batch_planar(self._h, fp, frames[0].strides[0], n, int(step),
+        if code != PLANAR_F32:
+            self._check(self._L.dfx_calc_batch_planar_as(self._h, fp, pitch, n, int(step),
+                                                         0.0 if bound is None else float(bound), code, up, vp,
+                                                         self.width * np_dt.itemsize))
+            return out
+        self._check(self._L.dfx_calc_batch_planar(self._h, fp, pitch, n, int(step),
                                                   0.0 if bound is None else float(bound), up, vp, self.width * 4))
         return out
 
     def calc_optflows_planar_device(self, d_frames_ptr: int, pitch: int, frame_stride: int, n_frames: int, step: int,
                                     bound: float | None, d_out_ptr: int, row_pitch_floats: int, plane_stride_floats: int,
-                                    flow_stride_floats: int):
+                                    flow_stride_floats: int, dtype=None):
         """Frames and planes resident in HBM (raw device pointers): flow i's u plane at d_out + i * flow_stride_floats, its
-        v plane plane_stride_floats behind it, rows row_pitch_floats apart."""
+        v plane plane_stride_floats behind it, rows row_pitch_floats apart.
+        dtype None: float32 planes (dfx_calc_batch_planar_device).  np.float32 / np.float16 / "bfloat16": planes of that
+        type through dfx_calc_batch_planar_as_device, the three strides in elements of it."""
+        code = None if dtype is None else _planar_dtype(dtype)[0]
         self._num_pairs(n_frames, step)
         self._arm()
+        if code is not None:
+            self._check(self._L.dfx_calc_batch_planar_as_device(self._h, d_frames_ptr, pitch, frame_stride, n_frames,
+                                                                int(step), 0.0 if bound is None else float(bound), code,
+                                                                d_out_ptr, row_pitch_floats, plane_stride_floats,
+                                                                flow_stride_floats))
+            return
         self._check(self._L.dfx_calc_batch_planar_device(self._h, d_frames_ptr, pitch, frame_stride, n_frames, int(step),
                                                          0.0 if bound is None else float(bound), d_out_ptr,
                                                          row_pitch_floats, plane_stride_floats, flow_stride_floats))
 
-    def flow_tensor(self, frames, step: int, bound: float | None = None, out=None, init=None):
-        """Flows of a FlowBuffer of torch frames as an (M, 2, H, W) float32 torch tensor on the same device, the layout
-        (and, with bound, the [-1, 1] scaling) a two-stream / TSN / I3D network takes: no pointer handling, no permute
-        pass, no clamp-and-divide pass.
+    def flow_tensor(self, frames, step: int, bound: float | None = None, out=None, init=None, dtype=None):
+        """Flows of a FlowBuffer of torch frames as an (M, 2, H, W) torch tensor on the same device, the layout (and, with
+        bound, the [-1, 1] scaling) a two-stream / TSN / I3D network takes: no pointer handling, no permute pass, no
+        clamp-and-divide pass.
 
-        frames: torch.uint8 tensor on this handle's device, (N, H, W), or (N, Hs, Ws, 3) BGR / (N, Hs, Ws) gray when a
-        source format is set.  Any strides as long as the innermost dimension is contiguous (for BGR: the pixel's three
-        bytes too); row pitch and frame stride are taken from the tensor.
-        out: optional (M, 2, H, W) float32 tensor on that device to write into, any strides with a contiguous innermost
-        dimension that do not make rows, planes or flows overlap; otherwise the result is allocated.
+        frames: torch.uint8 tensor on this handle's device, (N, H, W), or — when a source format is set — (N, Hs, Ws) gray,
+        (N, Hs, Ws, 3) interleaved colour or (N, 3, Hs, Ws) channels-first colour (layout "chw"), BGR or RGB as declared.
+        Any strides as long as the innermost dimension is contiguous (interleaved: the pixel's three bytes too) and rows,
+        planes and frames do not overlap; row pitch, plane stride and frame stride are taken from the tensor, so a
+        permuted view of an NHWC batch or a slice of a larger tensor is read where it lies.
+        dtype: torch.float32 (default), torch.float16 or torch.bfloat16 — the float32 value rounded once, to nearest even,
+        in the store that writes the plane (dfx_calc_batch_planar_as_device).
+        out: optional (M, 2, H, W) tensor of that dtype on that device to write into, any strides with a contiguous
+        innermost dimension that do not make rows, planes or flows overlap; otherwise the result is allocated.
         bound None: raw flow values, bit for bit those of calc_optflows; bound > 0: clamp(x, -bound, bound) / bound.
         init: optional (M, 2, H, W) float32 tensor on that device, the initial flow of every output flow in raw pixels
-        (whatever bound is; dfx_calc_batch_planar_init_device).  The library reads it with the strides of `out`: without
+        (whatever bound and dtype are).  With float32 planes the library reads it with the strides of `out`: without
         `out` any strides are accepted (a contiguous copy is made if needed); with `out` it must have out's strides, and it
-        may be `out` itself (refinement in place).
+        may be `out` itself (refinement in place).  With half planes it is made contiguous.
 
         Streams: torch's current stream on that device is synchronised before the call, so frames produced on it just
         before are complete; the library call returns with all its device work complete, so the result may be used on
         any stream afterwards without further synchronisation.
 
         Raises ValueError — before the library is reached — for a wrong dtype, device, rank or shape, a non-contiguous
-        innermost dimension, or an `out` that does not match."""
+        innermost dimension, overlapping rows, planes or frames, or an `out` that does not match."""
         import torch
 
+        codes = {torch.float32: PLANAR_F32, torch.float16: PLANAR_F16, torch.bfloat16: PLANAR_BF16}
+        tdt = torch.float32 if dtype is None else dtype
+        if tdt not in codes:
+            raise ValueError("dtype must be torch.float32, torch.float16 or torch.bfloat16")
+        code = codes[tdt]
         if not isinstance(frames, torch.Tensor):
             raise ValueError("frames must be a torch tensor")
         if frames.dtype != torch.uint8:
             raise ValueError("frames must be torch.uint8")
         shape = self._frame_shape()
+        chw = bool(getattr(self, "_src_chw", False))
         if frames.dim() != 1 + len(shape) or tuple(frames.shape[1:]) != tuple(shape):
             raise ValueError(f"frames must be (N,) + {tuple(shape)}")
         st = frames.stride()
-        if st[-1] != 1 or (len(shape) == 3 and st[2] != 3):
+        # a channels-first SHAPE over interleaved memory — the permuted view of an NHWC batch, torch's channels_last — is read
+        # as the interleaved frames it is
+        nhwc_view = chw and st[3] == 3 and st[1] == 1
+        if not nhwc_view and (st[-1] != 1 or (len(shape) == 3 and not chw and st[2] != 3)):
             raise ValueError("the innermost dimension of frames must be contiguous")
         n = int(frames.shape[0])
-        row_bytes = shape[1] * (3 if len(shape) == 3 else 1)
-        pitch = st[1] if shape[0] > 1 else row_bytes  # (the stride of a dimension of size 1 means nothing)
-        frame_stride = st[0] if n > 1 else pitch * shape[0]
-        if pitch < row_bytes or frame_stride < pitch * shape[0]:
+        plane_stride = 0
+        if nhwc_view:
+            rows, row_bytes = shape[1], shape[2] * 3
+            pitch = st[2] if rows > 1 else row_bytes
+            span = pitch * rows
+        elif chw:
+            rows, row_bytes = shape[1], shape[2]
+            pitch = st[2] if rows > 1 else row_bytes  # (the stride of a dimension of size 1 means nothing)
+            plane_stride = st[1]
+            if pitch < row_bytes or plane_stride < pitch * rows:
+                raise ValueError("frames: rows or planes overlap")
+            span = 2 * plane_stride + pitch * rows
+        else:
+            rows, row_bytes = shape[0], shape[1] * (3 if len(shape) == 3 else 1)
+            pitch = st[1] if rows > 1 else row_bytes
+            span = pitch * rows
+        frame_stride = st[0] if n > 1 else span
+        if pitch < row_bytes or frame_stride < span:
             raise ValueError("frames: rows or frames overlap")
         dev = frames.device
         m = self._peek_pairs(n, step)
         want = (m, 2, self.height, self.width)
         if out is not None:
-            if not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.device != dev:
-                raise ValueError("out must be a torch.float32 tensor on the frames' device")
+            if not isinstance(out, torch.Tensor) or out.dtype != tdt or out.device != dev:
+                raise ValueError(f"out must be a {tdt} tensor on the frames' device")
             if tuple(out.shape) != want:
                 raise ValueError(f"out must have shape {want}")
             so = out.stride()
             row_pitch = so[2] if self.height > 1 else self.width
-            plane_stride, flow_stride = so[1], (so[0] if m > 1 else 2 * so[1])
-            if so[3] != 1 or row_pitch < self.width or plane_stride < self.height * row_pitch or flow_stride < 2 * plane_stride:
+            out_plane_stride, flow_stride = so[1], (so[0] if m > 1 else 2 * so[1])
+            if so[3] != 1 or row_pitch < self.width or out_plane_stride < self.height * row_pitch or flow_stride < 2 * out_plane_stride:
                 raise ValueError("out: the innermost dimension must be contiguous and rows, planes and flows must not overlap")
         if dev.type != "cuda" or (dev.index is not None and dev.index != getattr(self, "_device", dev.index)):
             raise ValueError("frames must be on this handle's device")
@@ -667,28 +805,55 @@ class FlowEngine:
                 raise ValueError("init must be a torch.float32 tensor on the frames' device")
             if tuple(init.shape) != want:
                 raise ValueError(f"init must have shape {want}")
-            if out is None:
+            if out is None or code != PLANAR_F32:
                 init = init.contiguous()
             elif init.stride() != out.stride():
                 raise ValueError("init must have the strides of out")
         if out is None:
-            out = torch.empty(want, dtype=torch.float32, device=dev)
-            row_pitch, plane_stride = self.width, self.height * self.width
-            flow_stride = 2 * plane_stride
+            out = torch.empty(want, dtype=tdt, device=dev)
+            row_pitch, out_plane_stride = self.width, self.height * self.width
+            flow_stride = 2 * out_plane_stride
         self._num_pairs(n, step)
         torch.cuda.current_stream(dev).synchronize()
+        if nhwc_view or (chw and plane_stride != pitch * rows):  # how THIS tensor lies in memory, declared for this call only
+            self._set_call_layout(0 if nhwc_view else 1, plane_stride)
+            try:
+                return self._flow_tensor_call(code, frames, pitch, frame_stride, n, step, bound, init, out, m, row_pitch,
+                                              out_plane_stride, flow_stride)
+            finally:
+                self._set_call_layout(1, 0)
+        return self._flow_tensor_call(code, frames, pitch, frame_stride, n, step, bound, init, out, m, row_pitch,
+                                      out_plane_stride, flow_stride)
+
+    def _flow_tensor_call(self, code, frames, pitch, frame_stride, n, step, bound, init, out, m, row_pitch, out_plane_stride,
+                          flow_stride):
         self._arm()
+        fptr, optr = frames.data_ptr() if n else None, out.data_ptr() if m else None
+        b = 0.0 if bound is None else float(bound)
         if init is not None and m:  # (no output flow: nothing to seed)
+            if code != PLANAR_F32:
+                hw = self.height * self.width
+                self._check(self._L.dfx_calc_batch_planar_as_init_device(
+                    self._h, fptr, pitch, frame_stride, n, int(step), b, code, init.data_ptr(), self.width, hw, 2 * hw,
+                    optr, row_pitch, out_plane_stride, flow_stride))
+                return out
             self._check(self._L.dfx_calc_batch_planar_init_device(
-                self._h, frames.data_ptr() if n else None, pitch, frame_stride, n, int(step),
-                0.0 if bound is None else float(bound), init.data_ptr(), out.data_ptr() if m else None, row_pitch,
-                plane_stride, flow_stride))
+                self._h, fptr, pitch, frame_stride, n, int(step), b, init.data_ptr(), optr, row_pitch, out_plane_stride,
+                flow_stride))
             return out
-        self._check(self._L.dfx_calc_batch_planar_device(self._h, frames.data_ptr() if n else None, pitch, frame_stride, n,
-                                                         int(step), 0.0 if bound is None else float(bound),
-                                                         out.data_ptr() if m else None, row_pitch, plane_stride,
-                                                         flow_stride))
+        if code != PLANAR_F32:
+            self._check(self._L.dfx_calc_batch_planar_as_device(self._h, fptr, pitch, frame_stride, n, int(step), b, code,
+                                                                optr, row_pitch, out_plane_stride, flow_stride))
+            return out
+        self._check(self._L.dfx_calc_batch_planar_device(self._h, fptr, pitch, frame_stride, n, int(step), b, optr,
+                                                         row_pitch, out_plane_stride, flow_stride))
         return out
+
+    def _set_call_layout(self, layout: int, plane_stride: int):
+        """The memory layout and plane stride of the tensor the next device-resident call reads; size, channels and order stay
+        the declared ones (host frames hold dense planes and take plane stride 0)."""
+        sw, sh, ch, o, _ = self._src_fmt
+        self._check(self._L.dfx_set_source_format_ex(self._h, sw, sh, ch, o, int(layout), int(plane_stride)))
 
     def _peek_pairs(self, n: int, step: int) -> int:
         """The number of flows the next call gives for n frames, a pending next_segments included; consumes nothing."""
@@ -718,7 +883,7 @@ class FlowEngine:
         xp = (C.c_void_p * m)(*[f.ctypes.data for f in img_x])
         yp = (C.c_void_p * m)(*[f.ctypes.data for f in img_y])
         self._arm()
-        self._check(self._L.dfx_calc_batch_u8(self._h, fp, frames[0].strides[0], n, int(step), lo, float(bound), xp,
+        self._check(self._L.dfx_calc_batch_u8(self._h, fp, self._host_pitch(frames[0]), n, int(step), lo, float(bound), xp,
                                               yp, self.width))
         return img_x, img_y
 
@@ -746,11 +911,11 @@ class FlowEngine:
         self._arm()
         if submit:
             t = C.c_uint64(0)
-            self._check(self._L.dfx_submit_batch_png(self._h, fp, frames[0].strides[0], n, int(step), xp, yp, self.width,
+            self._check(self._L.dfx_submit_batch_png(self._h, fp, self._host_pitch(frames[0]), n, int(step), xp, yp, self.width,
                                                      bp, C.byref(t)))
             self._check(self._L.dfx_wait(self._h, t.value))
         else:
-            self._check(self._L.dfx_calc_batch_png(self._h, fp, frames[0].strides[0], n, int(step), xp, yp, self.width, bp))
+            self._check(self._L.dfx_calc_batch_png(self._h, fp, self._host_pitch(frames[0]), n, int(step), xp, yp, self.width, bp))
         return img_x, img_y, bounds
 
     def calc_optflows_png_device(self, d_frames_ptr: int, pitch: int, frame_stride: int, n_frames: int, step: int,
@@ -793,7 +958,7 @@ class FlowEngine:
         sx, sy = (C.c_uint32 * m)(), (C.c_uint32 * m)()
         fp = (C.c_void_p * n)(*[f.ctypes.data for f in frames])
         self._arm()
-        self._check(self._L.dfx_calc_batch_jpeg(self._h, fp, frames[0].strides[0], n, int(step), -float(bound),
+        self._check(self._L.dfx_calc_batch_jpeg(self._h, fp, self._host_pitch(frames[0]), n, int(step), -float(bound),
                                                 float(bound), int(quality), (C.c_void_p * m)(*[b.ctypes.data for b in bx]),
                                                 (C.c_void_p * m)(*[b.ctypes.data for b in by]), cap, sx, sy))
         return ([bx[i][:sx[i]].tobytes() for i in range(m)], [by[i][:sy[i]].tobytes() for i in range(m)])
