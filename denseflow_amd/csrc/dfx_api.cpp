@@ -7,6 +7,7 @@
 #include <cstring>
 
 #include "dfx_pipeline.h"
+#include "fb_check_kernels.h"
 #include "jpeg_kernels.h"
 #include "prepare_kernels.h"
 #include "quantize_kernels.h"
@@ -525,6 +526,93 @@ int dfx_calc_batch_planar_as_device(dfx_handle h, const uint8_t *d_frames, size_
                                     size_t plane_stride, size_t flow_stride) {
     return planar_device(h, d_frames, pitch, frame_stride, n_frames, step, norm_bound, dtype, true, d_out, row_pitch,
                          plane_stride, flow_stride);
+}
+
+// ---- both directions of every pair in one call, and the forward-backward check of two flows ----
+namespace {
+// alpha1 / alpha2 of the check: finite and not negative
+inline bool fb_alpha_ok(float a) { return std::isfinite(a) && a >= 0.0f; }
+const char *const kFbAlpha = "alpha1 and alpha2 must be finite and >= 0";
+const char *const kFbOcc = "mask planes: occ_pitch >= W and occ_stride >= H * occ_pitch are required";
+inline bool fb_occ_bad(dfx_handle h, size_t occ_pitch, size_t occ_stride) {
+    return occ_pitch < (size_t)h->W || occ_pitch > ((size_t)1 << 40) || occ_stride < occ_pitch * (size_t)h->H;
+}
+} // namespace
+
+int dfx_calc_batch_bidir_device(dfx_handle h, const uint8_t *d_frames, size_t pitch, size_t frame_stride, int n_frames,
+                                int step, float *d_fwd, float *d_bwd, size_t row_pitch_floats, size_t plane_stride_floats,
+                                size_t flow_stride_floats, float alpha1, float alpha2, uint8_t *d_occ_fwd,
+                                uint8_t *d_occ_bwd, size_t occ_pitch, size_t occ_stride) {
+    if (!h)
+        return DFX_ERR_INVALID;
+    SegmentsScope seg_scope(h);
+    if (h->algo == DFX_ALGO_FRAMES)
+        return dfx_fail(h, DFX_ERR_UNSUPPORTED, "a DFX_ALGO_FRAMES handle computes no flow");
+    if (src_segments_pending(h))
+        return dfx_fail(h, DFX_ERR_UNSUPPORTED, "dfx_next_segments_src applies to host-pointer calls only");
+    if (step == 0)
+        return dfx_fail(h, DFX_ERR_INVALID, "n_frames must be >= 0 and step non-zero");
+    if ((d_occ_fwd == nullptr) != (d_occ_bwd == nullptr))
+        return dfx_fail(h, DFX_ERR_INVALID, "both mask pointers or neither (NULL, NULL: no check)");
+    const bool check = d_occ_fwd != nullptr;
+    if (check && (!fb_alpha_ok(alpha1) || !fb_alpha_ok(alpha2)))
+        return dfx_fail(h, DFX_ERR_INVALID, kFbAlpha);
+    const int M = std::max(n_frames - abs_step(step), 0);
+    if (M > 0 && (!d_frames || !d_fwd || !d_bwd))
+        return dfx_fail(h, DFX_ERR_INVALID, "NULL device frames or flow planes");
+    if (M > 0 && device_frames_too_small(h, pitch, frame_stride))
+        return dfx_fail(h, DFX_ERR_INVALID, "pitch/stride smaller than a frame");
+    if (M > 0 && planar_strides_bad(h, row_pitch_floats, plane_stride_floats, flow_stride_floats))
+        return dfx_fail(h, DFX_ERR_INVALID, kPlanarStrides);
+    if (M > 0 && check && fb_occ_bad(h, occ_pitch, occ_stride))
+        return dfx_fail(h, DFX_ERR_INVALID, kFbOcc);
+    OutSpec out;
+    out.planar = out.bidir = true;
+    out.elem = DFX_PLANAR_F32;
+    out.d_planar = d_fwd, out.d_planar_bwd = d_bwd;
+    out.d_row_pitch = row_pitch_floats, out.d_plane_stride = plane_stride_floats, out.d_flow_stride = flow_stride_floats;
+    out.d_occ_fwd = d_occ_fwd, out.d_occ_bwd = d_occ_bwd, out.occ_pitch = occ_pitch, out.d_occ_stride = occ_stride;
+    out.alpha1 = alpha1, out.alpha2 = alpha2;
+    return dfx_run_flowbuffer(h, InSpec::device(d_frames, pitch, frame_stride), n_frames, step, out, nullptr);
+}
+
+int dfx_fb_check_device(dfx_handle h, const float *d_fwd, const float *d_bwd, size_t row_pitch_floats,
+                        size_t plane_stride_floats, size_t flow_stride_floats, int n, float alpha1, float alpha2,
+                        uint8_t *d_occ, size_t occ_pitch, size_t occ_stride, float *d_err, size_t err_pitch_floats,
+                        size_t err_stride_floats) {
+    if (!h)
+        return DFX_ERR_INVALID;
+    (void)dfx_finish_tails(h, 0, -1);
+    if (h->algo == DFX_ALGO_FRAMES)
+        return dfx_fail(h, DFX_ERR_UNSUPPORTED, "a DFX_ALGO_FRAMES handle computes no flow");
+    if (n < 0)
+        return dfx_fail(h, DFX_ERR_INVALID, "n must be >= 0");
+    if (n == 0)
+        return DFX_OK;
+    if (!d_fwd || !d_bwd || !d_occ)
+        return dfx_fail(h, DFX_ERR_INVALID, "NULL device flows or mask planes");
+    if (planar_strides_bad(h, row_pitch_floats, plane_stride_floats, flow_stride_floats))
+        return dfx_fail(h, DFX_ERR_INVALID, kPlanarStrides);
+    if (fb_occ_bad(h, occ_pitch, occ_stride))
+        return dfx_fail(h, DFX_ERR_INVALID, kFbOcc);
+    if (d_err && (err_pitch_floats < (size_t)h->W || err_pitch_floats > ((size_t)1 << 40) ||
+                  err_stride_floats < err_pitch_floats * (size_t)h->H))
+        return dfx_fail(h, DFX_ERR_INVALID, "err planes: err_pitch_floats >= W and err_stride_floats >= H * err_pitch_floats are required");
+    if (!fb_alpha_ok(alpha1) || !fb_alpha_ok(alpha2))
+        return dfx_fail(h, DFX_ERR_INVALID, kFbAlpha);
+    HIPCHK(h, hipSetDevice(h->device));
+    FbCheckArgs a{};
+    a.dir[0].f = d_fwd, a.dir[0].b = d_bwd, a.dir[0].occ = d_occ, a.dir[0].err = d_err;
+    a.dirs = 1, a.n = n, a.w = h->W, a.h = h->H;
+    a.row_pitch = (long long)row_pitch_floats, a.plane_stride = (long long)plane_stride_floats;
+    a.flow_stride = (long long)flow_stride_floats;
+    a.occ_pitch = (long long)occ_pitch, a.occ_stride = (long long)occ_stride;
+    a.err_pitch = (long long)err_pitch_floats, a.err_stride = (long long)err_stride_floats;
+    a.alpha1 = alpha1, a.alpha2 = alpha2;
+    fb_check_launch(h->stream, a);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return DFX_OK;
 }
 
 // ---- caller-supplied initial flows (TVL1's useInitialFlow, Farneback's OPTFLOW_USE_INITIAL_FLOW) ----

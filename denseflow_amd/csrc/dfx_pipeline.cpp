@@ -10,6 +10,7 @@
 
 #include "dfx_pipeline.h"
 #include "dfx_plan.h"
+#include "fb_check_kernels.h"
 #include "jpeg_kernels.h"
 #include "prepare_kernels.h"
 #include "quantize_kernels.h"
@@ -152,6 +153,7 @@ struct FlowRun {
     int hand_over(size_t k);
     int overlap_copies(size_t k);
     int compute(size_t k);
+    int backward(const DfxBatchPlan &p, const DfxPlanarOut &fwd);
     int launch_jpeg(size_t k);
     int finish(uint64_t *ticket);
 };
@@ -408,6 +410,42 @@ int FlowRun::launch_jpeg(size_t k) { // imencode(".jpg") of both planes of every
     return rc;
 }
 
+// dfx_calc_batch_bidir_device: the batch's pairs once more with the two frames exchanged — the frames are resident, nothing
+// is built again — into the caller's backward planes, then the forward-backward check of both directions in one launch.
+// Two run_pairs calls of nb pairs each, each with the account() it is owed on an idle stream: the engine sees the two
+// batches it would see from a planar call with `step` and one with -step, so the bits (and TVL1's early-exit grouping)
+// are those calls'.  fwd: where the forward planes of this batch just went.
+int FlowRun::backward(const DfxBatchPlan &p, const DfxPlanarOut &fwd) {
+    HIPCHK(c, dfx_stream_wait(c, c->stream)); // the forward batch's statistics read-backs are complete
+    int rc = E->account(p.nb);
+    if (rc != DFX_OK)
+        return rc;
+    for (int j = 0; j < p.nb; ++j) {
+        const int i = p.i0 + j;
+        c->h_pairs[j].frame_a = dfx_pair_a(pairs, i, -step) % F;
+        c->h_pairs[j].frame_b = dfx_pair_b(pairs, i, -step) % F;
+    }
+    DfxPlanarOut bwd = fwd;
+    bwd.base = out.d_planar_bwd + (size_t)p.i0 * out.d_flow_stride;
+    bwd.vec = dfx_planar_vec(bwd.base, bwd.flow_stride, bwd.plane_stride, bwd.row_pitch, 4);
+    rc = E->run_pairs(p.nb, c->h_pairs.data(), nullptr, 0, &bwd, nullptr);
+    if (rc != DFX_OK || !out.d_occ_fwd)
+        return rc;
+    FbCheckArgs a{};
+    a.dir[0].f = a.dir[1].b = static_cast<const float *>(fwd.base);
+    a.dir[0].b = a.dir[1].f = static_cast<const float *>(bwd.base);
+    a.dir[0].occ = out.d_occ_fwd + (size_t)p.i0 * out.d_occ_stride;
+    a.dir[1].occ = out.d_occ_bwd + (size_t)p.i0 * out.d_occ_stride;
+    a.dirs = 2, a.n = p.nb, a.w = c->W, a.h = c->H;
+    a.row_pitch = fwd.row_pitch, a.plane_stride = fwd.plane_stride, a.flow_stride = fwd.flow_stride;
+    a.occ_pitch = (long long)out.occ_pitch, a.occ_stride = (long long)out.d_occ_stride;
+    a.alpha1 = out.alpha1, a.alpha2 = out.alpha2;
+    fb_check_launch(c->stream, a);
+    HIPCHK(c, hipGetLastError());
+    c->stats.kernel_launches += 1;
+    return DFX_OK;
+}
+
 int FlowRun::compute(size_t k) { // batch k on the compute stream, up to its statistics and (JPEG) its coded sizes
     const DfxBatchPlan &p = plan[k];
     const int q = par(k);
@@ -477,6 +515,8 @@ int FlowRun::compute(size_t k) { // batch k on the compute stream, up to its sta
         po.bound = out.norm_bound;
         po.vec = dfx_planar_vec(po.base, po.flow_stride, po.plane_stride, po.row_pitch, (int)out_elem_bytes());
         rc = E->run_pairs(p.nb, c->h_pairs.data(), nullptr, 0, &po, seedp);
+        if (rc == DFX_OK && out.bidir)
+            rc = backward(p, po);
     } else {
         rc = E->run_pairs(p.nb, c->h_pairs.data(), dst, dst_stride, nullptr, seedp);
     }

@@ -48,6 +48,15 @@ struct OutSpec {
     void *const *flows_u = nullptr, *const *flows_v = nullptr; // host mode: one pointer per plane, out_pitch bytes per row
     void *d_planar = nullptr; // device mode: u plane of flow i at d_planar + i*d_flow_stride, v plane d_plane_stride behind
     size_t d_row_pitch = 0, d_plane_stride = 0; // it, rows d_row_pitch apart (all in elements of `elem`)
+    // both directions of every pair in one call (dfx_calc_batch_bidir_device: device mode, raw float32 planes): d_planar takes
+    // the flows of `step`, d_planar_bwd — same three strides — those of -step; with mask pointers the forward-backward check
+    // (fb_check_kernels.hip) of (fwd, bwd) goes to d_occ_fwd and that of (bwd, fwd) to d_occ_bwd, mask plane i at
+    // + i*d_occ_stride bytes, occ_pitch bytes per row
+    bool bidir = false;
+    float *d_planar_bwd = nullptr;
+    uint8_t *d_occ_fwd = nullptr, *d_occ_bwd = nullptr;
+    size_t occ_pitch = 0, d_occ_stride = 0;
+    float alpha1 = 0.f, alpha2 = 0.f;
     // 8-bit output
     uint8_t *const *img_x = nullptr, *const *img_y = nullptr; // host mode: one pointer per plane
     size_t img_pitch = 0;                                     // bytes per row (host and device mode)

@@ -198,6 +198,12 @@ def load_library():
         L.dfx_prepare_frames_layout.restype = i
         L.dfx_prepare_frames_layout_device.argtypes = [vp, vp, sz, sz, sz, i, i, i, i, i, i, vp, sz, sz]
         L.dfx_prepare_frames_layout_device.restype = i
+    if hasattr(L, "dfx_calc_batch_bidir_device"):  # a library built before the bidirectional call (DFX_LIBRARY A/B) still loads
+        f32 = C.c_float
+        L.dfx_calc_batch_bidir_device.argtypes = [vp, vp, sz, sz, i, i, vp, vp, sz, sz, sz, f32, f32, vp, vp, sz, sz]
+        L.dfx_calc_batch_bidir_device.restype = i
+        L.dfx_fb_check_device.argtypes = [vp, vp, vp, sz, sz, sz, i, f32, f32, vp, sz, sz, vp, sz, sz]
+        L.dfx_fb_check_device.restype = i
     if hasattr(L, "dfxi_probe_planar_value_as"):  # test hook (selftest.hip)
         L.dfxi_probe_planar_value_as.argtypes = [i, i, vp, C.c_float, vp, sz]
         L.dfxi_probe_planar_value_as.restype = i
@@ -751,40 +757,7 @@ class FlowEngine:
         if tdt not in codes:
             raise ValueError("dtype must be torch.float32, torch.float16 or torch.bfloat16")
         code = codes[tdt]
-        if not isinstance(frames, torch.Tensor):
-            raise ValueError("frames must be a torch tensor")
-        if frames.dtype != torch.uint8:
-            raise ValueError("frames must be torch.uint8")
-        shape = self._frame_shape()
-        chw = bool(getattr(self, "_src_chw", False))
-        if frames.dim() != 1 + len(shape) or tuple(frames.shape[1:]) != tuple(shape):
-            raise ValueError(f"frames must be (N,) + {tuple(shape)}")
-        st = frames.stride()
-        # a channels-first SHAPE over interleaved memory — the permuted view of an NHWC batch, torch's channels_last — is read
-        # as the interleaved frames it is
-        nhwc_view = chw and st[3] == 3 and st[1] == 1
-        if not nhwc_view and (st[-1] != 1 or (len(shape) == 3 and not chw and st[2] != 3)):
-            raise ValueError("the innermost dimension of frames must be contiguous")
-        n = int(frames.shape[0])
-        plane_stride = 0
-        if nhwc_view:
-            rows, row_bytes = shape[1], shape[2] * 3
-            pitch = st[2] if rows > 1 else row_bytes
-            span = pitch * rows
-        elif chw:
-            rows, row_bytes = shape[1], shape[2]
-            pitch = st[2] if rows > 1 else row_bytes  # (the stride of a dimension of size 1 means nothing)
-            plane_stride = st[1]
-            if pitch < row_bytes or plane_stride < pitch * rows:
-                raise ValueError("frames: rows or planes overlap")
-            span = 2 * plane_stride + pitch * rows
-        else:
-            rows, row_bytes = shape[0], shape[1] * (3 if len(shape) == 3 else 1)
-            pitch = st[1] if rows > 1 else row_bytes
-            span = pitch * rows
-        frame_stride = st[0] if n > 1 else span
-        if pitch < row_bytes or frame_stride < span:
-            raise ValueError("frames: rows or frames overlap")
+        n, pitch, frame_stride, layout = self._tensor_frames(frames)
         dev = frames.device
         m = self._peek_pairs(n, step)
         want = (m, 2, self.height, self.width)
@@ -815,8 +788,8 @@ class FlowEngine:
             flow_stride = 2 * out_plane_stride
         self._num_pairs(n, step)
         torch.cuda.current_stream(dev).synchronize()
-        if nhwc_view or (chw and plane_stride != pitch * rows):  # how THIS tensor lies in memory, declared for this call only
-            self._set_call_layout(0 if nhwc_view else 1, plane_stride)
+        if layout is not None:  # how THIS tensor lies in memory, declared for this call only
+            self._set_call_layout(*layout)
             try:
                 return self._flow_tensor_call(code, frames, pitch, frame_stride, n, step, bound, init, out, m, row_pitch,
                                               out_plane_stride, flow_stride)
@@ -863,6 +836,228 @@ class FlowEngine:
         if sum(seg) != n or min(seg, default=0) < 0:
             raise ValueError("segment lengths must be >= 0 and add up to the number of frames")
         return sum(max(x - abs(int(step)), 0) for x in seg)
+
+    # -- both directions of every pair and the forward-backward occlusion mask (dfx_calc_batch_bidir_device) ----
+    def calc_optflows_bidir_device(self, d_frames_ptr: int, pitch: int, frame_stride: int, n_frames: int, step: int,
+                                   d_fwd_ptr: int, d_bwd_ptr: int, row_pitch_floats: int, plane_stride_floats: int,
+                                   flow_stride_floats: int, alpha1: float = 0.01, alpha2: float = 0.5,
+                                   d_occ_fwd_ptr: int | None = None, d_occ_bwd_ptr: int | None = None, occ_pitch: int = 0,
+                                   occ_stride: int = 0):
+        """Frames, planes and masks resident in HBM (raw device pointers): the flows of `step` to d_fwd and those of -step to
+        d_bwd, both in the layout of calc_optflows_planar_device, every frame built once; with mask pointers the
+        forward-backward check of (fwd, bwd) to d_occ_fwd and of (bwd, fwd) to d_occ_bwd (uint8 planes, 0 = consistent,
+        1 = occluded or leaving the frame), both None: no check."""
+        self._num_pairs(n_frames, step)
+        self._arm()
+        self._check(self._L.dfx_calc_batch_bidir_device(self._h, d_frames_ptr, pitch, frame_stride, n_frames, int(step),
+                                                        d_fwd_ptr, d_bwd_ptr, row_pitch_floats, plane_stride_floats,
+                                                        flow_stride_floats, float(alpha1), float(alpha2), d_occ_fwd_ptr,
+                                                        d_occ_bwd_ptr, occ_pitch, occ_stride))
+
+    def fb_check_device(self, d_fwd_ptr: int, d_bwd_ptr: int, row_pitch_floats: int, plane_stride_floats: int,
+                        flow_stride_floats: int, n: int, alpha1: float, alpha2: float, d_occ_ptr: int, occ_pitch: int,
+                        occ_stride: int, d_err_ptr: int | None = None, err_pitch_floats: int = 0,
+                        err_stride_floats: int = 0):
+        """The forward-backward check of n planar float32 flows that are already in device memory (dfx_fb_check_device)."""
+        self._check(self._L.dfx_fb_check_device(self._h, d_fwd_ptr, d_bwd_ptr, row_pitch_floats, plane_stride_floats,
+                                                flow_stride_floats, int(n), float(alpha1), float(alpha2), d_occ_ptr,
+                                                occ_pitch, occ_stride, d_err_ptr, err_pitch_floats, err_stride_floats))
+
+    def _dev_bufs(self, sizes):
+        """Device buffers of the given byte sizes (dfx_device_malloc; at least one byte each) as a list of pointers."""
+        ptrs = []
+        try:
+            for b in sizes:
+                p = C.c_void_p()
+                self._check(self._L.dfx_device_malloc(self._h, C.byref(p), max(int(b), 1)))
+                ptrs.append(p)
+        except DfxError:
+            self._dev_free(ptrs)
+            raise
+        return ptrs
+
+    def _dev_free(self, ptrs):
+        for p in ptrs:
+            self._L.dfx_device_free(self._h, p)
+
+    def calc_optflows_bidir(self, frames_gray, step: int, check: bool = True, alpha1: float = 0.01, alpha2: float = 0.5):
+        """Both directions of every pair of a FlowBuffer, every frame uploaded and built once: (fwd, bwd, occ_fwd, occ_bwd),
+        two (M, 2, H, W) float32 arrays — fwd what calc_optflows_planar gives for `step`, bwd what it gives for -step — and
+        two (M, H, W) uint8 masks of the forward-backward check (0 = consistent, 1 = occluded or leaving the frame;
+        alpha1 / alpha2: UnFlow's constants by default), None with check=False.  The frames go to the device through
+        dfx_device_malloc / dfx_memcpy_h2d and the call is dfx_calc_batch_bidir_device."""
+        frames = [np.ascontiguousarray(f, dtype=np.uint8) for f in frames_gray]
+        n = len(frames)
+        if any(f.shape != self._frame_shape() for f in frames):
+            raise ValueError("frame shape does not match the engine")
+        m = self._num_pairs(n, step)
+        H, W = self.height, self.width
+        fwd, bwd = np.empty((m, 2, H, W), np.float32), np.empty((m, 2, H, W), np.float32)
+        occ = (np.empty((m, H, W), np.uint8), np.empty((m, H, W), np.uint8)) if check else (None, None)
+        if m == 0:
+            self._armed_seg = self._armed_src = None
+            return fwd, bwd, occ[0], occ[1]
+        pitch = self._host_pitch(frames[0])
+        fb = frames[0].nbytes
+        bufs = self._dev_bufs([n * fb, fwd.nbytes, bwd.nbytes] + ([m * H * W] * 2 if check else []))
+        try:
+            for k, f in enumerate(frames):
+                self._check(self._L.dfx_memcpy_h2d(self._h, bufs[0].value + k * fb, f.ctypes.data, fb))
+            self._arm()
+            self._check(self._L.dfx_calc_batch_bidir_device(
+                self._h, bufs[0], pitch, fb, n, int(step), bufs[1], bufs[2], W, H * W, 2 * H * W, float(alpha1),
+                float(alpha2), bufs[3] if check else None, bufs[4] if check else None, W, H * W))
+            self._check(self._L.dfx_memcpy_d2h(self._h, fwd.ctypes.data, bufs[1], fwd.nbytes))
+            self._check(self._L.dfx_memcpy_d2h(self._h, bwd.ctypes.data, bufs[2], bwd.nbytes))
+            if check:
+                self._check(self._L.dfx_memcpy_d2h(self._h, occ[0].ctypes.data, bufs[3], occ[0].nbytes))
+                self._check(self._L.dfx_memcpy_d2h(self._h, occ[1].ctypes.data, bufs[4], occ[1].nbytes))
+        finally:
+            self._dev_free(bufs)
+        return fwd, bwd, occ[0], occ[1]
+
+    def fb_check(self, fwd, bwd, alpha1: float = 0.01, alpha2: float = 0.5, want_err: bool = False):
+        """The forward-backward check of n flows given as (n, 2, H, W) float32 arrays: the (n, H, W) uint8 mask of fwd against
+        bwd (0 = consistent, 1 = occluded or leaving the frame), and with want_err=True (mask, err) with the (n, H, W)
+        float32 squared residual, +inf where the flow leaves the frame (dfx_fb_check_device)."""
+        H, W = self.height, self.width
+        fwd, bwd = np.ascontiguousarray(fwd, dtype=np.float32), np.ascontiguousarray(bwd, dtype=np.float32)
+        if fwd.ndim != 4 or fwd.shape[1:] != (2, H, W) or bwd.shape != fwd.shape:
+            raise ValueError("fwd and bwd must both be (n, 2, H, W)")
+        n = fwd.shape[0]
+        occ = np.empty((n, H, W), np.uint8)
+        err = np.empty((n, H, W), np.float32) if want_err else None
+        if n:
+            bufs = self._dev_bufs([fwd.nbytes, bwd.nbytes, occ.nbytes] + ([err.nbytes] if want_err else []))
+            try:
+                self._check(self._L.dfx_memcpy_h2d(self._h, bufs[0], fwd.ctypes.data, fwd.nbytes))
+                self._check(self._L.dfx_memcpy_h2d(self._h, bufs[1], bwd.ctypes.data, bwd.nbytes))
+                self.fb_check_device(bufs[0], bufs[1], W, H * W, 2 * H * W, n, alpha1, alpha2, bufs[2], W, H * W,
+                                     bufs[3] if want_err else None, W, H * W)
+                self._check(self._L.dfx_memcpy_d2h(self._h, occ.ctypes.data, bufs[2], occ.nbytes))
+                if want_err:
+                    self._check(self._L.dfx_memcpy_d2h(self._h, err.ctypes.data, bufs[3], err.nbytes))
+            finally:
+                self._dev_free(bufs)
+        return (occ, err) if want_err else occ
+
+    def flow_tensor_bidir(self, frames, step: int, check: bool = True, alpha1: float = 0.01, alpha2: float = 0.5, out=None):
+        """flow_tensor for both directions and the occlusion masks: (fwd, bwd, occ_fwd, occ_bwd) as torch tensors on the
+        frames' device — two (M, 2, H, W) float32 tensors of raw flow values (fwd: flow_tensor's for `step`, bwd: for -step)
+        and two (M, H, W) uint8 masks of the forward-backward check, None with check=False.  Every frame is built once.
+
+        frames: as flow_tensor takes them, strides read from the tensor.  out: optional 4-tuple (fwd, bwd, occ_fwd, occ_bwd)
+        to write into (the masks None with check=False): fwd and bwd float32 with equal strides, the two masks uint8 with
+        equal strides, innermost dimension contiguous, rows, planes and flows not overlapping.  Torch's current stream on
+        that device is synchronised before the call; the call returns with its device work complete."""
+        import torch
+
+        n, pitch, frame_stride, layout = self._tensor_frames(frames)
+        dev = frames.device
+        m = self._peek_pairs(n, step)
+        H, W = self.height, self.width
+        if out is None:
+            out = (torch.empty((m, 2, H, W), dtype=torch.float32, device=dev),
+                   torch.empty((m, 2, H, W), dtype=torch.float32, device=dev),
+                   torch.empty((m, H, W), dtype=torch.uint8, device=dev) if check else None,
+                   torch.empty((m, H, W), dtype=torch.uint8, device=dev) if check else None)
+        if len(out) != 4:
+            raise ValueError("out must be a 4-tuple (fwd, bwd, occ_fwd, occ_bwd)")
+        fwd, bwd, of, ob = out
+        for t in (fwd, bwd):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device != dev or tuple(t.shape) != (m, 2, H, W):
+                raise ValueError(f"out: fwd and bwd must be float32 tensors of shape {(m, 2, H, W)} on the frames' device")
+        if fwd.stride() != bwd.stride():
+            raise ValueError("out: fwd and bwd must have equal strides")
+        so = fwd.stride()
+        row_pitch = so[2] if H > 1 else W
+        plane_stride, flow_stride = so[1], (so[0] if m > 1 else 2 * so[1])
+        if so[3] != 1 or row_pitch < W or plane_stride < H * row_pitch or flow_stride < 2 * plane_stride:
+            raise ValueError("out: the innermost dimension must be contiguous and rows, planes and flows must not overlap")
+        occ_pitch = occ_stride = 0
+        if check:
+            for t in (of, ob):
+                if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.device != dev or tuple(t.shape) != (m, H, W):
+                    raise ValueError(f"out: the masks must be uint8 tensors of shape {(m, H, W)} on the frames' device")
+            if of.stride() != ob.stride():
+                raise ValueError("out: the two masks must have equal strides")
+            sm = of.stride()
+            occ_pitch = sm[1] if H > 1 else W
+            occ_stride = sm[0] if m > 1 else occ_pitch * H
+            if sm[2] != 1 or occ_pitch < W or occ_stride < H * occ_pitch:
+                raise ValueError("out: the masks' innermost dimension must be contiguous and rows and planes must not overlap")
+        elif of is not None or ob is not None:
+            raise ValueError("out: the masks must be None with check=False")
+        if dev.type != "cuda" or (dev.index is not None and dev.index != getattr(self, "_device", dev.index)):
+            raise ValueError("frames must be on this handle's device")
+        self._num_pairs(n, step)
+        torch.cuda.current_stream(dev).synchronize()
+
+        def call():
+            self._arm()
+            self._check(self._L.dfx_calc_batch_bidir_device(
+                self._h, frames.data_ptr() if n else None, pitch, frame_stride, n, int(step),
+                fwd.data_ptr() if m else None, bwd.data_ptr() if m else None, row_pitch, plane_stride, flow_stride,
+                float(alpha1), float(alpha2), of.data_ptr() if check and m else None,
+                ob.data_ptr() if check and m else None, occ_pitch, occ_stride))
+            return fwd, bwd, (of if check else None), (ob if check else None)
+
+        if m == 0 and check:  # (an empty tensor's data_ptr is 0: one mask pointer alone would be refused; there is nothing to do)
+            self._armed_seg = self._armed_src = None
+            return fwd, bwd, of, ob
+        if layout is not None:  # how THIS tensor lies in memory, declared for this call only
+            self._set_call_layout(*layout)
+            try:
+                return call()
+            finally:
+                self._set_call_layout(1, 0)
+        return call()
+
+    def _tensor_frames(self, frames):
+        """A torch frames tensor as the device-resident calls take it: (n, row pitch, frame stride, layout), in bytes and read
+        from the tensor's strides; layout is None, or the (layout, plane stride) to declare for the one call that reads a
+        tensor lying otherwise than the declared source format.  ValueError for a wrong type, rank or shape, a non-contiguous
+        innermost dimension, overlapping rows, planes or frames."""
+        import torch
+
+        if not isinstance(frames, torch.Tensor):
+            raise ValueError("frames must be a torch tensor")
+        if frames.dtype != torch.uint8:
+            raise ValueError("frames must be torch.uint8")
+        shape = self._frame_shape()
+        chw = bool(getattr(self, "_src_chw", False))
+        if frames.dim() != 1 + len(shape) or tuple(frames.shape[1:]) != tuple(shape):
+            raise ValueError(f"frames must be (N,) + {tuple(shape)}")
+        st = frames.stride()
+        # a channels-first SHAPE over interleaved memory — the permuted view of an NHWC batch, torch's channels_last — is read
+        # as the interleaved frames it is
+        nhwc_view = chw and st[3] == 3 and st[1] == 1
+        if not nhwc_view and (st[-1] != 1 or (len(shape) == 3 and not chw and st[2] != 3)):
+            raise ValueError("the innermost dimension of frames must be contiguous")
+        n = int(frames.shape[0])
+        plane_stride = 0
+        if nhwc_view:
+            rows, row_bytes = shape[1], shape[2] * 3
+            pitch = st[2] if rows > 1 else row_bytes
+            span = pitch * rows
+        elif chw:
+            rows, row_bytes = shape[1], shape[2]
+            pitch = st[2] if rows > 1 else row_bytes  # (the stride of a dimension of size 1 means nothing)
+            plane_stride = st[1]
+            if pitch < row_bytes or plane_stride < pitch * rows:
+                raise ValueError("frames: rows or planes overlap")
+            span = 2 * plane_stride + pitch * rows
+        else:
+            rows, row_bytes = shape[0], shape[1] * (3 if len(shape) == 3 else 1)
+            pitch = st[1] if rows > 1 else row_bytes
+            span = pitch * rows
+        frame_stride = st[0] if n > 1 else span
+        if pitch < row_bytes or frame_stride < span:
+            raise ValueError("frames: rows or frames overlap")
+        layout = None
+        if nhwc_view or (chw and plane_stride != pitch * rows):
+            layout = (0 if nhwc_view else 1, plane_stride)
+        return n, pitch, frame_stride, layout
 
     # -- flow bounding on the device (reference: convertFlowToImage, src/common.cpp:4-16) ------
     def calc_optflows_u8(self, frames_gray, step: int, bound: float, lower: float | None = None):
