@@ -11,6 +11,7 @@
 #include "jpeg_kernels.h"
 #include "prepare_kernels.h"
 #include "quantize_kernels.h"
+#include "warp_kernels.h"
 
 namespace {
 
@@ -610,6 +611,76 @@ int dfx_fb_check_device(dfx_handle h, const float *d_fwd, const float *d_bwd, si
     a.err_pitch = (long long)err_pitch_floats, a.err_stride = (long long)err_stride_floats;
     a.alpha1 = alpha1, a.alpha2 = alpha2;
     fb_check_launch(h->stream, a);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return DFX_OK;
+}
+
+// ---- the backward warp of 8-bit images by a flow (warp_kernels.hip) ----
+namespace {
+// rows of P elements, optionally three planes, images: the stride rules of the source, reference and output images
+bool warp_image_strides_bad(dfx_handle h, bool interleaved3, bool planes, size_t pitch, size_t plane, size_t image) {
+    const size_t row = (size_t)h->W * (interleaved3 ? 3 : 1);
+    if (pitch < row || pitch > ((size_t)1 << 40))
+        return true;
+    if (planes)
+        return plane < (size_t)h->H * pitch || plane > ((size_t)1 << 58) || image < 3 * plane;
+    return image < (size_t)h->H * pitch;
+}
+} // namespace
+
+int dfx_warp_device(dfx_handle h, const dfx_warp_desc *d) {
+    if (!h)
+        return DFX_ERR_INVALID;
+    (void)dfx_finish_tails(h, 0, -1);
+    if (h->algo == DFX_ALGO_FRAMES)
+        return dfx_fail(h, DFX_ERR_UNSUPPORTED, "a DFX_ALGO_FRAMES handle computes no flow");
+    if (!d)
+        return dfx_fail(h, DFX_ERR_INVALID, "NULL descriptor");
+    if (d->n < 0)
+        return dfx_fail(h, DFX_ERR_INVALID, "n must be >= 0");
+    if (d->n == 0)
+        return DFX_OK;
+    if (!d->d_src || !d->d_flow)
+        return dfx_fail(h, DFX_ERR_INVALID, "NULL device images or flows");
+    if (!d->d_out && !d->d_valid && !d->d_stats)
+        return dfx_fail(h, DFX_ERR_INVALID, "nothing asked for: d_out, d_valid and d_stats are all NULL");
+    if (d->d_stats && !d->d_ref)
+        return dfx_fail(h, DFX_ERR_INVALID, "d_stats needs d_ref");
+    if (d->channels != 1 && d->channels != 3)
+        return dfx_fail(h, DFX_ERR_INVALID, "channels must be 1 or 3");
+    if (d->channels == 3 && d->layout != DFX_SRC_INTERLEAVED && d->layout != DFX_SRC_PLANAR)
+        return dfx_fail(h, DFX_ERR_INVALID, "layout must be DFX_SRC_INTERLEAVED or DFX_SRC_PLANAR");
+    if (d->border != DFX_WARP_BORDER_ZERO && d->border != DFX_WARP_BORDER_CLAMP)
+        return dfx_fail(h, DFX_ERR_INVALID, "border must be DFX_WARP_BORDER_ZERO or DFX_WARP_BORDER_CLAMP");
+    if (d->out_dtype < DFX_PLANAR_F32 || d->out_dtype > DFX_WARP_U8)
+        return dfx_fail(h, DFX_ERR_INVALID, "out_dtype must be DFX_PLANAR_F32, DFX_PLANAR_F16, DFX_PLANAR_BF16 or DFX_WARP_U8");
+    const bool planes = d->channels == 3 && d->layout == DFX_SRC_PLANAR, il3 = d->channels == 3 && !planes;
+    if (warp_image_strides_bad(h, il3, planes, d->src_pitch, d->src_plane_stride, d->src_image_stride))
+        return dfx_fail(h, DFX_ERR_INVALID, "source images: a pitch or stride smaller than what it spans");
+    if (planar_strides_bad(h, d->row_pitch_floats, d->plane_stride_floats, d->flow_stride_floats))
+        return dfx_fail(h, DFX_ERR_INVALID, kPlanarStrides);
+    if (d->d_out && warp_image_strides_bad(h, il3, planes, d->out_pitch, d->out_plane_stride, d->out_image_stride))
+        return dfx_fail(h, DFX_ERR_INVALID, "warped images: a pitch or stride smaller than what it spans");
+    if (d->d_occ && fb_occ_bad(h, d->occ_pitch, d->occ_stride))
+        return dfx_fail(h, DFX_ERR_INVALID, kFbOcc);
+    if (d->d_valid && fb_occ_bad(h, d->valid_pitch, d->valid_stride))
+        return dfx_fail(h, DFX_ERR_INVALID, "valid planes: valid_pitch >= W and valid_stride >= H * valid_pitch are required");
+    HIPCHK(h, hipSetDevice(h->device));
+    WarpArgs a{};
+    a.src = d->d_src, a.ref = d->d_ref, a.flow = d->d_flow, a.out = d->d_out, a.occ = d->d_occ, a.valid = d->d_valid;
+    a.stats = reinterpret_cast<unsigned long long *>(d->d_stats);
+    a.n = d->n, a.w = h->W, a.h = h->H;
+    a.channels = d->channels, a.planar = planes ? 1 : 0, a.border = d->border, a.out_dtype = d->out_dtype;
+    a.src_pitch = (long long)d->src_pitch, a.src_plane = (long long)d->src_plane_stride;
+    a.src_image = (long long)d->src_image_stride;
+    a.row_pitch = (long long)d->row_pitch_floats, a.plane_stride = (long long)d->plane_stride_floats;
+    a.flow_stride = (long long)d->flow_stride_floats;
+    a.out_pitch = (long long)d->out_pitch, a.out_plane = (long long)d->out_plane_stride;
+    a.out_image = (long long)d->out_image_stride;
+    a.occ_pitch = (long long)d->occ_pitch, a.occ_stride = (long long)d->occ_stride;
+    a.valid_pitch = (long long)d->valid_pitch, a.valid_stride = (long long)d->valid_stride;
+    warp_launch(h->stream, a);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return DFX_OK;

@@ -113,6 +113,37 @@ class DfxStats(C.Structure):
         return [[self.tvl1_iters[s][w] for w in range(DFX_MAX_WARPS)] for s in range(self.levels)]
 
 
+class DfxWarpDesc(C.Structure):
+    """dfx_warp_desc of include/dfx.h, field for field."""
+    _fields_ = [
+        ("d_src", C.c_void_p),
+        ("channels", C.c_int),
+        ("layout", C.c_int),
+        ("src_pitch", C.c_size_t),
+        ("src_plane_stride", C.c_size_t),
+        ("src_image_stride", C.c_size_t),
+        ("d_ref", C.c_void_p),
+        ("d_flow", C.c_void_p),
+        ("row_pitch_floats", C.c_size_t),
+        ("plane_stride_floats", C.c_size_t),
+        ("flow_stride_floats", C.c_size_t),
+        ("n", C.c_int),
+        ("border", C.c_int),
+        ("out_dtype", C.c_int),
+        ("d_out", C.c_void_p),
+        ("out_pitch", C.c_size_t),
+        ("out_plane_stride", C.c_size_t),
+        ("out_image_stride", C.c_size_t),
+        ("d_occ", C.c_void_p),
+        ("occ_pitch", C.c_size_t),
+        ("occ_stride", C.c_size_t),
+        ("d_valid", C.c_void_p),
+        ("valid_pitch", C.c_size_t),
+        ("valid_stride", C.c_size_t),
+        ("d_stats", C.c_void_p),
+    ]
+
+
 # ------------------------------------------------------------------------------------------ build
 
 def library_path() -> str:
@@ -204,6 +235,9 @@ def load_library():
         L.dfx_calc_batch_bidir_device.restype = i
         L.dfx_fb_check_device.argtypes = [vp, vp, vp, sz, sz, sz, i, f32, f32, vp, sz, sz, vp, sz, sz]
         L.dfx_fb_check_device.restype = i
+    if hasattr(L, "dfx_warp_device"):  # a library built before the warp (DFX_LIBRARY A/B) still loads
+        L.dfx_warp_device.argtypes = [vp, C.POINTER(DfxWarpDesc)]
+        L.dfx_warp_device.restype = i
     if hasattr(L, "dfxi_probe_planar_value_as"):  # test hook (selftest.hip)
         L.dfxi_probe_planar_value_as.argtypes = [i, i, vp, C.c_float, vp, sz]
         L.dfxi_probe_planar_value_as.restype = i
@@ -345,6 +379,32 @@ def _planar_dtype(dtype):
     if dt == np.float16:
         return PLANAR_F16, dt
     raise ValueError('dtype must be np.float32, np.float16 or "bfloat16"')
+
+
+WARP_U8 = 3                               # DFX_WARP_U8: the fourth out_dtype of dfx_warp_device
+WARP_BORDERS = {"zero": 0, "clamp": 1}    # DFX_WARP_BORDER_ZERO / DFX_WARP_BORDER_CLAMP
+
+
+def _warp_border(border):
+    if not isinstance(border, str) or border not in WARP_BORDERS:
+        raise ValueError('border must be "zero" or "clamp"')
+    return WARP_BORDERS[border]
+
+
+def _warp_layout(layout):
+    if not isinstance(layout, str) or layout not in SRC_LAYOUTS:
+        raise ValueError('layout must be "hwc" or "chw"')
+    return SRC_LAYOUTS[layout]
+
+
+def _warp_dtype(dtype):
+    """(out_dtype code, numpy dtype of the array that holds the warped images): np.uint8 next to what _planar_dtype takes."""
+    if dtype is np.uint8 or (isinstance(dtype, (str, np.dtype)) and dtype == "uint8"):
+        return WARP_U8, np.dtype(np.uint8)
+    try:
+        return _planar_dtype(dtype)
+    except ValueError:
+        raise ValueError('dtype must be np.uint8, np.float32, np.float16 or "bfloat16"') from None
 
 
 def _source_codes(channels, order, layout):
@@ -940,6 +1000,263 @@ class FlowEngine:
             finally:
                 self._dev_free(bufs)
         return (occ, err) if want_err else occ
+
+    # -- the backward warp of 8-bit images by a flow, its valid mask and photometric statistics (dfx_warp_device) ----
+    def warp_device(self, d_src_ptr: int, channels: int, layout: int, src_pitch: int, src_plane_stride: int,
+                    src_image_stride: int, d_flow_ptr: int, row_pitch_floats: int, plane_stride_floats: int,
+                    flow_stride_floats: int, n: int, border: int = 0, out_dtype: int = WARP_U8,
+                    d_out_ptr: int | None = None, out_pitch: int = 0, out_plane_stride: int = 0, out_image_stride: int = 0,
+                    d_ref_ptr: int | None = None, d_occ_ptr: int | None = None, occ_pitch: int = 0, occ_stride: int = 0,
+                    d_valid_ptr: int | None = None, valid_pitch: int = 0, valid_stride: int = 0,
+                    d_stats_ptr: int | None = None):
+        """n 8-bit images that are already in device memory, sampled at the positions n planar float32 flows name: the fields
+        of dfx_warp_desc (include/dfx.h) as arguments, codes and raw pointers as the header gives them."""
+        d = DfxWarpDesc(d_src_ptr, int(channels), int(layout), src_pitch, src_plane_stride, src_image_stride, d_ref_ptr,
+                        d_flow_ptr, row_pitch_floats, plane_stride_floats, flow_stride_floats, int(n), int(border),
+                        int(out_dtype), d_out_ptr, out_pitch, out_plane_stride, out_image_stride, d_occ_ptr, occ_pitch,
+                        occ_stride, d_valid_ptr, valid_pitch, valid_stride, d_stats_ptr)
+        self._check(self._L.dfx_warp_device(self._h, C.byref(d)))
+
+    def _warp_images(self, images, layout_code, what="images"):
+        """A uint8 array of images as the warp takes it: (array, channels).  (n, H, W), (n, H, W, 3) or — channels first —
+        (n, 3, H, W)."""
+        a = np.asarray(images)
+        H, W = self.height, self.width
+        if a.dtype != np.uint8:
+            raise ValueError(f"{what} must be uint8")
+        if a.ndim == 3 and a.shape[1:] == (H, W):
+            return np.ascontiguousarray(a), 1
+        if a.ndim == 4 and a.shape[1:] == ((3, H, W) if layout_code else (H, W, 3)):
+            return np.ascontiguousarray(a), 3
+        raise ValueError(f"{what} must be (n, H, W), (n, H, W, 3) or, with layout=\"chw\", (n, 3, H, W)")
+
+    def _warp_flows(self, flows, n):
+        f = np.asarray(flows)
+        if f.dtype != np.float32 or f.shape != (n, 2, self.height, self.width):
+            raise ValueError("flows must be (n, 2, H, W) float32, one flow per image")
+        return np.ascontiguousarray(f)
+
+    def warp(self, images, flows, border: str = "zero", dtype=np.uint8, layout: str = "hwc", ref=None, occ=None,
+             want_valid: bool = False, want_stats: bool = False):
+        """Image i sampled bilinearly at p + flows[i](p) (dfx_warp_device): the warped images in the images' shape, as
+        np.uint8 (rounded to nearest even), np.float32, np.float16 or "bfloat16" (np.uint16 bit patterns).
+
+        images: uint8, (n, H, W), (n, H, W, 3) or, with layout="chw", (n, 3, H, W).  flows: (n, 2, H, W) float32.
+        border "zero": 0 where the target leaves the frame; "clamp": the sample at the nearest edge position.
+        occ: optional (n, H, W) uint8 occlusion masks (0 = visible) as fb_check gives them.  ref: optional images of the
+        same shape the warp is compared with.  want_valid: also return the (n, H, W) uint8 mask of the pixels whose target
+        stays in the frame (and is not occluded); want_stats (needs ref): also return the (n, 2) uint64 {count, sad} over
+        those pixels, sad the sum over channels of |ref - round(warp)|.  Returns out, or (out[, valid][, stats])."""
+        code, np_dt = _warp_dtype(dtype)
+        b, l = _warp_border(border), _warp_layout(layout)
+        img, ch = self._warp_images(images, l)
+        n = img.shape[0]
+        H, W = self.height, self.width
+        fl = self._warp_flows(flows, n)
+        if want_stats and ref is None:
+            raise ValueError("want_stats needs ref")
+        if ref is not None:
+            ref, _ = self._warp_images(ref, l, "ref")
+            if ref.shape != img.shape:
+                raise ValueError("ref must have the shape of images")
+        if occ is not None:
+            occ = np.asarray(occ)
+            if occ.dtype != np.uint8 or occ.shape != (n, H, W):
+                raise ValueError("occ must be (n, H, W) uint8")
+            occ = np.ascontiguousarray(occ)
+        out = np.empty(img.shape, np_dt)
+        valid = np.empty((n, H, W), np.uint8) if want_valid else None
+        stats = np.zeros((n, 2), np.uint64) if want_stats else None
+        if n:
+            planes = ch == 3 and l == 1
+            pitch = W * (1 if ch == 1 or planes else 3)
+            plane = H * W if planes else 0
+            image = ch * H * W
+            ins = [img, fl] + [x for x in (ref, occ) if x is not None]
+            outs = [out] + [x for x in (valid, stats) if x is not None]
+            bufs = self._dev_bufs([x.nbytes for x in ins + outs])
+            try:
+                for p, x in zip(bufs, ins):
+                    self._check(self._L.dfx_memcpy_h2d(self._h, p, x.ctypes.data, x.nbytes))
+                at = {id(x): p for p, x in zip(bufs, ins + outs)}
+                ptr = lambda x: None if x is None else at[id(x)]  # noqa: E731
+                self.warp_device(ptr(img), ch, l if ch == 3 else 0, pitch, plane, image, ptr(fl), W, H * W, 2 * H * W, n, b, code,
+                                 ptr(out), pitch, plane, image, ptr(ref), ptr(occ), W, H * W, ptr(valid), W, H * W, ptr(stats))
+                for x in outs:
+                    self._check(self._L.dfx_memcpy_d2h(self._h, x.ctypes.data, at[id(x)], x.nbytes))
+            finally:
+                self._dev_free(bufs)
+        res = (out,) + ((valid,) if want_valid else ()) + ((stats,) if want_stats else ())
+        return res if len(res) > 1 else out
+
+    def warp_error(self, frames, flows, step: int, occ=None):
+        """The photometric error of the flows of a FlowBuffer: flow i of `step` is a -> b (for step > 0 frames i -> i + step,
+        for step < 0 frames i - step -> i: the pair rule of calc_optflows), frame b is warped back by it and compared with
+        frame a.  Returns the float64 array of the M = max(N - |step|, 0) mean absolute errors in grey levels, sad / (count *
+        channels) over the pixels whose target stays in the frame (and, with occ — (M, H, W) uint8, 0 = visible — is not
+        occluded); NaN where no pixel counts.  frames: N uint8 frames (H, W) or (H, W, 3); flows: (M, 2, H, W) float32.
+        Only the statistics are computed on the device (no warped image is stored)."""
+        step = int(step)
+        if step == 0:
+            raise ValueError("step must not be 0")
+        H, W = self.height, self.width
+        fr = np.asarray(frames)
+        if fr.dtype != np.uint8 or fr.ndim not in (3, 4) or fr.shape[1:3] != (H, W) or (fr.ndim == 4 and fr.shape[3] != 3):
+            raise ValueError("frames must be N uint8 frames of (H, W) or (H, W, 3)")
+        fr = np.ascontiguousarray(fr)
+        ch = 1 if fr.ndim == 3 else 3
+        m = max(fr.shape[0] - abs(step), 0)
+        fl = self._warp_flows(flows, m)
+        if occ is not None:
+            occ = np.asarray(occ)
+            if occ.dtype != np.uint8 or occ.shape != (m, H, W):
+                raise ValueError("occ must be (M, H, W) uint8")
+            occ = np.ascontiguousarray(occ)
+        stats = np.zeros((m, 2), np.uint64)
+        if m:
+            fb = ch * H * W
+            bufs = self._dev_bufs([fr.nbytes, fl.nbytes, stats.nbytes] + ([occ.nbytes] if occ is not None else []))
+            try:
+                self._check(self._L.dfx_memcpy_h2d(self._h, bufs[0], fr.ctypes.data, fr.nbytes))
+                self._check(self._L.dfx_memcpy_h2d(self._h, bufs[1], fl.ctypes.data, fl.nbytes))
+                if occ is not None:
+                    self._check(self._L.dfx_memcpy_h2d(self._h, bufs[3], occ.ctypes.data, occ.nbytes))
+                first_a, first_b = (0, step) if step > 0 else (-step, 0)  # flow 0 is frame first_a -> frame first_b
+                self.warp_device(bufs[0].value + first_b * fb, ch, 0, W * ch, 0, fb, bufs[1], W, H * W, 2 * H * W, m,
+                                 d_ref_ptr=bufs[0].value + first_a * fb, d_occ_ptr=bufs[3] if occ is not None else None,
+                                 occ_pitch=W, occ_stride=H * W, d_stats_ptr=bufs[2])
+                self._check(self._L.dfx_memcpy_d2h(self._h, stats.ctypes.data, bufs[2], stats.nbytes))
+            finally:
+                self._dev_free(bufs)
+        cnt, sad = stats[:, 0].astype(np.float64), stats[:, 1].astype(np.float64)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return np.where(cnt > 0, sad / (cnt * ch), np.nan)
+
+    def _warp_tensor_images(self, t, layout, what):
+        """A torch uint8 / output tensor of images as the warp takes it, read from its shape and strides: (channels, layout
+        code of how it lies in MEMORY, row pitch, plane stride, image stride, whether the SHAPE is channels-first), strides in
+        elements.  The shape is (n, H, W), (n, 3, H, W) or (n, H, W, 3); memory may be interleaved or planar under either shape
+        (a permuted view is read where it lies)."""
+        H, W = self.height, self.width
+        n = t.shape[0] if t.dim() else 0
+        st = t.stride()
+        if t.dim() == 3 and tuple(t.shape[1:]) == (H, W):
+            pitch = st[1] if H > 1 else W
+            image = st[0] if n > 1 else H * pitch
+            if (st[2] != 1 and W > 1) or pitch < W or image < H * pitch:
+                raise ValueError(f"{what}: the innermost dimension must be contiguous and rows and images must not overlap")
+            return 1, 0, pitch, 0, image, False
+        chw, hwc = tuple(t.shape[1:]) == (3, H, W), tuple(t.shape[1:]) == (H, W, 3)
+        if t.dim() != 4 or not (chw or hwc):
+            raise ValueError(f"{what} must be (n, H, W), (n, 3, H, W) or (n, H, W, 3)")
+        if chw and hwc:  # H = W = 3: the shape does not say
+            if layout is None:
+                raise ValueError(f'{what}: H = W = 3, say layout="chw" or "hwc"')
+            chw = _warp_layout(layout) == 1
+        sc, sy, sx = (st[1], st[2], st[3]) if chw else (st[3], st[1], st[2])  # strides of channel, row, pixel
+        if sc == 1 and (sx == 3 or W == 1):  # interleaved pixels
+            pitch = sy if H > 1 else 3 * W
+            image = st[0] if n > 1 else H * pitch
+            if pitch < 3 * W or image < H * pitch:
+                raise ValueError(f"{what}: rows and images must not overlap")
+            return 3, 0, pitch, 0, image, chw
+        if sx == 1 or W == 1:  # three planes
+            pitch = sy if H > 1 else W
+            plane = sc
+            image = st[0] if n > 1 else 3 * plane
+            if pitch < W or plane < H * pitch or image < 3 * plane:
+                raise ValueError(f"{what}: rows, planes and images must not overlap")
+            return 3, 1, pitch, plane, image, chw
+        raise ValueError(f"{what}: pixels must be interleaved (channel stride 1, pixel stride 3) or planar (pixel stride 1)")
+
+    def warp_tensor(self, images, flows, border: str = "zero", dtype=None, layout: str | None = None, ref=None, occ=None,
+                    want_valid: bool = False, want_stats: bool = False, out=None):
+        """warp for torch tensors on this handle's device, read and written where they lie.
+
+        images: torch.uint8, (n, H, W), (n, 3, H, W) or (n, H, W, 3); the memory layout — interleaved or three planes — and
+        every stride are taken from the tensor, so the NCHW view of an NHWC batch or a slice of a larger tensor is read
+        without a copy (layout is needed only for H = W = 3, where the shape does not say which it is).  flows: (n, 2, H, W)
+        torch.float32 with a contiguous innermost dimension, e.g. what flow_tensor returns.  dtype: torch.uint8 (default),
+        torch.float32, torch.float16 or torch.bfloat16.  out: optional tensor of that dtype and the images' shape whose
+        memory layout is the images' (interleaved or planar); otherwise the result is allocated in the images' memory
+        layout and returned in the images' shape.  ref: optional uint8 tensor of the images' shape (copied only if its
+        strides differ from the images'); occ: optional (n, H, W) uint8 masks (0 = visible).  want_valid / want_stats as
+        warp: valid is an (n, H, W) uint8 tensor, stats an (n, 2) torch.int64 tensor {count, sad}.
+
+        Torch's current stream on that device is synchronised before the call; the call returns with its device work
+        complete.  Raises ValueError before the library is reached for a wrong dtype, device, shape or stride."""
+        import torch
+
+        codes = {torch.uint8: WARP_U8, torch.float32: PLANAR_F32, torch.float16: PLANAR_F16, torch.bfloat16: PLANAR_BF16}
+        tdt = torch.uint8 if dtype is None else dtype
+        if tdt not in codes:
+            raise ValueError("dtype must be torch.uint8, torch.float32, torch.float16 or torch.bfloat16")
+        b = _warp_border(border)
+        if layout is not None:
+            _warp_layout(layout)
+        if not isinstance(images, torch.Tensor) or images.dtype != torch.uint8:
+            raise ValueError("images must be a torch.uint8 tensor")
+        H, W = self.height, self.width
+        ch, mem, pitch, plane, image, chw = self._warp_tensor_images(images, layout, "images")
+        n = images.shape[0]
+        dev = images.device
+        if not isinstance(flows, torch.Tensor) or flows.dtype != torch.float32 or tuple(flows.shape) != (n, 2, H, W):
+            raise ValueError("flows must be an (n, 2, H, W) torch.float32 tensor, one flow per image")
+        sf = flows.stride()
+        row_pitch = sf[2] if H > 1 else W
+        flow_plane, flow_stride = sf[1], (sf[0] if n > 1 else 2 * sf[1])
+        if (sf[3] != 1 and W > 1) or row_pitch < W or flow_plane < H * row_pitch or flow_stride < 2 * flow_plane:
+            raise ValueError("flows: the innermost dimension must be contiguous and rows, planes and flows must not overlap")
+        if want_stats and ref is None:
+            raise ValueError("want_stats needs ref")
+        if ref is not None:
+            if not isinstance(ref, torch.Tensor) or ref.dtype != torch.uint8 or ref.shape != images.shape:
+                raise ValueError("ref must be a torch.uint8 tensor of the images' shape")
+        occ_pitch = occ_stride = 0
+        if occ is not None:
+            if not isinstance(occ, torch.Tensor) or occ.dtype != torch.uint8 or tuple(occ.shape) != (n, H, W):
+                raise ValueError("occ must be an (n, H, W) torch.uint8 tensor")
+            so = occ.stride()
+            occ_pitch = so[1] if H > 1 else W
+            occ_stride = so[0] if n > 1 else H * occ_pitch
+            if (so[2] != 1 and W > 1) or occ_pitch < W or occ_stride < H * occ_pitch:
+                raise ValueError("occ: the innermost dimension must be contiguous and rows and masks must not overlap")
+        if out is not None:
+            if not isinstance(out, torch.Tensor) or out.dtype != tdt or out.shape != images.shape:
+                raise ValueError(f"out must be a {tdt} tensor of the images' shape")
+            och, omem, out_pitch, out_plane, out_image, _ = self._warp_tensor_images(out, layout, "out")
+            if (och, omem) != (ch, mem):
+                raise ValueError("out must lie in memory as the images do (interleaved or planar)")
+        others = [t for t in (flows, ref, occ, out) if t is not None]
+        if dev.type != "cuda" or (dev.index is not None and dev.index != getattr(self, "_device", dev.index)):
+            raise ValueError("images must be on this handle's device")
+        if any(t.device != dev for t in others):
+            raise ValueError("flows, ref, occ and out must be on the images' device")
+        if out is None:
+            if ch == 3 and mem == 0:  # interleaved memory, whatever the shape's order
+                base = torch.empty((n, H, W, 3), dtype=tdt, device=dev)
+                out = base.permute(0, 3, 1, 2) if chw else base
+                out_pitch, out_plane, out_image = 3 * W, 0, 3 * H * W
+            elif ch == 3:
+                base = torch.empty((n, 3, H, W), dtype=tdt, device=dev)
+                out = base if chw else base.permute(0, 2, 3, 1)
+                out_pitch, out_plane, out_image = W, H * W, 3 * H * W
+            else:
+                out = torch.empty((n, H, W), dtype=tdt, device=dev)
+                out_pitch, out_plane, out_image = W, 0, H * W
+        if ref is not None and n and ref.stride() != images.stride():
+            ref = torch.empty_strided(images.shape, images.stride(), dtype=torch.uint8, device=dev).copy_(ref)
+        valid = torch.empty((n, H, W), dtype=torch.uint8, device=dev) if want_valid else None
+        stats = torch.zeros((n, 2), dtype=torch.int64, device=dev) if want_stats else None
+        torch.cuda.current_stream(dev).synchronize()
+        if n:
+            self.warp_device(images.data_ptr(), ch, mem, pitch, plane, image, flows.data_ptr(), row_pitch, flow_plane,
+                             flow_stride, n, b, codes[tdt], out.data_ptr(), out_pitch, out_plane, out_image,
+                             ref.data_ptr() if ref is not None else None, occ.data_ptr() if occ is not None else None,
+                             occ_pitch, occ_stride, valid.data_ptr() if want_valid else None, W, H * W,
+                             stats.data_ptr() if want_stats else None)
+        res = (out,) + ((valid,) if want_valid else ()) + ((stats,) if want_stats else ())
+        return res if len(res) > 1 else out
 
     def flow_tensor_bidir(self, frames, step: int, check: bool = True, alpha1: float = 0.01, alpha2: float = 0.5, out=None):
         """flow_tensor for both directions and the occlusion masks: (fwd, bwd, occ_fwd, occ_bwd) as torch tensors on the
