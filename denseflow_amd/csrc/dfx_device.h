@@ -29,8 +29,8 @@ enum : int {
     PL_COUNT_GAMMA
 };
 // plane of channel ch = 0, 1, 2 (u1, u2, u3) in ping-pong set S: u, and the first of its two dual planes (the second follows it)
-DFX_HD int tvl1_pl_u(int ch, int S) { return ch < 2 ? PL_U1_0 + 2 * S + ch : PL_U3_0 + S; }
-DFX_HD int tvl1_pl_p(int ch, int S) { return ch < 2 ? PL_P11_0 + 4 * S + 2 * ch : PL_P31_0 + 2 * S; }
+DFX_HD constexpr int tvl1_pl_u(int ch, int S) { return ch < 2 ? PL_U1_0 + 2 * S + ch : PL_U3_0 + S; }
+DFX_HD constexpr int tvl1_pl_p(int ch, int S) { return ch < 2 ? PL_P11_0 + 4 * S + 2 * ch : PL_P31_0 + 2 * S; }
 
 struct PairDesc {
     int frame_a; // frame slot of I0

@@ -1,14 +1,28 @@
-// tvl1_device_common.h — device helpers shared by tvl1_kernels.hip (step kernels, level control) and tvl1_warp_kernels.hip
-// (the backward warp as its own kernel): plane addressing, the deterministic reductions, the arrival ticket that lets the
-// last workgroup of a pair advance its state machine, and A.5's backward warp of one pixel.  Device code only.
+// tvl1_device_common.h — device helpers shared by tvl1_kernels.hip (step kernels, level control), tvl1_head_kernels.hip (the
+// warp-and-head kernel) and tvl1_warp_kernels.hip (the backward warp as its own kernel): plane addressing, the deterministic
+// reductions, the arrival ticket that lets the last workgroup of a pair advance its state machine, the tails that do so at
+// the end of a warp phase and of a segment of the inner loop, and A.5's backward warp of one pixel.  Device code, but for
+// tvl1_with_math, which the launchers of the kernels templated on the arithmetic mode share.
 #pragma once
 
 #include <hip/hip_runtime.h>
+
+#include <type_traits>
 
 #include "dfx_device.h"
 #include "tvl1_math.h"
 
 #define AGENT __HIP_MEMORY_SCOPE_AGENT
+
+// Measurement builds of the TVL1 kernels (scripts/build_variant.sh; WRONG flows): non-zero, the inner loop never converges
+// (end_segment_tile), so that every build runs the same step schedule; 1: the tile function's memory phases without its
+// arithmetic, 2: its arithmetic without the HBM traffic (tvl1_tile.h).  Such a library must be asked for twice.
+#ifndef DFX_TVL1_DEBUG
+#define DFX_TVL1_DEBUG 0
+#endif
+#if DFX_TVL1_DEBUG && !DFX_MEASUREMENT_BUILD
+#error "DFX_TVL1_DEBUG computes wrong flows: build a measurement library with -DDFX_MEASUREMENT_BUILD=1 as well"
+#endif
 
 // ------------------------------------------------------------------------------------------------
 // small helpers
@@ -125,6 +139,66 @@ __device__ __forceinline__ void finish_level(const Tvl1LevelCtx &c, int pair, co
         __hip_atomic_store(c.level_done_count, 0u, __ATOMIC_RELAXED, AGENT);
         __hip_atomic_store((int *)c.host_done_flag, c.done_token, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
+}
+
+// A workgroup of a pair in phase WARP has written its pixels: take the ticket; the pair's last one starts the inner loop.
+__device__ __forceinline__ void end_warp_tile(const Tvl1LevelCtx &c, int pair, Tvl1State *st, unsigned nblk, int step_id,
+                                              int *lds_flag) {
+    if (arrive_is_last(st, nblk, lds_flag) && threadIdx.x == 0) {
+        // advance the state in place: every other workgroup of this pair has already arrived
+        tvl1_begin_loop(*st, c.loop, step_id);
+        if (st->phase == TVL1_PH_LEVEL_DONE)
+            finish_level(dfx_kernarg_ctx(), pair, *st, step_id); // (once per pair and level: the context from the kernel-argument segment)
+        __hip_atomic_store(&st->ticket, 0u, __ATOMIC_RELAXED, AGENT);
+    }
+}
+
+// The tail of every launch that ends a segment of the inner loop (all step kernels and the warp-and-head kernel): publish
+// the workgroup's share of sum(diff) in its slot, take the ticket; the last workgroup of the pair sums the nblk partials in
+// index order (deterministic: the convergence check and the iteration tables do not depend on arrival order) and advances the
+// state (A.4) with `end(state, error)`: tvl1_end_segment, or tvl1_end_head in the warp-and-head kernel.
+template <class EndFn>
+__device__ __forceinline__ void end_segment_tile(const Tvl1LevelCtx &c, int pair, Tvl1State *st, bool do_check, unsigned nblk,
+                                                 int slot, int step_id, double dsum, double *lds_red, int *lds_flag,
+                                                 EndFn end) {
+    const int tid = threadIdx.x;
+    double *partials = c.partials + (long long)pair * c.partials_stride;
+    if (do_check) {
+        const double bs = block_reduce_sum_f64(dsum, lds_red);
+        if (tid == 0)
+            publish_partial(partials + slot, bs);
+    }
+    if (!arrive_is_last(st, nblk, lds_flag))
+        return;
+    double err = 0.0;
+    if (do_check) {
+        double acc = 0.0;
+        for (unsigned i = tid; i < nblk; i += blockDim.x)
+            acc += read_partial(partials + i);
+        err = block_reduce_sum_f64(acc, lds_red);
+    }
+#if DFX_TVL1_DEBUG // measurement builds: never converge, so every build runs the same step schedule
+    err = 1e300;
+#endif
+    if (tid == 0) {
+        end(*st, err);
+        if (st->phase == TVL1_PH_LEVEL_DONE)
+            finish_level(dfx_kernarg_ctx(), pair, *st, step_id); // (once per pair and level: the context from the kernel-argument segment)
+        __hip_atomic_store(&st->ticket, 0u, __ATOMIC_RELAXED, AGENT);
+    }
+}
+
+// Host side: the run-time dfx_params.tvl1_math value as a template argument, f(std::integral_constant<int, MATH>()).
+template <class F>
+static inline void tvl1_with_math(int math, F f) {
+    if (math == 1)
+        f(std::integral_constant<int, 1>());
+    else if (math == TVL1_HYP_SQRT)
+        f(std::integral_constant<int, TVL1_HYP_SQRT>());
+    else if (math == TVL1_HYP_LIBM)
+        f(std::integral_constant<int, TVL1_HYP_LIBM>());
+    else
+        f(std::integral_constant<int, 0>());
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -437,31 +437,8 @@ __device__ __forceinline__ void warp_head(const Tvl1LevelCtx &c, int step_id) {
         dsum = head_tile<false, MATH, LEAN>(c, b, lds_raw, plan, xs, ys, tp.own_lo != 0, tp.own_hi != 0, p_zero);
 
     // the tile's share of sum(diff), the arrival ticket, and — in the pair's last workgroup — the state transition
-    const int tid = threadIdx.x;
-    double *partials = c.partials + (long long)b * c.partials_stride;
-    if (plan.do_check) {
-        const double bs = block_reduce_sum_f64(dsum, lds_red);
-        if (tid == 0)
-            publish_partial(partials + blockIdx.x, bs);
-    }
-    if (!arrive_is_last(st, nblk, &lds_flag))
-        return;
-    double err = 0.0;
-    if (plan.do_check) {
-        double acc = 0.0;
-        for (unsigned i = tid; i < nblk; i += blockDim.x)
-            acc += read_partial(partials + i);
-        err = block_reduce_sum_f64(acc, lds_red);
-    }
-#if DFX_TVL1_DEBUG // measurement builds: never converge, so every build runs the same step schedule
-    err = 1e300;
-#endif
-    if (tid == 0) {
-        tvl1_end_head(*st, c.loop, plan, step_id, err);
-        if (st->phase == TVL1_PH_LEVEL_DONE)
-            finish_level(dfx_kernarg_ctx(), b, *st, step_id); // (once per pair and level: the context from the kernel-argument segment)
-        __hip_atomic_store(&st->ticket, 0u, __ATOMIC_RELAXED, AGENT);
-    }
+    end_segment_tile(c, b, st, plan.do_check != 0, nblk, (int)blockIdx.x, step_id, dsum, lds_red, &lds_flag,
+                     [&](Tvl1State &s, double err) { tvl1_end_head(s, c.loop, plan, step_id, err); });
 }
 
 } // namespace
@@ -492,21 +469,10 @@ int tvl1_head_blocks(const Tvl1LevelCtx &c) { return tvl1_step_grid(c.w, c.h, HD
 
 void tvl1_launch_warp_head(hipStream_t s, const Tvl1LevelCtx &c, int step_id, int math, bool regs) {
     const dim3 grid(tvl1_head_blocks(c), 1, c.n_pairs), block(64 * HD_NW);
-    if (regs) {
-        if (math == 1)
-            hipLaunchKernelGGL((k_tvl1_warp_head_regs<1>), grid, block, 0, s, c, step_id);
-        else if (math == TVL1_HYP_SQRT)
-            hipLaunchKernelGGL((k_tvl1_warp_head_regs<TVL1_HYP_SQRT>), grid, block, 0, s, c, step_id);
-        else if (math == TVL1_HYP_LIBM)
-            hipLaunchKernelGGL((k_tvl1_warp_head_regs<TVL1_HYP_LIBM>), grid, block, 0, s, c, step_id);
+    tvl1_with_math(math, [&](auto m) {
+        if (regs)
+            hipLaunchKernelGGL((k_tvl1_warp_head_regs<decltype(m)::value>), grid, block, 0, s, c, step_id);
         else
-            hipLaunchKernelGGL((k_tvl1_warp_head_regs<0>), grid, block, 0, s, c, step_id);
-    } else if (math == 1)
-        hipLaunchKernelGGL((k_tvl1_warp_head<1>), grid, block, 0, s, c, step_id);
-    else if (math == TVL1_HYP_SQRT)
-        hipLaunchKernelGGL((k_tvl1_warp_head<TVL1_HYP_SQRT>), grid, block, 0, s, c, step_id);
-    else if (math == TVL1_HYP_LIBM)
-        hipLaunchKernelGGL((k_tvl1_warp_head<TVL1_HYP_LIBM>), grid, block, 0, s, c, step_id);
-    else
-        hipLaunchKernelGGL((k_tvl1_warp_head<0>), grid, block, 0, s, c, step_id);
+            hipLaunchKernelGGL((k_tvl1_warp_head<decltype(m)::value>), grid, block, 0, s, c, step_id);
+    });
 }

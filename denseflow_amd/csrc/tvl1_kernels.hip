@@ -19,11 +19,6 @@
 #include "tvl1_math_pk.h"
 #include "tvl1_device_common.h"
 
-
-#ifndef DFX_TVL1_DEBUG
-#define DFX_TVL1_DEBUG 0
-#endif
-
 // ------------------------------------------------------------------------------------------------
 // frame preparation: u8 -> f32 (E.2), pyramid resize (E.1), centred gradient (A.3)
 
@@ -174,35 +169,81 @@ __global__ __launch_bounds__(256) void k_tvl1_merge_planar(Tvl1LevelCtx c, DfxPl
 }
 
 // ------------------------------------------------------------------------------------------------
-// A.6 primal update of one pixel from planes in global memory (simple variant)
+// A.6 primal update of one pixel from planes in global memory (simple variant), NC = 2 channels (u1, u2) or 3 (with the
+// illumination channel u3 of dfx_params.tvl1_gamma, SURVEY.md Appendix A "with gamma"; its planes: see further down).
+// With NC = 2 this is tvl1_threshold followed by v + theta * div, operation for operation: no gamma term is formed.
 
+// channels 0 and 1 live where the two-channel kernels have always read them
+static_assert(tvl1_pl_u(0, 0) == PL_U1_0 && tvl1_pl_u(1, 0) == PL_U2_0 && tvl1_pl_u(0, 1) == PL_U1_0 + 2 &&
+                  tvl1_pl_u(1, 1) == PL_U2_0 + 2,
+              "u1 / u2 of set S are planes PL_U1_0 + 2S, PL_U2_0 + 2S");
+static_assert(tvl1_pl_p(0, 0) == PL_P11_0 && tvl1_pl_p(0, 0) + 1 == PL_P12_0 && tvl1_pl_p(1, 0) == PL_P21_0 &&
+                  tvl1_pl_p(1, 0) + 1 == PL_P22_0 && tvl1_pl_p(0, 1) == PL_P11_0 + 4 && tvl1_pl_p(0, 1) + 1 == PL_P12_0 + 4 &&
+                  tvl1_pl_p(1, 1) == PL_P21_0 + 4 && tvl1_pl_p(1, 1) + 1 == PL_P22_0 + 4,
+              "p11, p12, p21, p22 of set S are planes PL_P11_0 + 4S ... PL_P22_0 + 4S");
+
+template <int NC>
 struct PlanesRO {
-    const float *I1wx, *I1wy, *grad, *rho_c, *u1, *u2, *p11, *p12, *p21, *p22;
+    const float *I1wx, *I1wy, *grad, *rho_c, *u[NC], *pa[NC], *pb[NC];
 };
 
-__device__ __forceinline__ void estimate_u_px(const PlanesRO &P, int pitch, int x, int y, float l_t, float theta,
-                                              float &u1n, float &u2n, float &u1o, float &u2o) {
+template <int NC>
+__device__ __forceinline__ void estimate_u_px(const PlanesRO<NC> &P, int pitch, int x, int y, float l_t, float theta,
+                                              float gamma, float (&un)[NC], float (&uo)[NC]) {
     const long long o = (long long)y * pitch + x;
-    u1o = P.u1[o];
-    u2o = P.u2[o];
-    float v1, v2;
-    tvl1_threshold(P.I1wx[o], P.I1wy[o], P.grad[o], P.rho_c[o], u1o, u2o, l_t, v1, v2);
+#pragma unroll
+    for (int ch = 0; ch < NC; ++ch)
+        uo[ch] = P.u[ch][o];
+    const float I1wx = P.I1wx[o], I1wy = P.I1wy[o], grad = P.grad[o];
+    float dot = I1wx * uo[0] + I1wy * uo[1];
+    if (NC == 3)
+        dot = dot + gamma * uo[NC - 1];
+    const float rho = P.rho_c[o] + dot;
+    const float lg = l_t * grad;
+    const float fi = tvl1_div(-rho, grad);
+    const bool c1 = rho < -lg, c2 = rho > lg, c3 = grad > FLT_EPSILON;
+    const float w[3] = {I1wx, I1wy, gamma};
     const bool hl = x > 0, hu = y > 0;
-    const float p11 = P.p11[o], p12 = P.p12[o], p21 = P.p21[o], p22 = P.p22[o];
-    const float p11l = hl ? P.p11[o - 1] : 0.0f, p21l = hl ? P.p21[o - 1] : 0.0f;
-    const float p12u = hu ? P.p12[o - pitch] : 0.0f, p22u = hu ? P.p22[o - pitch] : 0.0f;
-    const float div1 = tvl1_divergence(p11, p11l, p12, p12u, hl, hu);
-    const float div2 = tvl1_divergence(p21, p21l, p22, p22u, hl, hu);
-    u1n = v1 + theta * div1;
-    u2n = v2 + theta * div2;
+#pragma unroll
+    for (int ch = 0; ch < NC; ++ch) {
+        const float a = l_t * w[ch], bq = fi * w[ch];
+        const float d = c1 ? a : (c2 ? -a : (c3 ? bq : 0.0f));
+        const float pal = hl ? P.pa[ch][o - 1] : 0.0f, pbu = hu ? P.pb[ch][o - pitch] : 0.0f;
+        un[ch] = (uo[ch] + d) + theta * tvl1_divergence(P.pa[ch][o], pal, P.pb[ch][o], pbu, hl, hu);
+    }
+}
+
+// A workgroup has stored its pixels of a step: where the step ends its segment, the segment tail (tvl1_device_common.h).
+__device__ __forceinline__ void end_iter_tile(const Tvl1LevelCtx &c, int b, Tvl1State *st, const Tvl1StepPlan &plan,
+                                              unsigned nblk, int slot, int step_id, double dsum, double *lds_red,
+                                              int *lds_flag) {
+    if (plan.is_last)
+        end_segment_tile(c, b, st, plan.do_check != 0, nblk, slot, step_id, dsum, lds_red, lds_flag,
+                         [&](Tvl1State &s, double err) { tvl1_end_segment(s, c.loop, plan, step_id, err); });
+}
+
+// A.5 for one pixel of the simple kernel's warp phase (the warp reads u1, u2 only, with or without u3)
+__device__ __forceinline__ void simple_warp_px(const Tvl1LevelCtx &c, int b, int cur, int x, int y) {
+    const long long o = (long long)y * c.pitch + x;
+    const PairDesc pd = c.pairs[b];
+    const float *I0 = c.frame_I + (long long)pd.frame_a * c.frame_stride + c.lvl_off;
+    const long long fb = (long long)pd.frame_b * c.frame_stride + c.lvl_off;
+    const float u1v = pair_plane(c, b, PL_U1_0 + 2 * cur)[o];
+    const float u2v = pair_plane(c, b, PL_U2_0 + 2 * cur)[o];
+    const WarpOut r = warp_backward_px(I0, c.frame_I + fb, c.frame_Ix + fb, c.frame_Iy + fb, c.w, c.h, c.pitch, x, y, u1v, u2v);
+    pair_plane(c, b, PL_I1WX)[o] = r.I1wx;
+    pair_plane(c, b, PL_I1WY)[o] = r.I1wy;
+    pair_plane(c, b, PL_GRAD)[o] = r.grad;
+    pair_plane(c, b, PL_RHOC)[o] = r.rho_c;
 }
 
 // ------------------------------------------------------------------------------------------------
-// The step kernel, simple variant: one pixel per thread, one inner iteration per step.
-// Each thread recomputes the new u of its right and lower neighbours instead of exchanging it,
+// The step kernel, simple variant (impl 1, the cross-check form; NC = 3 with tvl1_gamma): one pixel per thread, one inner
+// iteration per step.  Each thread recomputes the new u of its right and lower neighbours instead of exchanging it,
 // so a step is a single launch with no intra-kernel dependency (the fused variant shares them
 // through LDS).  Reads ping-pong set `src`, writes set `src ^ 1`.
 
+template <int NC>
 __global__ __launch_bounds__(256) void k_tvl1_step_simple(Tvl1LevelCtx c, int step_id) {
     __shared__ double lds_red[8];
     __shared__ int lds_flag;
@@ -221,27 +262,9 @@ __global__ __launch_bounds__(256) void k_tvl1_step_simple(Tvl1LevelCtx c, int st
     const long long o = (long long)y * c.pitch + x;
 
     if (phase == TVL1_PH_WARP) {
-        const int cur = st->cur;
-        if (inside) {
-            const PairDesc pd = c.pairs[b];
-            const float *I0 = c.frame_I + (long long)pd.frame_a * c.frame_stride + c.lvl_off;
-            const long long fb = (long long)pd.frame_b * c.frame_stride + c.lvl_off;
-            const float u1v = pair_plane(c, b, PL_U1_0 + 2 * cur)[o];
-            const float u2v = pair_plane(c, b, PL_U2_0 + 2 * cur)[o];
-            const WarpOut r = warp_backward_px(I0, c.frame_I + fb, c.frame_Ix + fb, c.frame_Iy + fb, c.w, c.h,
-                                               c.pitch, x, y, u1v, u2v);
-            pair_plane(c, b, PL_I1WX)[o] = r.I1wx;
-            pair_plane(c, b, PL_I1WY)[o] = r.I1wy;
-            pair_plane(c, b, PL_GRAD)[o] = r.grad;
-            pair_plane(c, b, PL_RHOC)[o] = r.rho_c;
-        }
-        if (arrive_is_last(st, nblk, &lds_flag) && threadIdx.x == 0) {
-            // advance the state in place: every other workgroup of this pair has already arrived
-            tvl1_begin_loop(*st, c.loop, step_id);
-            if (st->phase == TVL1_PH_LEVEL_DONE)
-                finish_level(dfx_kernarg_ctx(), b, *st, step_id); // (once per pair and level: the context from the kernel-argument segment)
-            __hip_atomic_store(&st->ticket, 0u, __ATOMIC_RELAXED, AGENT);
-        }
+        if (inside)
+            simple_warp_px(c, b, st->cur, x, y);
+        end_warp_tile(c, b, st, nblk, step_id, &lds_flag);
         return;
     }
 
@@ -251,76 +274,54 @@ __global__ __launch_bounds__(256) void k_tvl1_step_simple(Tvl1LevelCtx c, int st
     if (plan.n_iters <= 0)
         return;
     const int S = plan.src, D = S ^ 1;
-    PlanesRO P;
+    PlanesRO<NC> P;
     P.I1wx = pair_plane(c, b, PL_I1WX);
     P.I1wy = pair_plane(c, b, PL_I1WY);
     P.grad = pair_plane(c, b, PL_GRAD);
     P.rho_c = pair_plane(c, b, PL_RHOC);
-    P.u1 = pair_plane(c, b, PL_U1_0 + 2 * S);
-    P.u2 = pair_plane(c, b, PL_U2_0 + 2 * S);
-    P.p11 = pair_plane(c, b, PL_P11_0 + 4 * S);
-    P.p12 = pair_plane(c, b, PL_P12_0 + 4 * S);
-    P.p21 = pair_plane(c, b, PL_P21_0 + 4 * S);
-    P.p22 = pair_plane(c, b, PL_P22_0 + 4 * S);
+#pragma unroll
+    for (int ch = 0; ch < NC; ++ch) {
+        P.u[ch] = pair_plane(c, b, tvl1_pl_u(ch, S));
+        P.pa[ch] = pair_plane(c, b, tvl1_pl_p(ch, S));
+        P.pb[ch] = pair_plane(c, b, tvl1_pl_p(ch, S) + 1);
+    }
 
     double dsum = 0.0;
     if (inside) {
-        float u1n, u2n, u1o, u2o;
-        estimate_u_px(P, c.pitch, x, y, c.k.l_t, c.k.theta, u1n, u2n, u1o, u2o);
+        const float l_t = c.k.l_t, theta = c.k.theta, gamma = c.k.gamma;
+        float un[NC], uo[NC];
+        estimate_u_px(P, c.pitch, x, y, l_t, theta, gamma, un, uo);
         // forward differences of the NEW u with clamp (A.7): neighbours are recomputed here
-        float u1x = 0.0f, u2x = 0.0f, u1y = 0.0f, u2y = 0.0f;
+        float ux[NC] = {}, uy[NC] = {};
         if (x + 1 < c.w) {
-            float a, bq, t0, t1;
-            estimate_u_px(P, c.pitch, x + 1, y, c.k.l_t, c.k.theta, a, bq, t0, t1);
-            u1x = a - u1n;
-            u2x = bq - u2n;
+            float a[NC], t[NC];
+            estimate_u_px(P, c.pitch, x + 1, y, l_t, theta, gamma, a, t);
+#pragma unroll
+            for (int ch = 0; ch < NC; ++ch)
+                ux[ch] = a[ch] - un[ch];
         }
         if (y + 1 < c.h) {
-            float a, bq, t0, t1;
-            estimate_u_px(P, c.pitch, x, y + 1, c.k.l_t, c.k.theta, a, bq, t0, t1);
-            u1y = a - u1n;
-            u2y = bq - u2n;
+            float a[NC], t[NC];
+            estimate_u_px(P, c.pitch, x, y + 1, l_t, theta, gamma, a, t);
+#pragma unroll
+            for (int ch = 0; ch < NC; ++ch)
+                uy[ch] = a[ch] - un[ch];
         }
-        float p11 = P.p11[o], p12 = P.p12[o], p21 = P.p21[o], p22 = P.p22[o];
-        tvl1_dual(p11, p12, u1x, u1y, c.k.taut, c.k.hyp);
-        tvl1_dual(p21, p22, u2x, u2y, c.k.taut, c.k.hyp);
-        pair_plane(c, b, PL_U1_0 + 2 * D)[o] = u1n;
-        pair_plane(c, b, PL_U2_0 + 2 * D)[o] = u2n;
-        pair_plane(c, b, PL_P11_0 + 4 * D)[o] = p11;
-        pair_plane(c, b, PL_P12_0 + 4 * D)[o] = p12;
-        pair_plane(c, b, PL_P21_0 + 4 * D)[o] = p21;
-        pair_plane(c, b, PL_P22_0 + 4 * D)[o] = p22;
+#pragma unroll
+        for (int ch = 0; ch < NC; ++ch) {
+            float pa = P.pa[ch][o], pb = P.pb[ch][o];
+            tvl1_dual(pa, pb, ux[ch], uy[ch], c.k.taut, c.k.hyp);
+            pair_plane(c, b, tvl1_pl_u(ch, D))[o] = un[ch];
+            pair_plane(c, b, tvl1_pl_p(ch, D))[o] = pa;
+            pair_plane(c, b, tvl1_pl_p(ch, D) + 1)[o] = pb;
+        }
         if (plan.do_check) {
-            const float e1 = u1o - u1n, e2 = u2o - u2n;
-            dsum = (double)(e1 * e1 + e2 * e2); // diff(y,x) is stored as float upstream
+            const float e1 = uo[0] - un[0], e2 = uo[1] - un[1];
+            dsum = (double)(e1 * e1 + e2 * e2); // diff(y,x) is stored as float upstream; u3 does not enter it
         }
     }
 
-    if (!plan.is_last)
-        return;
-
-    double *partials = c.partials + (long long)b * c.partials_stride;
-    if (plan.do_check) {
-        const double bs = block_reduce_sum_f64(dsum, lds_red);
-        if (threadIdx.x == 0)
-            publish_partial(partials + blk, bs);
-    }
-    if (!arrive_is_last(st, nblk, &lds_flag))
-        return;
-
-    double err = 0.0;
-    if (plan.do_check) {
-        double acc = 0.0;
-        for (unsigned i = threadIdx.x; i < nblk; i += blockDim.x)
-            acc += read_partial(partials + i);
-        err = block_reduce_sum_f64(acc, lds_red);
-    }
-    if (threadIdx.x == 0) {
-        tvl1_end_segment(*st, c.loop, plan, step_id, err);
-        if (st->phase == TVL1_PH_LEVEL_DONE)
-            finish_level(dfx_kernarg_ctx(), b, *st, step_id); // (once per pair and level: the context from the kernel-argument segment)
-        __hip_atomic_store(&st->ticket, 0u, __ATOMIC_RELAXED, AGENT);
-    }
+    end_iter_tile(c, b, st, plan, nblk, blk, step_id, dsum, lds_red, &lds_flag);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -473,7 +474,9 @@ __device__ __forceinline__ double fused_tile_iterate(const Tvl1LevelCtx &c, int 
             const int ly = ly0 + i;
             const int gy = y0 + ly;
             if (col_owned && ly >= K && ly < TH - K && (INTERIOR || (gy >= 0 && gy < c.h))) {
-                const long long o = (long long)gy * c.pitch + gx;
+                int gyo = gy;
+                asm volatile("" : "+v"(gyo)); // recompute the offset here: held from the loads, it costs two VGPRs of scratch
+                const long long o = (long long)gyo * c.pitch + gx;
                 g_u1[o] = u1[i];
                 g_u2[o] = u2[i];
                 g_p11[o] = p11[i];
@@ -574,50 +577,6 @@ __device__ __forceinline__ double fused_tile_iterate_trap(const Tvl1LevelCtx &c,
     return dsum;
 }
 
-// A tile of a pair in phase WARP has been written: take the ticket; the last tile starts the inner loop.
-__device__ __forceinline__ void end_warp_tile(const Tvl1LevelCtx &c, int b, Tvl1State *st, unsigned nblk, int step_id,
-                                              int *lds_flag) {
-    if (arrive_is_last(st, nblk, lds_flag) && threadIdx.x == 0) {
-        // advance the state in place: every other workgroup of this pair has already arrived
-        tvl1_begin_loop(*st, c.loop, step_id);
-        if (st->phase == TVL1_PH_LEVEL_DONE)
-            finish_level(dfx_kernarg_ctx(), b, *st, step_id); // (once per pair and level: the context from the kernel-argument segment)
-        __hip_atomic_store(&st->ticket, 0u, __ATOMIC_RELAXED, AGENT);
-    }
-}
-
-// A tile of the segment-final step has been stored: publish its share of sum(diff), take the ticket; the last
-// tile of the pair sums the partials in index order (deterministic) and advances the state (A.4).
-__device__ __forceinline__ void end_iter_tile(const Tvl1LevelCtx &c, int b, Tvl1State *st, const Tvl1StepPlan &plan,
-                                              unsigned nblk, int slot, int step_id, double dsum, double *lds_red,
-                                              int *lds_flag) {
-    const int tid = threadIdx.x;
-    double *partials = c.partials + (long long)b * c.partials_stride;
-    if (plan.do_check) {
-        const double bs = block_reduce_sum_f64(dsum, lds_red);
-        if (tid == 0)
-            publish_partial(partials + slot, bs);
-    }
-    if (!arrive_is_last(st, nblk, lds_flag))
-        return;
-    double err = 0.0;
-    if (plan.do_check) {
-        double acc = 0.0;
-        for (unsigned i = tid; i < nblk; i += blockDim.x)
-            acc += read_partial(partials + i);
-        err = block_reduce_sum_f64(acc, lds_red);
-    }
-#if DFX_TVL1_DEBUG // measurement builds: never converge, so every build runs the same step schedule
-    err = 1e300;
-#endif
-    if (tid == 0) {
-        tvl1_end_segment(*st, c.loop, plan, step_id, err);
-        if (st->phase == TVL1_PH_LEVEL_DONE)
-            finish_level(dfx_kernarg_ctx(), b, *st, step_id); // (once per pair and level: the context from the kernel-argument segment)
-        __hip_atomic_store(&st->ticket, 0u, __ATOMIC_RELAXED, AGENT);
-    }
-}
-
 // The fused step kernel: 64 x 32 tile, 4 waves, up to K inner iterations per launch.
 //   PK = true : the packed-math tile function on the trapezoid row layout (the tuned default, impl 0), MATH as above;
 //               LK = true: its lean form (tvl1_tile.h: DPP lane neighbours, loop constants in LDS), 128 VGPRs = 4 waves
@@ -699,8 +658,7 @@ __device__ __forceinline__ void step_fused(const Tvl1LevelCtx &c, int step_id, i
         else
             dsum = fused_tile_iterate<TH, NW, false>(c, b, lds, plan.src, plan.n_iters, plan.do_check != 0, K, xs, ys);
     }
-    if (plan.is_last)
-        end_iter_tile(c, b, st, plan, nblk, (int)blockIdx.x, step_id, dsum, lds_red, &lds_flag);
+    end_iter_tile(c, b, st, plan, nblk, (int)blockIdx.x, step_id, dsum, lds_red, &lds_flag);
 }
 
 template <bool PK, int MATH>
@@ -720,8 +678,9 @@ __global__ __launch_bounds__(64 * FT_NW, DFX_FT_WGS) void k_tvl1_step_fused_nbr_
 // with its dual (p31, p32) in planes PL_U3_* / PL_P31_* / PL_P32_* behind the 16 of the default slot (dfx_device.h).  The
 // backward warp does not read u3 (A.5 unchanged), the convergence sum does not contain it and merge does not output it, so
 // those kernels, the state machine and the ticket reduction are the default path's.  What follows is what differs:
-// level begin (p31 = p32 = 0, u3 = 0 at the coarsest level), the upsample of u3 (factor 1), the simple step (impl 1) and
-// the fused tile step (impl 0, tvl1_gamma_tile.h).  Exact arithmetic with the default hypot reading only.
+// level begin (p31 = p32 = 0, u3 = 0 at the coarsest level), the upsample of u3 (factor 1) and the fused tile step (impl 0,
+// tvl1_gamma_tile.h); the simple step (impl 1) is k_tvl1_step_simple<3> above.  Exact arithmetic with the default hypot
+// reading only.
 
 #include "tvl1_gamma_tile.h"
 
@@ -751,156 +710,6 @@ __global__ __launch_bounds__(256) void k_tvl1_upsample_u3(Tvl1LevelCtx c, int dw
     const int cur = c.state[b].cur;
     pair_plane(c, b, PL_U3_0 + (cur ^ 1))[(long long)y * dpitch + x] =
         resize_linear_px(pair_plane(c, b, PL_U3_0 + cur), c.w, c.h, c.pitch, x, y, ifx, ify);
-}
-
-// A.6 with gamma for one pixel from planes in global memory (the simple variant's estimate_u_px with the third channel)
-struct PlanesGammaRO {
-    const float *I1wx, *I1wy, *grad, *rho_c, *u[3], *pa[3], *pb[3];
-};
-
-__device__ __forceinline__ void estimate_u_px_gamma(const PlanesGammaRO &P, int pitch, int x, int y, float l_t, float theta,
-                                                    float gamma, float (&un)[3], float (&uo)[3]) {
-    const long long o = (long long)y * pitch + x;
-#pragma unroll
-    for (int ch = 0; ch < 3; ++ch)
-        uo[ch] = P.u[ch][o];
-    const float I1wx = P.I1wx[o], I1wy = P.I1wy[o], grad = P.grad[o];
-    const float rho = P.rho_c[o] + ((I1wx * uo[0] + I1wy * uo[1]) + gamma * uo[2]);
-    const float lg = l_t * grad;
-    const float fi = tvl1_div(-rho, grad);
-    const bool c1 = rho < -lg, c2 = rho > lg, c3 = grad > FLT_EPSILON;
-    const float w[3] = {I1wx, I1wy, gamma};
-    const bool hl = x > 0, hu = y > 0;
-#pragma unroll
-    for (int ch = 0; ch < 3; ++ch) {
-        const float a = l_t * w[ch], bq = fi * w[ch];
-        const float d = c1 ? a : (c2 ? -a : (c3 ? bq : 0.0f));
-        const float pal = hl ? P.pa[ch][o - 1] : 0.0f, pbu = hu ? P.pb[ch][o - pitch] : 0.0f;
-        un[ch] = (uo[ch] + d) + theta * tvl1_divergence(P.pa[ch][o], pal, P.pb[ch][o], pbu, hl, hu);
-    }
-}
-
-// The simple step kernel with the third channel (impl 1: the cross-check form): k_tvl1_step_simple's phases, ticket protocol
-// and error sum; one pixel per thread, one inner iteration per step.
-__global__ __launch_bounds__(256) void k_tvl1_step_simple_gamma(Tvl1LevelCtx c, int step_id) {
-    __shared__ double lds_red[8];
-    __shared__ int lds_flag;
-
-    const int b = blockIdx.z;
-    Tvl1State *st = c.state + b;
-    const int phase = st->phase;
-    if (phase == TVL1_PH_LEVEL_DONE)
-        return;
-
-    const int x = blockIdx.x * 64 + (threadIdx.x & 63);
-    const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    const bool inside = x < c.w && y < c.h;
-    const unsigned nblk = gridDim.x * gridDim.y;
-    const int blk = blockIdx.y * gridDim.x + blockIdx.x;
-    const long long o = (long long)y * c.pitch + x;
-
-    if (phase == TVL1_PH_WARP) { // A.5 unchanged: the warp reads u1, u2 only
-        const int cur = st->cur;
-        if (inside) {
-            const PairDesc pd = c.pairs[b];
-            const float *I0 = c.frame_I + (long long)pd.frame_a * c.frame_stride + c.lvl_off;
-            const long long fb = (long long)pd.frame_b * c.frame_stride + c.lvl_off;
-            const float u1v = pair_plane(c, b, PL_U1_0 + 2 * cur)[o];
-            const float u2v = pair_plane(c, b, PL_U2_0 + 2 * cur)[o];
-            const WarpOut r = warp_backward_px(I0, c.frame_I + fb, c.frame_Ix + fb, c.frame_Iy + fb, c.w, c.h,
-                                               c.pitch, x, y, u1v, u2v);
-            pair_plane(c, b, PL_I1WX)[o] = r.I1wx;
-            pair_plane(c, b, PL_I1WY)[o] = r.I1wy;
-            pair_plane(c, b, PL_GRAD)[o] = r.grad;
-            pair_plane(c, b, PL_RHOC)[o] = r.rho_c;
-        }
-        if (arrive_is_last(st, nblk, &lds_flag) && threadIdx.x == 0) {
-            tvl1_begin_loop(*st, c.loop, step_id);
-            if (st->phase == TVL1_PH_LEVEL_DONE)
-                finish_level(dfx_kernarg_ctx(), b, *st, step_id);
-            __hip_atomic_store(&st->ticket, 0u, __ATOMIC_RELAXED, AGENT);
-        }
-        return;
-    }
-
-    // ---- phase ITER
-    const Tvl1State s0 = *st;
-    const Tvl1StepPlan plan = tvl1_plan_step(s0, c.loop, step_id);
-    if (plan.n_iters <= 0)
-        return;
-    const int S = plan.src, D = S ^ 1;
-    PlanesGammaRO P;
-    P.I1wx = pair_plane(c, b, PL_I1WX);
-    P.I1wy = pair_plane(c, b, PL_I1WY);
-    P.grad = pair_plane(c, b, PL_GRAD);
-    P.rho_c = pair_plane(c, b, PL_RHOC);
-#pragma unroll
-    for (int ch = 0; ch < 3; ++ch) {
-        P.u[ch] = pair_plane(c, b, tvl1_pl_u(ch, S));
-        P.pa[ch] = pair_plane(c, b, tvl1_pl_p(ch, S));
-        P.pb[ch] = pair_plane(c, b, tvl1_pl_p(ch, S) + 1);
-    }
-
-    double dsum = 0.0;
-    if (inside) {
-        const float l_t = c.k.l_t, theta = c.k.theta, gamma = c.k.gamma;
-        float un[3], uo[3];
-        estimate_u_px_gamma(P, c.pitch, x, y, l_t, theta, gamma, un, uo);
-        // forward differences of the NEW u with clamp (A.7): neighbours are recomputed here
-        float ux[3] = {0.0f, 0.0f, 0.0f}, uy[3] = {0.0f, 0.0f, 0.0f};
-        if (x + 1 < c.w) {
-            float a[3], t[3];
-            estimate_u_px_gamma(P, c.pitch, x + 1, y, l_t, theta, gamma, a, t);
-#pragma unroll
-            for (int ch = 0; ch < 3; ++ch)
-                ux[ch] = a[ch] - un[ch];
-        }
-        if (y + 1 < c.h) {
-            float a[3], t[3];
-            estimate_u_px_gamma(P, c.pitch, x, y + 1, l_t, theta, gamma, a, t);
-#pragma unroll
-            for (int ch = 0; ch < 3; ++ch)
-                uy[ch] = a[ch] - un[ch];
-        }
-#pragma unroll
-        for (int ch = 0; ch < 3; ++ch) {
-            float pa = P.pa[ch][o], pb = P.pb[ch][o];
-            tvl1_dual(pa, pb, ux[ch], uy[ch], c.k.taut, c.k.hyp);
-            pair_plane(c, b, tvl1_pl_u(ch, D))[o] = un[ch];
-            pair_plane(c, b, tvl1_pl_p(ch, D))[o] = pa;
-            pair_plane(c, b, tvl1_pl_p(ch, D) + 1)[o] = pb;
-        }
-        if (plan.do_check) {
-            const float e1 = uo[0] - un[0], e2 = uo[1] - un[1];
-            dsum = (double)(e1 * e1 + e2 * e2); // diff(y,x): u3 does not enter it
-        }
-    }
-
-    if (!plan.is_last)
-        return;
-
-    double *partials = c.partials + (long long)b * c.partials_stride;
-    if (plan.do_check) {
-        const double bs = block_reduce_sum_f64(dsum, lds_red);
-        if (threadIdx.x == 0)
-            publish_partial(partials + blk, bs);
-    }
-    if (!arrive_is_last(st, nblk, &lds_flag))
-        return;
-
-    double err = 0.0;
-    if (plan.do_check) {
-        double acc = 0.0;
-        for (unsigned i = threadIdx.x; i < nblk; i += blockDim.x)
-            acc += read_partial(partials + i);
-        err = block_reduce_sum_f64(acc, lds_red);
-    }
-    if (threadIdx.x == 0) {
-        tvl1_end_segment(*st, c.loop, plan, step_id, err);
-        if (st->phase == TVL1_PH_LEVEL_DONE)
-            finish_level(dfx_kernarg_ctx(), b, *st, step_id);
-        __hip_atomic_store(&st->ticket, 0u, __ATOMIC_RELAXED, AGENT);
-    }
 }
 
 template <int TH, int NW, bool INTERIOR>
@@ -952,8 +761,7 @@ __global__ __launch_bounds__(64 * FT_NW, DFX_FT_WGS) void k_tvl1_step_fused_gamm
     else
         dsum = fused_tile_iterate_gamma<TH, NW, false>(c, b, kc, bnd, plan.src, plan.n_iters, plan.do_check != 0, K, xs, ys,
                                                        tp.own_lo != 0, tp.own_hi != 0);
-    if (plan.is_last)
-        end_iter_tile(c, b, st, plan, nblk, (int)blockIdx.x, step_id, dsum, lds_red, &lds_flag);
+    end_iter_tile(c, b, st, plan, nblk, (int)blockIdx.x, step_id, dsum, lds_red, &lds_flag);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1007,31 +815,22 @@ extern "C" int dfxi_tvl1_fused_max_k() { return tvl1_fused_max_k(); } // test ho
 // tile count (tvl1_step_blocks).
 void tvl1_launch_step(hipStream_t s, const Tvl1LevelCtx &c, int step_id, int impl, int math, bool nbr_lds) {
     if (impl == 1) {
-        hipLaunchKernelGGL(k_tvl1_step_simple, grid_for(c.w, c.h, c.n_pairs), dim3(256), 0, s, c, step_id);
+        hipLaunchKernelGGL(k_tvl1_step_simple<2>, grid_for(c.w, c.h, c.n_pairs), dim3(256), 0, s, c, step_id);
         return;
     }
     const int K = c.loop.fuse_k;
     const Tvl1StepGeom g = tvl1_step_geom(c.w, c.h, 64, FT_TH, K, 0); // classic counts: the in-kernel warp phase
     const dim3 grid(tvl1_step_blocks(c, impl), 1, c.n_pairs), block(64 * FT_NW);
-    if (impl == 0 && (nbr_lds || !c.split_warp)) { // the lean form has no in-kernel warp phase
-        if (math == 1)
-            hipLaunchKernelGGL((k_tvl1_step_fused_nbr_lds<1>), grid, block, 0, s, c, step_id, g.ntx, g.nty);
-        else if (math == TVL1_HYP_SQRT)
-            hipLaunchKernelGGL((k_tvl1_step_fused_nbr_lds<TVL1_HYP_SQRT>), grid, block, 0, s, c, step_id, g.ntx, g.nty);
-        else if (math == TVL1_HYP_LIBM)
-            hipLaunchKernelGGL((k_tvl1_step_fused_nbr_lds<TVL1_HYP_LIBM>), grid, block, 0, s, c, step_id, g.ntx, g.nty);
-        else
-            hipLaunchKernelGGL((k_tvl1_step_fused_nbr_lds<0>), grid, block, 0, s, c, step_id, g.ntx, g.nty);
-    } else if (impl == 2)
+    if (impl == 0 && (nbr_lds || !c.split_warp)) // the lean form has no in-kernel warp phase
+        tvl1_with_math(math, [&](auto m) {
+            hipLaunchKernelGGL((k_tvl1_step_fused_nbr_lds<decltype(m)::value>), grid, block, 0, s, c, step_id, g.ntx, g.nty);
+        });
+    else if (impl == 2)
         hipLaunchKernelGGL((k_tvl1_step_fused<false, 0>), grid, block, 0, s, c, step_id, g.ntx, g.nty);
-    else if (math == 1)
-        hipLaunchKernelGGL((k_tvl1_step_fused<true, 1>), grid, block, 0, s, c, step_id, g.ntx, g.nty);
-    else if (math == TVL1_HYP_SQRT)
-        hipLaunchKernelGGL((k_tvl1_step_fused<true, TVL1_HYP_SQRT>), grid, block, 0, s, c, step_id, g.ntx, g.nty);
-    else if (math == TVL1_HYP_LIBM)
-        hipLaunchKernelGGL((k_tvl1_step_fused<true, TVL1_HYP_LIBM>), grid, block, 0, s, c, step_id, g.ntx, g.nty);
     else
-        hipLaunchKernelGGL((k_tvl1_step_fused<true, 0>), grid, block, 0, s, c, step_id, g.ntx, g.nty);
+        tvl1_with_math(math, [&](auto m) {
+            hipLaunchKernelGGL((k_tvl1_step_fused<true, decltype(m)::value>), grid, block, 0, s, c, step_id, g.ntx, g.nty);
+        });
 }
 
 int tvl1_step_blocks(const Tvl1LevelCtx &c, int impl) {
@@ -1073,7 +872,7 @@ void tvl1_launch_level_begin_gamma(hipStream_t s, const Tvl1LevelCtx &c, int fir
 void tvl1_launch_step_gamma(hipStream_t s, const Tvl1LevelCtx &c, int step_id, int impl) {
     require_gamma_slot(c);
     if (impl == 1)
-        hipLaunchKernelGGL(k_tvl1_step_simple_gamma, grid_for(c.w, c.h, c.n_pairs), dim3(256), 0, s, c, step_id);
+        hipLaunchKernelGGL(k_tvl1_step_simple<3>, grid_for(c.w, c.h, c.n_pairs), dim3(256), 0, s, c, step_id);
     else
         hipLaunchKernelGGL(k_tvl1_step_fused_gamma, dim3(tvl1_step_blocks(c, 0), 1, c.n_pairs), dim3(64 * FT_NW), 0, s, c,
                            step_id);

@@ -11,10 +11,6 @@
 #include "tvl1_math.h"
 #include "tvl1_math_pk.h"
 
-#ifndef DFX_TVL1_DEBUG
-#define DFX_TVL1_DEBUG 0
-#endif
-
 // ------------------------------------------------------------------------------------------------
 // The fused step, packed-math variant (the tuned default).  Same tile, same halo scheme, same bits as
 // fused_tile_iterate above, but:
