@@ -8,6 +8,7 @@
 
 #include "dfx_pipeline.h"
 #include "fb_check_kernels.h"
+#include "global_motion_kernels.h"
 #include "jpeg_kernels.h"
 #include "prepare_kernels.h"
 #include "quantize_kernels.h"
@@ -681,6 +682,59 @@ int dfx_warp_device(dfx_handle h, const dfx_warp_desc *d) {
     a.occ_pitch = (long long)d->occ_pitch, a.occ_stride = (long long)d->occ_stride;
     a.valid_pitch = (long long)d->valid_pitch, a.valid_stride = (long long)d->valid_stride;
     warp_launch(h->stream, a);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return DFX_OK;
+}
+
+// ---- the global (camera) motion of a flow: robust fit and removal (global_motion_kernels.hip) ----
+int dfx_global_motion_device(dfx_handle h, const dfx_gm_desc *d) {
+    if (!h)
+        return DFX_ERR_INVALID;
+    (void)dfx_finish_tails(h, 0, -1);
+    if (h->algo == DFX_ALGO_FRAMES)
+        return dfx_fail(h, DFX_ERR_UNSUPPORTED, "a DFX_ALGO_FRAMES handle computes no flow");
+    if (!d)
+        return dfx_fail(h, DFX_ERR_INVALID, "NULL descriptor");
+    if (d->n < 0)
+        return dfx_fail(h, DFX_ERR_INVALID, "n must be >= 0");
+    if (d->n == 0)
+        return DFX_OK;
+    if (!d->d_flow || !d->d_result)
+        return dfx_fail(h, DFX_ERR_INVALID, "NULL device flows or result records");
+    if ((size_t)d->d_result % 8 != 0)
+        return dfx_fail(h, DFX_ERR_INVALID, "d_result must be 8-byte aligned");
+    if (d->model != DFX_GM_TRANSLATION && d->model != DFX_GM_AFFINE)
+        return dfx_fail(h, DFX_ERR_INVALID, "model must be DFX_GM_TRANSLATION or DFX_GM_AFFINE");
+    if (d->rounds < 1 || d->rounds > GM_MAX_ROUNDS)
+        return dfx_fail(h, DFX_ERR_INVALID, "rounds must be 1 .. 8");
+    if (!std::isfinite(d->thr) || !(d->thr > 0.0f))
+        return dfx_fail(h, DFX_ERR_INVALID, "thr must be finite and > 0");
+    if (!std::isfinite(d->growth) || !(d->growth >= 1.0f))
+        return dfx_fail(h, DFX_ERR_INVALID, "growth must be finite and >= 1");
+    if (planar_strides_bad(h, d->row_pitch_floats, d->plane_stride_floats, d->flow_stride_floats))
+        return dfx_fail(h, DFX_ERR_INVALID, kPlanarStrides);
+    if (d->d_mask && fb_occ_bad(h, d->mask_pitch, d->mask_stride))
+        return dfx_fail(h, DFX_ERR_INVALID, "mask planes: mask_pitch >= W and mask_stride >= H * mask_pitch are required");
+    if (d->d_out && planar_strides_bad(h, d->out_row_pitch_floats, d->out_plane_stride_floats, d->out_flow_stride_floats))
+        return dfx_fail(h, DFX_ERR_INVALID, "output flows: out_row_pitch_floats >= W, out_plane_stride_floats >= H * out_row_pitch_floats "
+                                            "and out_flow_stride_floats >= 2 * out_plane_stride_floats are required");
+    if (d->d_moving && fb_occ_bad(h, d->moving_pitch, d->moving_stride))
+        return dfx_fail(h, DFX_ERR_INVALID, "moving planes: moving_pitch >= W and moving_stride >= H * moving_pitch are required");
+    if (h->W > GM_MAX_SIDE || h->H > GM_MAX_SIDE)
+        return dfx_fail(h, DFX_ERR_UNSUPPORTED, "the integer sums are bounded for frames of at most 8192 x 8192");
+    HIPCHK(h, hipSetDevice(h->device));
+    GmArgs a{};
+    a.flow = d->d_flow, a.mask = d->d_mask, a.out = d->d_out, a.moving = d->d_moving, a.result = d->d_result;
+    a.n = d->n, a.w = h->W, a.h = h->H;
+    a.model = d->model, a.rounds = d->rounds, a.thr = d->thr, a.growth = d->growth;
+    a.row_pitch = (long long)d->row_pitch_floats, a.plane_stride = (long long)d->plane_stride_floats;
+    a.flow_stride = (long long)d->flow_stride_floats;
+    a.mask_pitch = (long long)d->mask_pitch, a.mask_stride = (long long)d->mask_stride;
+    a.out_pitch = (long long)d->out_row_pitch_floats, a.out_plane = (long long)d->out_plane_stride_floats;
+    a.out_stride = (long long)d->out_flow_stride_floats;
+    a.moving_pitch = (long long)d->moving_pitch, a.moving_stride = (long long)d->moving_stride;
+    gm_launch(h->stream, a);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return DFX_OK;

@@ -144,6 +144,50 @@ class DfxWarpDesc(C.Structure):
     ]
 
 
+class DfxGmResult(C.Structure):
+    """dfx_gm_result of include/dfx.h, field for field: one record per flow, the results and the call's only workspace."""
+    _fields_ = [
+        ("a", C.c_double * 6),
+        ("p", C.c_float * 6),
+        ("valid", C.c_uint64),
+        ("inliers", C.c_uint64 * 8),
+        ("status", C.c_uint32),
+        ("rounds", C.c_uint32),
+        ("sums", C.c_int64 * 12),
+        ("work", C.c_uint64 * 13),
+    ]
+
+
+class DfxGmDesc(C.Structure):
+    """dfx_gm_desc of include/dfx.h, field for field."""
+    _fields_ = [
+        ("d_flow", C.c_void_p),
+        ("row_pitch_floats", C.c_size_t),
+        ("plane_stride_floats", C.c_size_t),
+        ("flow_stride_floats", C.c_size_t),
+        ("n", C.c_int),
+        ("model", C.c_int),
+        ("rounds", C.c_int),
+        ("thr", C.c_float),
+        ("growth", C.c_float),
+        ("d_mask", C.c_void_p),
+        ("mask_pitch", C.c_size_t),
+        ("mask_stride", C.c_size_t),
+        ("d_out", C.c_void_p),
+        ("out_row_pitch_floats", C.c_size_t),
+        ("out_plane_stride_floats", C.c_size_t),
+        ("out_flow_stride_floats", C.c_size_t),
+        ("d_moving", C.c_void_p),
+        ("moving_pitch", C.c_size_t),
+        ("moving_stride", C.c_size_t),
+        ("d_result", C.c_void_p),
+    ]
+
+
+GM_RESULT_DTYPE = np.dtype([("a", "<f8", 6), ("p", "<f4", 6), ("valid", "<u8"), ("inliers", "<u8", 8), ("status", "<u4"),
+                            ("rounds", "<u4"), ("sums", "<i8", 12), ("work", "<u8", 13)])  # dfx_gm_result as a NumPy record
+
+
 # ------------------------------------------------------------------------------------------ build
 
 def library_path() -> str:
@@ -238,6 +282,9 @@ def load_library():
     if hasattr(L, "dfx_warp_device"):  # a library built before the warp (DFX_LIBRARY A/B) still loads
         L.dfx_warp_device.argtypes = [vp, C.POINTER(DfxWarpDesc)]
         L.dfx_warp_device.restype = i
+    if hasattr(L, "dfx_global_motion_device"):  # a library built before the global motion (DFX_LIBRARY A/B) still loads
+        L.dfx_global_motion_device.argtypes = [vp, C.POINTER(DfxGmDesc)]
+        L.dfx_global_motion_device.restype = i
     if hasattr(L, "dfxi_probe_planar_value_as"):  # test hook (selftest.hip)
         L.dfxi_probe_planar_value_as.argtypes = [i, i, vp, C.c_float, vp, sz]
         L.dfxi_probe_planar_value_as.restype = i
@@ -383,6 +430,30 @@ def _planar_dtype(dtype):
 
 WARP_U8 = 3                               # DFX_WARP_U8: the fourth out_dtype of dfx_warp_device
 WARP_BORDERS = {"zero": 0, "clamp": 1}    # DFX_WARP_BORDER_ZERO / DFX_WARP_BORDER_CLAMP
+
+
+GM_MODELS = {"translation": 0, "affine": 1}  # DFX_GM_TRANSLATION / DFX_GM_AFFINE
+GM_MAX_ROUNDS = 8
+
+
+def _gm_settings(model, rounds, thr, growth):
+    """(model code, rounds, thr, growth) checked as dfx_global_motion_device checks them, before the library is reached."""
+    if not isinstance(model, str) or model not in GM_MODELS:
+        raise ValueError('model must be "translation" or "affine"')
+    if isinstance(rounds, bool) or not isinstance(rounds, (int, np.integer)) or not 1 <= int(rounds) <= GM_MAX_ROUNDS:
+        raise ValueError("rounds must be an integer 1 .. 8")
+    thr32, growth32 = np.float32(thr), np.float32(growth)
+    if not np.isfinite(thr32) or not thr32 > 0:
+        raise ValueError("thr must be finite and > 0")
+    if not np.isfinite(growth32) or not growth32 >= 1:
+        raise ValueError("growth must be finite and >= 1")
+    return GM_MODELS[model], int(rounds), float(thr32), float(growth32)
+
+
+def _gm_info(rec):
+    """The counts and the status of n result records (a GM_RESULT_DTYPE array) as the wrappers return them."""
+    return {"valid": rec["valid"].copy(), "inliers": rec["inliers"].copy(), "status": rec["status"].copy(),
+            "rounds": rec["rounds"].copy()}
 
 
 def _warp_border(border):
@@ -1257,6 +1328,125 @@ class FlowEngine:
                              stats.data_ptr() if want_stats else None)
         res = (out,) + ((valid,) if want_valid else ()) + ((stats,) if want_stats else ())
         return res if len(res) > 1 else out
+
+    # -- the global (camera) motion of a flow: robust fit, removal, moving mask (dfx_global_motion_device) ----
+    def global_motion_device(self, d_flow_ptr: int, row_pitch_floats: int, plane_stride_floats: int, flow_stride_floats: int,
+                             n: int, d_result_ptr: int, model: int = 1, rounds: int = 5, thr: float = 0.5, growth: float = 2.0,
+                             d_mask_ptr: int | None = None, mask_pitch: int = 0, mask_stride: int = 0,
+                             d_out_ptr: int | None = None, out_row_pitch_floats: int = 0, out_plane_stride_floats: int = 0,
+                             out_flow_stride_floats: int = 0, d_moving_ptr: int | None = None, moving_pitch: int = 0,
+                             moving_stride: int = 0):
+        """n planar float32 flows that are already in device memory: the fields of dfx_gm_desc (include/dfx.h) as arguments,
+        codes and raw pointers as the header gives them; d_result_ptr: n dfx_gm_result records (DfxGmResult) in device memory."""
+        d = DfxGmDesc(d_flow_ptr, row_pitch_floats, plane_stride_floats, flow_stride_floats, int(n), int(model), int(rounds),
+                      float(thr), float(growth), d_mask_ptr, mask_pitch, mask_stride, d_out_ptr, out_row_pitch_floats,
+                      out_plane_stride_floats, out_flow_stride_floats, d_moving_ptr, moving_pitch, moving_stride, d_result_ptr)
+        self._check(self._L.dfx_global_motion_device(self._h, C.byref(d)))
+
+    def global_motion(self, flows, mask=None, model: str = "affine", rounds: int = 5, thr: float = 0.5, growth: float = 2.0):
+        """How much of each flow is the camera, and what the flow is without it (dfx_global_motion_device).
+
+        flows: (M, 2, H, W) float32.  mask: optional (M, H, W) uint8, nonzero = excluded from the fit (an occlusion mask as
+        fb_check gives it).  model "translation" or "affine"; rounds 1 .. 8 of re-fitting on the pixels within the previous
+        model (1 = plain least squares); thr: the inlier radius of the last round in pixels, each earlier round's `growth`
+        times wider.  Returns (params, compensated, moving, info): params (M, 6) float64 with u_cam = a0 + a1 x + a2 y,
+        v_cam = a3 + a4 x + a5 y in pixel coordinates; compensated (M, 2, H, W) float32, the flows minus that model;
+        moving (M, H, W) uint8, 1 where a pixel does not follow the model within thr (or is excluded); info: a dict of
+        "valid" (M,), "inliers" (M, 8), "status" (M,: bit k set = round k was degenerate and kept the model before it) and
+        "rounds"."""
+        code, rounds, thr, growth = _gm_settings(model, rounds, thr, growth)
+        H, W = self.height, self.width
+        fl = np.asarray(flows)
+        if fl.dtype != np.float32 or fl.ndim != 4 or fl.shape[1:] != (2, H, W):
+            raise ValueError("flows must be (M, 2, H, W) float32")
+        fl = np.ascontiguousarray(fl)
+        m = fl.shape[0]
+        if mask is not None:
+            mask = np.asarray(mask)
+            if mask.dtype != np.uint8 or mask.shape != (m, H, W):
+                raise ValueError("mask must be (M, H, W) uint8")
+            mask = np.ascontiguousarray(mask)
+        out, moving = np.empty_like(fl), np.empty((m, H, W), np.uint8)
+        rec = np.zeros(m, GM_RESULT_DTYPE)
+        if m:
+            ins = [fl] + ([mask] if mask is not None else [])
+            bufs = self._dev_bufs([x.nbytes for x in ins] + [out.nbytes, moving.nbytes, rec.nbytes])
+            try:
+                for p, x in zip(bufs, ins):
+                    self._check(self._L.dfx_memcpy_h2d(self._h, p, x.ctypes.data, x.nbytes))
+                d_out, d_moving, d_rec = bufs[-3:]
+                self.global_motion_device(bufs[0], W, H * W, 2 * H * W, m, d_rec, code, rounds, thr, growth,
+                                          bufs[1] if mask is not None else None, W, H * W, d_out, W, H * W, 2 * H * W,
+                                          d_moving, W, H * W)
+                for x, p in ((out, d_out), (moving, d_moving), (rec, d_rec)):
+                    self._check(self._L.dfx_memcpy_d2h(self._h, x.ctypes.data, p, x.nbytes))
+            finally:
+                self._dev_free(bufs)
+        return rec["a"].copy(), out, moving, _gm_info(rec)
+
+    def global_motion_tensor(self, flows, mask=None, model: str = "affine", rounds: int = 5, thr: float = 0.5,
+                             growth: float = 2.0, out=None, want_moving: bool = True):
+        """global_motion for torch tensors on this handle's device, read and written where they lie.
+
+        flows: (M, 2, H, W) torch.float32 with a contiguous innermost dimension, e.g. what flow_tensor returns; every stride is
+        taken from the tensor, so a slice of a larger tensor is read without a copy.  mask: optional (M, H, W) torch.uint8.
+        out: optional (M, 2, H, W) float32 tensor for the compensated flows; it may be `flows` itself (in place).  Returns
+        (params, compensated, moving, info): params an (M, 6) float64 tensor, moving an (M, H, W) uint8 tensor (None with
+        want_moving=False), info a dict of host tensors "valid", "inliers", "status", "rounds" as global_motion's
+        (the n records are copied to the host once; the counts are int64).
+
+        Torch's current stream on that device is synchronised before the call; the call returns with its device work
+        complete.  Raises ValueError before the library is reached for a wrong setting, dtype, device, shape or stride."""
+        import torch
+
+        code, rounds, thr, growth = _gm_settings(model, rounds, thr, growth)
+        H, W = self.height, self.width
+
+        def planes(t, what):  # (row pitch, plane stride, flow stride) of an (M, 2, H, W) float32 tensor
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 4 or tuple(t.shape[1:]) != (2, H, W):
+                raise ValueError(f"{what} must be an (M, 2, H, W) torch.float32 tensor")
+            st = t.stride()
+            pitch = st[2] if H > 1 else W
+            plane, flow = st[1], (st[0] if t.shape[0] > 1 else 2 * st[1])
+            if (st[3] != 1 and W > 1) or pitch < W or plane < H * pitch or flow < 2 * plane:
+                raise ValueError(f"{what}: the innermost dimension must be contiguous and rows, planes and flows must not overlap")
+            return pitch, plane, flow
+
+        row_pitch, flow_plane, flow_stride = planes(flows, "flows")
+        m, dev = flows.shape[0], flows.device
+        mask_pitch = mask_stride = 0
+        if mask is not None:
+            if not isinstance(mask, torch.Tensor) or mask.dtype != torch.uint8 or tuple(mask.shape) != (m, H, W):
+                raise ValueError("mask must be an (M, H, W) torch.uint8 tensor")
+            sm = mask.stride()
+            mask_pitch = sm[1] if H > 1 else W
+            mask_stride = sm[0] if m > 1 else H * mask_pitch
+            if (sm[2] != 1 and W > 1) or mask_pitch < W or mask_stride < H * mask_pitch:
+                raise ValueError("mask: the innermost dimension must be contiguous and rows and masks must not overlap")
+        if out is not None:
+            out_pitch, out_plane, out_stride = planes(out, "out")
+            if out.shape[0] != m:
+                raise ValueError("out must be an (M, 2, H, W) torch.float32 tensor")
+            if out.data_ptr() == flows.data_ptr() and (out_pitch, out_plane, out_stride) != (row_pitch, flow_plane, flow_stride):
+                raise ValueError("out: in place needs the strides of flows")
+        if dev.type != "cuda" or (dev.index is not None and dev.index != getattr(self, "_device", dev.index)):
+            raise ValueError("flows must be on this handle's device")
+        if any(t.device != dev for t in (mask, out) if t is not None):
+            raise ValueError("mask and out must be on the flows' device")
+        if out is None:
+            out = torch.empty((m, 2, H, W), dtype=torch.float32, device=dev)
+            out_pitch, out_plane, out_stride = W, H * W, 2 * H * W
+        moving = torch.empty((m, H, W), dtype=torch.uint8, device=dev) if want_moving else None
+        rec = torch.zeros((m, C.sizeof(DfxGmResult) // 8), dtype=torch.int64, device=dev)  # 8-byte aligned records
+        torch.cuda.current_stream(dev).synchronize()
+        if m:
+            self.global_motion_device(flows.data_ptr(), row_pitch, flow_plane, flow_stride, m, rec.data_ptr(), code, rounds, thr,
+                                      growth, mask.data_ptr() if mask is not None else None, mask_pitch, mask_stride,
+                                      out.data_ptr(), out_pitch, out_plane, out_stride,
+                                      moving.data_ptr() if want_moving else None, W, H * W)
+        host = rec.cpu().numpy().view(np.uint8).reshape(m, -1).copy().view(GM_RESULT_DTYPE).reshape(m)
+        info = {k: torch.from_numpy(v.astype(np.int64) if v.dtype.kind == "u" else v) for k, v in _gm_info(host).items()}
+        return torch.from_numpy(host["a"].copy()).to(dev), out, moving, info
 
     def flow_tensor_bidir(self, frames, step: int, check: bool = True, alpha1: float = 0.01, alpha2: float = 0.5, out=None):
         """flow_tensor for both directions and the occlusion masks: (fwd, bwd, occ_fwd, occ_bwd) as torch tensors on the
