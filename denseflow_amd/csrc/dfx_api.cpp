@@ -8,6 +8,7 @@
 
 #include "dfx_pipeline.h"
 #include "fb_check_kernels.h"
+#include "flow_median_kernels.h"
 #include "global_motion_kernels.h"
 #include "jpeg_kernels.h"
 #include "prepare_kernels.h"
@@ -735,6 +736,55 @@ int dfx_global_motion_device(dfx_handle h, const dfx_gm_desc *d) {
     a.out_stride = (long long)d->out_flow_stride_floats;
     a.moving_pitch = (long long)d->moving_pitch, a.moving_stride = (long long)d->moving_stride;
     gm_launch(h->stream, a);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return DFX_OK;
+}
+
+// ---- median filter and occlusion fill of flows, mask-aware (flow_median_kernels.hip) ----
+int dfx_flow_median_device(dfx_handle h, const dfx_median_desc *d) {
+    if (!h)
+        return DFX_ERR_INVALID;
+    (void)dfx_finish_tails(h, 0, -1);
+    if (h->algo == DFX_ALGO_FRAMES)
+        return dfx_fail(h, DFX_ERR_UNSUPPORTED, "a DFX_ALGO_FRAMES handle computes no flow");
+    if (!d)
+        return dfx_fail(h, DFX_ERR_INVALID, "NULL descriptor");
+    if (d->n < 0)
+        return dfx_fail(h, DFX_ERR_INVALID, "n must be >= 0");
+    if (d->n == 0)
+        return DFX_OK;
+    if (!d->d_flow || !d->d_out)
+        return dfx_fail(h, DFX_ERR_INVALID, "NULL device flows or output flows");
+    if (d->ksize != 3 && d->ksize != 5)
+        return dfx_fail(h, DFX_ERR_INVALID, "ksize must be 3 or 5");
+    if (d->mode != DFX_MEDIAN_ALL && d->mode != DFX_MEDIAN_FILL)
+        return dfx_fail(h, DFX_ERR_INVALID, "mode must be DFX_MEDIAN_ALL or DFX_MEDIAN_FILL");
+    if (!d->d_mask && (d->mode == DFX_MEDIAN_FILL || d->d_mask_out))
+        return dfx_fail(h, DFX_ERR_INVALID, "DFX_MEDIAN_FILL and d_mask_out need d_mask");
+    if (d->d_out == d->d_flow || (d->d_mask_out && d->d_mask_out == d->d_mask))
+        return dfx_fail(h, DFX_ERR_INVALID, "a stencil cannot run in place: d_out != d_flow and d_mask_out != d_mask are required");
+    if (planar_strides_bad(h, d->row_pitch_floats, d->plane_stride_floats, d->flow_stride_floats))
+        return dfx_fail(h, DFX_ERR_INVALID, kPlanarStrides);
+    if (planar_strides_bad(h, d->out_row_pitch_floats, d->out_plane_stride_floats, d->out_flow_stride_floats))
+        return dfx_fail(h, DFX_ERR_INVALID, "output flows: out_row_pitch_floats >= W, out_plane_stride_floats >= H * out_row_pitch_floats "
+                                            "and out_flow_stride_floats >= 2 * out_plane_stride_floats are required");
+    if (d->d_mask && fb_occ_bad(h, d->mask_pitch, d->mask_stride))
+        return dfx_fail(h, DFX_ERR_INVALID, "mask planes: mask_pitch >= W and mask_stride >= H * mask_pitch are required");
+    if (d->d_mask_out && fb_occ_bad(h, d->mask_out_pitch, d->mask_out_stride))
+        return dfx_fail(h, DFX_ERR_INVALID, "output mask planes: mask_out_pitch >= W and mask_out_stride >= H * mask_out_pitch are required");
+    HIPCHK(h, hipSetDevice(h->device));
+    FmArgs a{};
+    a.flow = d->d_flow, a.mask = d->d_mask, a.out = d->d_out, a.mask_out = d->d_mask_out;
+    a.n = d->n, a.w = h->W, a.h = h->H;
+    a.ksize = d->ksize, a.mode = d->mode;
+    a.row_pitch = (long long)d->row_pitch_floats, a.plane_stride = (long long)d->plane_stride_floats;
+    a.flow_stride = (long long)d->flow_stride_floats;
+    a.mask_pitch = (long long)d->mask_pitch, a.mask_stride = (long long)d->mask_stride;
+    a.out_pitch = (long long)d->out_row_pitch_floats, a.out_plane = (long long)d->out_plane_stride_floats;
+    a.out_stride = (long long)d->out_flow_stride_floats;
+    a.mask_out_pitch = (long long)d->mask_out_pitch, a.mask_out_stride = (long long)d->mask_out_stride;
+    fm_launch(h->stream, a);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return DFX_OK;

@@ -188,6 +188,29 @@ GM_RESULT_DTYPE = np.dtype([("a", "<f8", 6), ("p", "<f4", 6), ("valid", "<u8"), 
                             ("rounds", "<u4"), ("sums", "<i8", 12), ("work", "<u8", 13)])  # dfx_gm_result as a NumPy record
 
 
+class DfxMedianDesc(C.Structure):
+    """dfx_median_desc of include/dfx.h, field for field."""
+    _fields_ = [
+        ("d_flow", C.c_void_p),
+        ("row_pitch_floats", C.c_size_t),
+        ("plane_stride_floats", C.c_size_t),
+        ("flow_stride_floats", C.c_size_t),
+        ("n", C.c_int),
+        ("ksize", C.c_int),
+        ("mode", C.c_int),
+        ("d_mask", C.c_void_p),
+        ("mask_pitch", C.c_size_t),
+        ("mask_stride", C.c_size_t),
+        ("d_out", C.c_void_p),
+        ("out_row_pitch_floats", C.c_size_t),
+        ("out_plane_stride_floats", C.c_size_t),
+        ("out_flow_stride_floats", C.c_size_t),
+        ("d_mask_out", C.c_void_p),
+        ("mask_out_pitch", C.c_size_t),
+        ("mask_out_stride", C.c_size_t),
+    ]
+
+
 # ------------------------------------------------------------------------------------------ build
 
 def library_path() -> str:
@@ -285,6 +308,9 @@ def load_library():
     if hasattr(L, "dfx_global_motion_device"):  # a library built before the global motion (DFX_LIBRARY A/B) still loads
         L.dfx_global_motion_device.argtypes = [vp, C.POINTER(DfxGmDesc)]
         L.dfx_global_motion_device.restype = i
+    if hasattr(L, "dfx_flow_median_device"):  # a library built before the flow median (DFX_LIBRARY A/B) still loads
+        L.dfx_flow_median_device.argtypes = [vp, C.POINTER(DfxMedianDesc)]
+        L.dfx_flow_median_device.restype = i
     if hasattr(L, "dfxi_probe_planar_value_as"):  # test hook (selftest.hip)
         L.dfxi_probe_planar_value_as.argtypes = [i, i, vp, C.c_float, vp, sz]
         L.dfxi_probe_planar_value_as.restype = i
@@ -454,6 +480,23 @@ def _gm_info(rec):
     """The counts and the status of n result records (a GM_RESULT_DTYPE array) as the wrappers return them."""
     return {"valid": rec["valid"].copy(), "inliers": rec["inliers"].copy(), "status": rec["status"].copy(),
             "rounds": rec["rounds"].copy()}
+
+
+MEDIAN_MODES = {"all": 0, "fill": 1}  # DFX_MEDIAN_ALL / DFX_MEDIAN_FILL
+MEDIAN_MAX_PASSES = 64
+
+
+def _median_settings(ksize, mode, passes, has_mask):
+    """(ksize, mode code, passes) checked as dfx_flow_median_device checks them, before the library is reached."""
+    if isinstance(ksize, bool) or not isinstance(ksize, (int, np.integer)) or int(ksize) not in (3, 5):
+        raise ValueError("ksize must be 3 or 5")
+    if not isinstance(mode, str) or mode not in MEDIAN_MODES:
+        raise ValueError('mode must be "all" or "fill"')
+    if isinstance(passes, bool) or not isinstance(passes, (int, np.integer)) or not 1 <= int(passes) <= MEDIAN_MAX_PASSES:
+        raise ValueError("passes must be an integer 1 .. 64")
+    if mode == "fill" and not has_mask:
+        raise ValueError('mode "fill" needs a mask')
+    return int(ksize), MEDIAN_MODES[mode], int(passes)
 
 
 def _warp_border(border):
@@ -1447,6 +1490,144 @@ class FlowEngine:
         host = rec.cpu().numpy().view(np.uint8).reshape(m, -1).copy().view(GM_RESULT_DTYPE).reshape(m)
         info = {k: torch.from_numpy(v.astype(np.int64) if v.dtype.kind == "u" else v) for k, v in _gm_info(host).items()}
         return torch.from_numpy(host["a"].copy()).to(dev), out, moving, info
+
+    # -- median filter and occlusion fill of flows, mask-aware (dfx_flow_median_device) ----
+    def flow_median_device(self, d_flow_ptr: int, row_pitch_floats: int, plane_stride_floats: int, flow_stride_floats: int,
+                           n: int, d_out_ptr: int, out_row_pitch_floats: int, out_plane_stride_floats: int,
+                           out_flow_stride_floats: int, ksize: int = 5, mode: int = 0, d_mask_ptr: int | None = None,
+                           mask_pitch: int = 0, mask_stride: int = 0, d_mask_out_ptr: int | None = None,
+                           mask_out_pitch: int = 0, mask_out_stride: int = 0):
+        """n planar float32 flows that are already in device memory: the fields of dfx_median_desc (include/dfx.h) as
+        arguments, codes and raw pointers as the header gives them."""
+        d = DfxMedianDesc(d_flow_ptr, row_pitch_floats, plane_stride_floats, flow_stride_floats, int(n), int(ksize), int(mode),
+                          d_mask_ptr, mask_pitch, mask_stride, d_out_ptr, out_row_pitch_floats, out_plane_stride_floats,
+                          out_flow_stride_floats, d_mask_out_ptr, mask_out_pitch, mask_out_stride)
+        self._check(self._L.dfx_flow_median_device(self._h, C.byref(d)))
+
+    def flow_median(self, flows, ksize: int = 5, mask=None, mode: str = "all", passes: int = 1):
+        """The ksize x ksize median of each flow plane on the keys of the samples' bit patterns, mask-aware
+        (dfx_flow_median_device).
+
+        flows: (M, 2, H, W) float32.  mask: optional (M, H, W) uint8, nonzero = the sample is not used (an occlusion mask as
+        fb_check gives it).  mode "all": every pixel takes the median of the unmasked samples of its window; "fill" (needs a
+        mask): only masked pixels do, unmasked flow is returned bit for bit.  passes > 1 repeats the call on its own output
+        with the returned mask as the mask, which grows a fill inward by ksize // 2 pixels per pass; in "fill" mode the passes
+        stop once the returned mask is all zero.  Returns (out, mask_out): (M, 2, H, W) float32 and (M, H, W) uint8 with 1
+        where a pixel had no unmasked sample in its window (it keeps its input), None without a mask."""
+        ksize, code, passes = _median_settings(ksize, mode, passes, mask is not None)
+        H, W = self.height, self.width
+        fl = np.asarray(flows)
+        if fl.dtype != np.float32 or fl.ndim != 4 or fl.shape[1:] != (2, H, W):
+            raise ValueError("flows must be (M, 2, H, W) float32")
+        fl = np.ascontiguousarray(fl)
+        m = fl.shape[0]
+        if mask is not None:
+            mask = np.asarray(mask)
+            if mask.dtype != np.uint8 or mask.shape != (m, H, W):
+                raise ValueError("mask must be (M, H, W) uint8")
+            mask = np.ascontiguousarray(mask)
+        out = np.empty_like(fl)
+        mask_out = np.empty((m, H, W), np.uint8) if mask is not None else None
+        if m:
+            mb = mask.nbytes if mask is not None else 0
+            bufs = self._dev_bufs([fl.nbytes, fl.nbytes, mb, mb])
+            try:
+                src, dst, msrc, mdst = bufs
+                self._check(self._L.dfx_memcpy_h2d(self._h, src, fl.ctypes.data, fl.nbytes))
+                if mask is not None:
+                    self._check(self._L.dfx_memcpy_h2d(self._h, msrc, mask.ctypes.data, mb))
+                for k in range(passes):
+                    self.flow_median_device(src, W, H * W, 2 * H * W, m, dst, W, H * W, 2 * H * W, ksize, code,
+                                            msrc if mask is not None else None, W, H * W,
+                                            mdst if mask is not None else None, W, H * W)
+                    src, dst, msrc, mdst = dst, src, mdst, msrc
+                    if mask is not None and code == MEDIAN_MODES["fill"] and k + 1 < passes:
+                        self._check(self._L.dfx_memcpy_d2h(self._h, mask_out.ctypes.data, msrc, mb))
+                        if not mask_out.any():
+                            break
+                self._check(self._L.dfx_memcpy_d2h(self._h, out.ctypes.data, src, out.nbytes))
+                if mask is not None:
+                    self._check(self._L.dfx_memcpy_d2h(self._h, mask_out.ctypes.data, msrc, mb))
+            finally:
+                self._dev_free(bufs)
+        return out, mask_out
+
+    def flow_median_tensor(self, flows, ksize: int = 5, mask=None, mode: str = "all", passes: int = 1, out=None):
+        """flow_median for torch tensors on this handle's device, read and written where they lie.
+
+        flows: (M, 2, H, W) torch.float32 with a contiguous innermost dimension, e.g. what flow_tensor returns; every stride is
+        taken from the tensor, so a slice of a larger tensor is read without a copy.  mask: optional (M, H, W) torch.uint8.
+        out: optional (M, 2, H, W) float32 tensor for the result, not `flows` itself (a stencil cannot run in place).  Returns
+        (out, mask_out): mask_out an (M, H, W) uint8 tensor, None without a mask.  passes > 1 alternates between `out` and
+        one temporary torch allocation (and two mask tensors); the result is copied into `out` where the last pass did not
+        write it there.  In "fill" mode the passes stop once a returned mask is all zero (one host read per pass).
+
+        Torch's current stream on that device is synchronised before the call; the call returns with its device work
+        complete.  Raises ValueError before the library is reached for a wrong setting, dtype, device, shape or stride."""
+        import torch
+
+        ksize, code, passes = _median_settings(ksize, mode, passes, mask is not None)
+        H, W = self.height, self.width
+
+        def planes(t, what):  # (row pitch, plane stride, flow stride) of an (M, 2, H, W) float32 tensor
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 4 or tuple(t.shape[1:]) != (2, H, W):
+                raise ValueError(f"{what} must be an (M, 2, H, W) torch.float32 tensor")
+            st = t.stride()
+            pitch = st[2] if H > 1 else W
+            plane, flow = st[1], (st[0] if t.shape[0] > 1 else 2 * st[1])
+            if (st[3] != 1 and W > 1) or pitch < W or plane < H * pitch or flow < 2 * plane:
+                raise ValueError(f"{what}: the innermost dimension must be contiguous and rows, planes and flows must not overlap")
+            return pitch, plane, flow
+
+        geom = planes(flows, "flows")
+        m, dev = flows.shape[0], flows.device
+        mgeom = (0, 0)
+        if mask is not None:
+            if not isinstance(mask, torch.Tensor) or mask.dtype != torch.uint8 or tuple(mask.shape) != (m, H, W):
+                raise ValueError("mask must be an (M, H, W) torch.uint8 tensor")
+            sm = mask.stride()
+            mask_pitch = sm[1] if H > 1 else W
+            mgeom = (mask_pitch, sm[0] if m > 1 else H * mask_pitch)
+            if (sm[2] != 1 and W > 1) or mgeom[0] < W or mgeom[1] < H * mgeom[0]:
+                raise ValueError("mask: the innermost dimension must be contiguous and rows and masks must not overlap")
+        if out is not None:
+            ogeom = planes(out, "out")
+            if out.shape[0] != m:
+                raise ValueError("out must be an (M, 2, H, W) torch.float32 tensor")
+            if out.data_ptr() == flows.data_ptr() and m:
+                raise ValueError("out must not be flows: a stencil cannot run in place")
+        if dev.type != "cuda" or (dev.index is not None and dev.index != getattr(self, "_device", dev.index)):
+            raise ValueError("flows must be on this handle's device")
+        if any(t.device != dev for t in (mask, out) if t is not None):
+            raise ValueError("mask and out must be on the flows' device")
+        dense, mdense = (W, H * W, 2 * H * W), (W, H * W)
+        if out is None:
+            out = torch.empty((m, 2, H, W), dtype=torch.float32, device=dev)
+            ogeom = dense
+        torch.cuda.current_stream(dev).synchronize()
+        if not m:
+            return out, (torch.empty((0, H, W), dtype=torch.uint8, device=dev) if mask is not None else None)
+        src, sgeom, msrc, msgeom = flows, geom, mask, mgeom
+        tmp = None
+        masks = [torch.empty((m, H, W), dtype=torch.uint8, device=dev) for _ in range(min(passes, 2))] if mask is not None else []
+        for k in range(passes):
+            if k % 2 == 0:
+                dst, dgeom = out, ogeom
+            else:
+                if tmp is None:
+                    tmp = torch.empty((m, 2, H, W), dtype=torch.float32, device=dev)
+                dst, dgeom = tmp, dense
+            mdst = masks[k % 2] if mask is not None else None
+            self.flow_median_device(src.data_ptr(), *sgeom, m, dst.data_ptr(), *dgeom, ksize, code,
+                                    msrc.data_ptr() if mask is not None else None, *msgeom,
+                                    mdst.data_ptr() if mask is not None else None, *mdense)
+            src, sgeom, msrc, msgeom = dst, dgeom, mdst, mdense
+            if mask is not None and code == MEDIAN_MODES["fill"] and k + 1 < passes and not bool(mdst.any()):
+                break
+        if src is not out:
+            out.copy_(src)
+            torch.cuda.current_stream(dev).synchronize()
+        return out, msrc if mask is not None else None
 
     def flow_tensor_bidir(self, frames, step: int, check: bool = True, alpha1: float = 0.01, alpha2: float = 0.5, out=None):
         """flow_tensor for both directions and the occlusion masks: (fwd, bwd, occ_fwd, occ_bwd) as torch tensors on the
