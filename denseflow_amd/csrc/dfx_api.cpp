@@ -8,6 +8,7 @@
 
 #include "dfx_pipeline.h"
 #include "fb_check_kernels.h"
+#include "flow_chain_kernels.h"
 #include "flow_median_kernels.h"
 #include "global_motion_kernels.h"
 #include "jpeg_kernels.h"
@@ -785,6 +786,65 @@ int dfx_flow_median_device(dfx_handle h, const dfx_median_desc *d) {
     a.out_stride = (long long)d->out_flow_stride_floats;
     a.mask_out_pitch = (long long)d->mask_out_pitch, a.mask_out_stride = (long long)d->mask_out_stride;
     fm_launch(h->stream, a);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return DFX_OK;
+}
+
+// ---- adjacent flows chained into long-range flows and dense trajectories (flow_chain_kernels.hip) ----
+int dfx_flow_chain_device(dfx_handle h, const dfx_chain_desc *d) {
+    if (!h)
+        return DFX_ERR_INVALID;
+    (void)dfx_finish_tails(h, 0, -1);
+    if (h->algo == DFX_ALGO_FRAMES)
+        return dfx_fail(h, DFX_ERR_UNSUPPORTED, "a DFX_ALGO_FRAMES handle computes no flow");
+    if (!d)
+        return dfx_fail(h, DFX_ERR_INVALID, "NULL descriptor");
+    if (d->n < 0)
+        return dfx_fail(h, DFX_ERR_INVALID, "n must be >= 0");
+    if (d->anchors < 0)
+        return dfx_fail(h, DFX_ERR_INVALID, "anchors must be >= 0");
+    if (d->n == 0 || d->anchors == 0)
+        return DFX_OK;
+    if (!d->d_flow || !d->d_out)
+        return dfx_fail(h, DFX_ERR_INVALID, "NULL device flows or output flows");
+    if (d->hop == 0 || d->length < 1 || d->anchor_step < 1)
+        return dfx_fail(h, DFX_ERR_INVALID, "hop != 0, length >= 1 and anchor_step >= 1 are required");
+    {
+        // the link indices are monotone in j and in k: the four corners bound them all
+        const long long j1 = (long long)(d->anchors - 1) * d->anchor_step, k1 = (long long)(d->length - 1) * d->hop;
+        const long long lo = (long long)d->first + std::min(k1, 0LL), hi = (long long)d->first + j1 + std::max(k1, 0LL);
+        if (lo < 0 || hi >= (long long)d->n)
+            return dfx_fail(h, DFX_ERR_INVALID, "a link index first + j * anchor_step + k * hop lies outside [0, n)");
+    }
+    if (d->emit != DFX_CHAIN_LAST && d->emit != DFX_CHAIN_ALL)
+        return dfx_fail(h, DFX_ERR_INVALID, "emit must be DFX_CHAIN_LAST or DFX_CHAIN_ALL");
+    if (d->border != DFX_WARP_BORDER_ZERO && d->border != DFX_WARP_BORDER_CLAMP)
+        return dfx_fail(h, DFX_ERR_INVALID, "border must be DFX_WARP_BORDER_ZERO or DFX_WARP_BORDER_CLAMP");
+    if (d->d_out == d->d_flow)
+        return dfx_fail(h, DFX_ERR_INVALID, "a chain cannot run in place: d_out != d_flow is required");
+    if (planar_strides_bad(h, d->row_pitch_floats, d->plane_stride_floats, d->flow_stride_floats))
+        return dfx_fail(h, DFX_ERR_INVALID, kPlanarStrides);
+    if (planar_strides_bad(h, d->out_row_pitch_floats, d->out_plane_stride_floats, d->out_flow_stride_floats))
+        return dfx_fail(h, DFX_ERR_INVALID, "output flows: out_row_pitch_floats >= W, out_plane_stride_floats >= H * out_row_pitch_floats "
+                                            "and out_flow_stride_floats >= 2 * out_plane_stride_floats are required");
+    if (d->d_occ && fb_occ_bad(h, d->occ_pitch, d->occ_stride))
+        return dfx_fail(h, DFX_ERR_INVALID, kFbOcc);
+    if (d->d_valid && fb_occ_bad(h, d->valid_pitch, d->valid_stride))
+        return dfx_fail(h, DFX_ERR_INVALID, "valid planes: valid_pitch >= W and valid_stride >= H * valid_pitch are required");
+    HIPCHK(h, hipSetDevice(h->device));
+    FcArgs a{};
+    a.flow = d->d_flow, a.occ = d->d_occ, a.out = d->d_out, a.valid = d->d_valid;
+    a.w = h->W, a.h = h->H;
+    a.first = d->first, a.hop = d->hop, a.length = d->length, a.anchors = d->anchors, a.anchor_step = d->anchor_step;
+    a.emit = d->emit, a.border = d->border;
+    a.row_pitch = (long long)d->row_pitch_floats, a.plane_stride = (long long)d->plane_stride_floats;
+    a.flow_stride = (long long)d->flow_stride_floats;
+    a.occ_pitch = (long long)d->occ_pitch, a.occ_stride = (long long)d->occ_stride;
+    a.out_pitch = (long long)d->out_row_pitch_floats, a.out_plane = (long long)d->out_plane_stride_floats;
+    a.out_stride = (long long)d->out_flow_stride_floats;
+    a.valid_pitch = (long long)d->valid_pitch, a.valid_stride = (long long)d->valid_stride;
+    fc_launch(h->stream, a);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return DFX_OK;

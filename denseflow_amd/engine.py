@@ -211,6 +211,34 @@ class DfxMedianDesc(C.Structure):
     ]
 
 
+class DfxChainDesc(C.Structure):
+    """dfx_chain_desc of include/dfx.h, field for field."""
+    _fields_ = [
+        ("d_flow", C.c_void_p),
+        ("row_pitch_floats", C.c_size_t),
+        ("plane_stride_floats", C.c_size_t),
+        ("flow_stride_floats", C.c_size_t),
+        ("n", C.c_int),
+        ("first", C.c_int),
+        ("hop", C.c_int),
+        ("length", C.c_int),
+        ("anchors", C.c_int),
+        ("anchor_step", C.c_int),
+        ("emit", C.c_int),
+        ("border", C.c_int),
+        ("d_occ", C.c_void_p),
+        ("occ_pitch", C.c_size_t),
+        ("occ_stride", C.c_size_t),
+        ("d_out", C.c_void_p),
+        ("out_row_pitch_floats", C.c_size_t),
+        ("out_plane_stride_floats", C.c_size_t),
+        ("out_flow_stride_floats", C.c_size_t),
+        ("d_valid", C.c_void_p),
+        ("valid_pitch", C.c_size_t),
+        ("valid_stride", C.c_size_t),
+    ]
+
+
 # ------------------------------------------------------------------------------------------ build
 
 def library_path() -> str:
@@ -311,6 +339,9 @@ def load_library():
     if hasattr(L, "dfx_flow_median_device"):  # a library built before the flow median (DFX_LIBRARY A/B) still loads
         L.dfx_flow_median_device.argtypes = [vp, C.POINTER(DfxMedianDesc)]
         L.dfx_flow_median_device.restype = i
+    if hasattr(L, "dfx_flow_chain_device"):  # a library built before the flow chain (DFX_LIBRARY A/B) still loads
+        L.dfx_flow_chain_device.argtypes = [vp, C.POINTER(DfxChainDesc)]
+        L.dfx_flow_chain_device.restype = i
     if hasattr(L, "dfxi_probe_planar_value_as"):  # test hook (selftest.hip)
         L.dfxi_probe_planar_value_as.argtypes = [i, i, vp, C.c_float, vp, sz]
         L.dfxi_probe_planar_value_as.restype = i
@@ -497,6 +528,42 @@ def _median_settings(ksize, mode, passes, has_mask):
     if mode == "fill" and not has_mask:
         raise ValueError('mode "fill" needs a mask')
     return int(ksize), MEDIAN_MODES[mode], int(passes)
+
+
+CHAIN_EMITS = {"last": 0, "all": 1}  # DFX_CHAIN_LAST / DFX_CHAIN_ALL
+
+
+def _chain_settings(n, length, first, hop, anchors, anchor_step, emit, border):
+    """(length, first, hop, anchors, anchor_step, emit code, border code) checked as dfx_flow_chain_device checks them,
+    before the library is reached; anchors None: as many chains as fit into the n flows (possibly none)."""
+    def whole(v, name):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"{name} must be an integer")
+        return int(v)
+
+    length, first, hop, anchor_step = whole(length, "length"), whole(first, "first"), whole(hop, "hop"), whole(anchor_step, "anchor_step")
+    if length < 1:
+        raise ValueError("length must be >= 1")
+    if hop == 0:
+        raise ValueError("hop must not be 0")
+    if anchor_step < 1:
+        raise ValueError("anchor_step must be >= 1")
+    if not isinstance(emit, str) or emit not in CHAIN_EMITS:
+        raise ValueError('emit must be "last" or "all"')
+    code = _warp_border(border)
+    k1 = (length - 1) * hop
+    lo, hi = first + min(k1, 0), first + max(k1, 0)  # the lowest and highest link index of anchor 0
+    if anchors is None:
+        if first < 0 or lo < 0:
+            raise ValueError("first: a link index first + k * hop lies below 0")
+        anchors = max(0, (n - 1 - hi) // anchor_step + 1)
+    else:
+        anchors = whole(anchors, "anchors")
+        if anchors < 0:
+            raise ValueError("anchors must be >= 0")
+        if anchors and (lo < 0 or hi + (anchors - 1) * anchor_step >= n):
+            raise ValueError("anchors: a link index first + j * anchor_step + k * hop lies outside the flows")
+    return length, first, hop, anchors, anchor_step, CHAIN_EMITS[emit], code
 
 
 def _warp_border(border):
@@ -1628,6 +1695,121 @@ class FlowEngine:
             out.copy_(src)
             torch.cuda.current_stream(dev).synchronize()
         return out, msrc if mask is not None else None
+
+    # -- adjacent flows chained into long-range flows and dense trajectories (dfx_flow_chain_device) ----
+    def flow_chain_device(self, d_flow_ptr: int, row_pitch_floats: int, plane_stride_floats: int, flow_stride_floats: int,
+                          n: int, d_out_ptr: int, out_row_pitch_floats: int, out_plane_stride_floats: int,
+                          out_flow_stride_floats: int, length: int, first: int = 0, hop: int = 1, anchors: int = 1,
+                          anchor_step: int = 1, emit: int = 0, border: int = 0, d_occ_ptr: int | None = None,
+                          occ_pitch: int = 0, occ_stride: int = 0, d_valid_ptr: int | None = None, valid_pitch: int = 0,
+                          valid_stride: int = 0):
+        """n planar float32 flows that are already in device memory: the fields of dfx_chain_desc (include/dfx.h) as
+        arguments, codes and raw pointers as the header gives them."""
+        d = DfxChainDesc(d_flow_ptr, row_pitch_floats, plane_stride_floats, flow_stride_floats, int(n), int(first), int(hop),
+                         int(length), int(anchors), int(anchor_step), int(emit), int(border), d_occ_ptr, occ_pitch, occ_stride,
+                         d_out_ptr, out_row_pitch_floats, out_plane_stride_floats, out_flow_stride_floats, d_valid_ptr,
+                         valid_pitch, valid_stride)
+        self._check(self._L.dfx_flow_chain_device(self._h, C.byref(d)))
+
+    def flow_chain(self, flows, length: int, first: int = 0, hop: int = 1, anchors: int | None = None, anchor_step: int = 1,
+                   emit: str = "last", border: str = "zero", occ=None):
+        """Adjacent flows composed into long-range flows: A_0 = 0, A_{k+1}(p) = A_k(p) + F_k(p + A_k(p)), bilinear samples
+        (dfx_flow_chain_device).
+
+        flows: (N, 2, H, W) float32, flows of adjacent frames.  Link k of anchor j reads flow first + j * anchor_step + k * hop
+        (hop -1 walks a list of backward flows down the clip); anchors None: as many chains as fit.  emit "last": the flow over
+        all `length` links per anchor; "all": the flow after every link, anchor by anchor (p + A_k(p) is the trajectory of pixel
+        p).  border "zero": a chain that leaves the frame is frozen; "clamp": it goes on from the nearest edge position.  occ:
+        optional (N, H, W) uint8 masks, one per flow, nonzero = occluded (as fb_check gives them).  Returns (out, valid):
+        (m * E, 2, H, W) float32 and (m * E, H, W) uint8, E = length for "all" and 1 otherwise; valid is 1 where every link so
+        far was sampled inside the frame from unoccluded taps."""
+        H, W = self.height, self.width
+        fl = np.asarray(flows)
+        if fl.dtype != np.float32 or fl.ndim != 4 or fl.shape[1:] != (2, H, W):
+            raise ValueError("flows must be (N, 2, H, W) float32")
+        n = fl.shape[0]
+        length, first, hop, m, anchor_step, ecode, bcode = _chain_settings(n, length, first, hop, anchors, anchor_step, emit, border)
+        fl = np.ascontiguousarray(fl)
+        if occ is not None:
+            occ = np.asarray(occ)
+            if occ.dtype != np.uint8 or occ.shape != (n, H, W):
+                raise ValueError("occ must be (N, H, W) uint8")
+            occ = np.ascontiguousarray(occ)
+        e = length if ecode else 1
+        out = np.empty((m * e, 2, H, W), np.float32)
+        valid = np.empty((m * e, H, W), np.uint8)
+        if m:
+            bufs = self._dev_bufs([fl.nbytes, occ.nbytes if occ is not None else 0, out.nbytes, valid.nbytes])
+            try:
+                src, docc, dst, dval = bufs
+                self._check(self._L.dfx_memcpy_h2d(self._h, src, fl.ctypes.data, fl.nbytes))
+                if occ is not None:
+                    self._check(self._L.dfx_memcpy_h2d(self._h, docc, occ.ctypes.data, occ.nbytes))
+                self.flow_chain_device(src, W, H * W, 2 * H * W, n, dst, W, H * W, 2 * H * W, length, first, hop, m, anchor_step,
+                                       ecode, bcode, docc if occ is not None else None, W, H * W, dval, W, H * W)
+                self._check(self._L.dfx_memcpy_d2h(self._h, out.ctypes.data, dst, out.nbytes))
+                self._check(self._L.dfx_memcpy_d2h(self._h, valid.ctypes.data, dval, valid.nbytes))
+            finally:
+                self._dev_free(bufs)
+        return out, valid
+
+    def flow_chain_tensor(self, flows, length: int, first: int = 0, hop: int = 1, anchors: int | None = None,
+                          anchor_step: int = 1, emit: str = "last", border: str = "zero", occ=None, out=None):
+        """flow_chain for torch tensors on this handle's device, read and written where they lie.
+
+        flows: (N, 2, H, W) torch.float32 with a contiguous innermost dimension, e.g. what flow_tensor returns; every stride is
+        taken from the tensor, so a slice of a larger tensor is read without a copy.  occ: optional (N, H, W) torch.uint8.
+        out: optional (m * E, 2, H, W) float32 tensor for the result, not `flows` itself.  Returns (out, valid): valid an
+        (m * E, H, W) uint8 tensor.
+
+        Torch's current stream on that device is synchronised before the call; the call returns with its device work
+        complete.  Raises ValueError before the library is reached for a wrong setting, dtype, device, shape or stride."""
+        import torch
+
+        H, W = self.height, self.width
+
+        def planes(t, what):  # (row pitch, plane stride, flow stride) of an (M, 2, H, W) float32 tensor
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 4 or tuple(t.shape[1:]) != (2, H, W):
+                raise ValueError(f"{what} must be an (N, 2, H, W) torch.float32 tensor")
+            st = t.stride()
+            pitch = st[2] if H > 1 else W
+            plane, flow = st[1], (st[0] if t.shape[0] > 1 else 2 * st[1])
+            if (st[3] != 1 and W > 1) or pitch < W or plane < H * pitch or flow < 2 * plane:
+                raise ValueError(f"{what}: the innermost dimension must be contiguous and rows, planes and flows must not overlap")
+            return pitch, plane, flow
+
+        geom = planes(flows, "flows")
+        n, dev = flows.shape[0], flows.device
+        length, first, hop, m, anchor_step, ecode, bcode = _chain_settings(n, length, first, hop, anchors, anchor_step, emit, border)
+        e = length if ecode else 1
+        ogeom_occ = (0, 0)
+        if occ is not None:
+            if not isinstance(occ, torch.Tensor) or occ.dtype != torch.uint8 or tuple(occ.shape) != (n, H, W):
+                raise ValueError("occ must be an (N, H, W) torch.uint8 tensor")
+            so = occ.stride()
+            occ_pitch = so[1] if H > 1 else W
+            ogeom_occ = (occ_pitch, so[0] if n > 1 else H * occ_pitch)
+            if (so[2] != 1 and W > 1) or ogeom_occ[0] < W or ogeom_occ[1] < H * ogeom_occ[0]:
+                raise ValueError("occ: the innermost dimension must be contiguous and rows and masks must not overlap")
+        if out is not None:
+            ogeom = planes(out, "out")
+            if out.shape[0] != m * e:
+                raise ValueError("out must be an (m * E, 2, H, W) torch.float32 tensor")
+            if out.data_ptr() == flows.data_ptr() and m and n:
+                raise ValueError("out must not be flows: a chain cannot run in place")
+        if dev.type != "cuda" or (dev.index is not None and dev.index != getattr(self, "_device", dev.index)):
+            raise ValueError("flows must be on this handle's device")
+        if any(t.device != dev for t in (occ, out) if t is not None):
+            raise ValueError("occ and out must be on the flows' device")
+        if out is None:
+            out = torch.empty((m * e, 2, H, W), dtype=torch.float32, device=dev)
+            ogeom = (W, H * W, 2 * H * W)
+        valid = torch.empty((m * e, H, W), dtype=torch.uint8, device=dev)
+        torch.cuda.current_stream(dev).synchronize()
+        if m:
+            self.flow_chain_device(flows.data_ptr(), *geom, n, out.data_ptr(), *ogeom, length, first, hop, m, anchor_step, ecode,
+                                   bcode, occ.data_ptr() if occ is not None else None, *ogeom_occ, valid.data_ptr(), W, H * W)
+        return out, valid
 
     def flow_tensor_bidir(self, frames, step: int, check: bool = True, alpha1: float = 0.01, alpha2: float = 0.5, out=None):
         """flow_tensor for both directions and the occlusion masks: (fwd, bwd, occ_fwd, occ_bwd) as torch tensors on the
