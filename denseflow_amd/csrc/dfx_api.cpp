@@ -9,6 +9,7 @@
 #include "dfx_pipeline.h"
 #include "fb_check_kernels.h"
 #include "flow_chain_kernels.h"
+#include "flow_project_kernels.h"
 #include "flow_median_kernels.h"
 #include "global_motion_kernels.h"
 #include "jpeg_kernels.h"
@@ -845,6 +846,84 @@ int dfx_flow_chain_device(dfx_handle h, const dfx_chain_desc *d) {
     a.out_stride = (long long)d->out_flow_stride_floats;
     a.valid_pitch = (long long)d->valid_pitch, a.valid_stride = (long long)d->valid_stride;
     fc_launch(h->stream, a);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return DFX_OK;
+}
+
+// ---- forward projection of flows: inverse and time-t flows, holes marked (flow_project_kernels.hip) ----
+size_t dfx_flow_project_work_bytes(dfx_handle h) {
+    if (!h)
+        return 0;
+    return (size_t)h->W * (size_t)h->H * FP_WORDS * sizeof(unsigned long long);
+}
+
+int dfx_flow_project_device(dfx_handle h, const dfx_project_desc *d) {
+    if (!h)
+        return DFX_ERR_INVALID;
+    (void)dfx_finish_tails(h, 0, -1);
+    if (h->algo == DFX_ALGO_FRAMES)
+        return dfx_fail(h, DFX_ERR_UNSUPPORTED, "a DFX_ALGO_FRAMES handle computes no flow");
+    if (!d)
+        return dfx_fail(h, DFX_ERR_INVALID, "NULL descriptor");
+    if (d->n < 0)
+        return dfx_fail(h, DFX_ERR_INVALID, "n must be >= 0");
+    if (d->n == 0)
+        return DFX_OK;
+    if (!d->d_flow || !d->d_work)
+        return dfx_fail(h, DFX_ERR_INVALID, "NULL device flows or workspace");
+    if (!d->d_out && !d->d_hole && !d->d_coverage)
+        return dfx_fail(h, DFX_ERR_INVALID, "one of d_out, d_hole and d_coverage is required");
+    if (!std::isfinite(d->t) || d->t == 0.0f)
+        return dfx_fail(h, DFX_ERR_INVALID, "t must be finite and nonzero");
+    if (!std::isfinite(d->scale))
+        return dfx_fail(h, DFX_ERR_INVALID, "scale must be finite");
+    if (!std::isfinite(d->min_weight) || !(d->min_weight >= 0.0f))
+        return dfx_fail(h, DFX_ERR_INVALID, "min_weight must be finite and >= 0");
+    if (d->d_out == d->d_flow)
+        return dfx_fail(h, DFX_ERR_INVALID, "a projection cannot run in place: d_out != d_flow is required");
+    if ((size_t)d->d_work % 8 != 0)
+        return dfx_fail(h, DFX_ERR_INVALID, "d_work must be 8-byte aligned");
+    const size_t per_flow = dfx_flow_project_work_bytes(h);
+    if (d->work_bytes < per_flow)
+        return dfx_fail(h, DFX_ERR_INVALID, "work_bytes must be at least dfx_flow_project_work_bytes");
+    if (planar_strides_bad(h, d->row_pitch_floats, d->plane_stride_floats, d->flow_stride_floats))
+        return dfx_fail(h, DFX_ERR_INVALID, kPlanarStrides);
+    if (d->d_importance && fb_occ_bad(h, d->importance_pitch_floats, d->importance_stride_floats))
+        return dfx_fail(h, DFX_ERR_INVALID, "importance planes: importance_pitch_floats >= W and importance_stride_floats >= H * "
+                                            "importance_pitch_floats are required");
+    if (d->d_occ && fb_occ_bad(h, d->occ_pitch, d->occ_stride))
+        return dfx_fail(h, DFX_ERR_INVALID, kFbOcc);
+    if (d->d_out && planar_strides_bad(h, d->out_row_pitch_floats, d->out_plane_stride_floats, d->out_flow_stride_floats))
+        return dfx_fail(h, DFX_ERR_INVALID, "output flows: out_row_pitch_floats >= W, out_plane_stride_floats >= H * out_row_pitch_floats "
+                                            "and out_flow_stride_floats >= 2 * out_plane_stride_floats are required");
+    if (d->d_hole && fb_occ_bad(h, d->hole_pitch, d->hole_stride))
+        return dfx_fail(h, DFX_ERR_INVALID, "hole planes: hole_pitch >= W and hole_stride >= H * hole_pitch are required");
+    if (d->d_coverage && fb_occ_bad(h, d->coverage_pitch_floats, d->coverage_stride_floats))
+        return dfx_fail(h, DFX_ERR_INVALID, "coverage planes: coverage_pitch_floats >= W and coverage_stride_floats >= H * "
+                                            "coverage_pitch_floats are required");
+    HIPCHK(h, hipSetDevice(h->device));
+    FpArgs a{};
+    a.flow = d->d_flow, a.imp = d->d_importance, a.occ = d->d_occ;
+    a.out = d->d_out, a.hole = d->d_hole, a.cov = d->d_coverage;
+    a.work = static_cast<unsigned long long *>(d->d_work);
+    a.n = d->n, a.w = h->W, a.h = h->H;
+    a.t = d->t;
+    a.sc = (double)d->scale / 256.0;
+    {
+        // Wmin = max(1, llrint(min_weight * 2^24)), at most 2^63 (a min_weight no sum can reach makes every pixel a hole)
+        const double m = (double)d->min_weight * 16777216.0;
+        a.wmin = m >= 9223372036854775808.0 ? (1ull << 63) : std::max<unsigned long long>(1ull, (unsigned long long)std::llrint(m));
+    }
+    a.row_pitch = (long long)d->row_pitch_floats, a.plane_stride = (long long)d->plane_stride_floats;
+    a.flow_stride = (long long)d->flow_stride_floats;
+    a.imp_pitch = (long long)d->importance_pitch_floats, a.imp_stride = (long long)d->importance_stride_floats;
+    a.occ_pitch = (long long)d->occ_pitch, a.occ_stride = (long long)d->occ_stride;
+    a.out_pitch = (long long)d->out_row_pitch_floats, a.out_plane = (long long)d->out_plane_stride_floats;
+    a.out_stride = (long long)d->out_flow_stride_floats;
+    a.hole_pitch = (long long)d->hole_pitch, a.hole_stride = (long long)d->hole_stride;
+    a.cov_pitch = (long long)d->coverage_pitch_floats, a.cov_stride = (long long)d->coverage_stride_floats;
+    fp_launch(h->stream, a, (long long)(d->work_bytes / per_flow));
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return DFX_OK;

@@ -239,6 +239,38 @@ class DfxChainDesc(C.Structure):
     ]
 
 
+class DfxProjectDesc(C.Structure):
+    """dfx_project_desc of include/dfx.h, field for field."""
+    _fields_ = [
+        ("d_flow", C.c_void_p),
+        ("row_pitch_floats", C.c_size_t),
+        ("plane_stride_floats", C.c_size_t),
+        ("flow_stride_floats", C.c_size_t),
+        ("n", C.c_int),
+        ("t", C.c_float),
+        ("scale", C.c_float),
+        ("min_weight", C.c_float),
+        ("d_importance", C.c_void_p),
+        ("importance_pitch_floats", C.c_size_t),
+        ("importance_stride_floats", C.c_size_t),
+        ("d_occ", C.c_void_p),
+        ("occ_pitch", C.c_size_t),
+        ("occ_stride", C.c_size_t),
+        ("d_out", C.c_void_p),
+        ("out_row_pitch_floats", C.c_size_t),
+        ("out_plane_stride_floats", C.c_size_t),
+        ("out_flow_stride_floats", C.c_size_t),
+        ("d_hole", C.c_void_p),
+        ("hole_pitch", C.c_size_t),
+        ("hole_stride", C.c_size_t),
+        ("d_coverage", C.c_void_p),
+        ("coverage_pitch_floats", C.c_size_t),
+        ("coverage_stride_floats", C.c_size_t),
+        ("d_work", C.c_void_p),
+        ("work_bytes", C.c_size_t),
+    ]
+
+
 # ------------------------------------------------------------------------------------------ build
 
 def library_path() -> str:
@@ -342,6 +374,11 @@ def load_library():
     if hasattr(L, "dfx_flow_chain_device"):  # a library built before the flow chain (DFX_LIBRARY A/B) still loads
         L.dfx_flow_chain_device.argtypes = [vp, C.POINTER(DfxChainDesc)]
         L.dfx_flow_chain_device.restype = i
+    if hasattr(L, "dfx_flow_project_device"):  # a library built before the flow projection (DFX_LIBRARY A/B) still loads
+        L.dfx_flow_project_device.argtypes = [vp, C.POINTER(DfxProjectDesc)]
+        L.dfx_flow_project_device.restype = i
+        L.dfx_flow_project_work_bytes.argtypes = [vp]
+        L.dfx_flow_project_work_bytes.restype = sz
     if hasattr(L, "dfxi_probe_planar_value_as"):  # test hook (selftest.hip)
         L.dfxi_probe_planar_value_as.argtypes = [i, i, vp, C.c_float, vp, sz]
         L.dfxi_probe_planar_value_as.restype = i
@@ -564,6 +601,31 @@ def _chain_settings(n, length, first, hop, anchors, anchor_step, emit, border):
         if anchors and (lo < 0 or hi + (anchors - 1) * anchor_step >= n):
             raise ValueError("anchors: a link index first + j * anchor_step + k * hop lies outside the flows")
     return length, first, hop, anchors, anchor_step, CHAIN_EMITS[emit], code
+
+
+PROJECT_WORDS = 3  # 64-bit words per pixel of the projection's workspace (Wsum, Su, Sv)
+
+
+def _project_settings(t, scale, min_weight):
+    """(t, scale, min_weight) as float32 values, checked as dfx_flow_project_device checks them, before the library is
+    reached; scale None: -t (the flow back to time 0)."""
+    def real(v, name):
+        if isinstance(v, (bool, str)) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise ValueError(f"{name} must be a number")
+        with np.errstate(over="ignore"):
+            v32 = np.float32(v)
+        if not np.isfinite(v32):
+            raise ValueError(f"{name} must be finite")
+        return v32
+
+    t32 = real(t, "t")
+    if t32 == 0:
+        raise ValueError("t must be nonzero")
+    scale32 = -t32 if scale is None else real(scale, "scale")
+    mw32 = real(min_weight, "min_weight")
+    if not mw32 >= 0:
+        raise ValueError("min_weight must be >= 0")
+    return float(t32), float(scale32), float(mw32)
 
 
 def _warp_border(border):
@@ -1810,6 +1872,169 @@ class FlowEngine:
             self.flow_chain_device(flows.data_ptr(), *geom, n, out.data_ptr(), *ogeom, length, first, hop, m, anchor_step, ecode,
                                    bcode, occ.data_ptr() if occ is not None else None, *ogeom_occ, valid.data_ptr(), W, H * W)
         return out, valid
+
+    # -- forward projection of flows: inverse and time-t flows, holes marked (dfx_flow_project_device) ----
+    def flow_project_work_bytes(self) -> int:
+        """The bytes of workspace one flow of this handle's size needs (dfx_flow_project_work_bytes)."""
+        return int(self._L.dfx_flow_project_work_bytes(self._h))
+
+    def flow_project_device(self, d_flow_ptr: int, row_pitch_floats: int, plane_stride_floats: int, flow_stride_floats: int,
+                            n: int, d_work_ptr: int, work_bytes: int, t: float = 1.0, scale: float = -1.0,
+                            min_weight: float = 0.25, d_out_ptr: int | None = None, out_row_pitch_floats: int = 0,
+                            out_plane_stride_floats: int = 0, out_flow_stride_floats: int = 0, d_hole_ptr: int | None = None,
+                            hole_pitch: int = 0, hole_stride: int = 0, d_coverage_ptr: int | None = None,
+                            coverage_pitch_floats: int = 0, coverage_stride_floats: int = 0,
+                            d_importance_ptr: int | None = None, importance_pitch_floats: int = 0,
+                            importance_stride_floats: int = 0, d_occ_ptr: int | None = None, occ_pitch: int = 0,
+                            occ_stride: int = 0):
+        """n planar float32 flows that are already in device memory: the fields of dfx_project_desc (include/dfx.h) as
+        arguments, raw pointers as the header gives them."""
+        d = DfxProjectDesc(d_flow_ptr, row_pitch_floats, plane_stride_floats, flow_stride_floats, int(n), t, scale, min_weight,
+                           d_importance_ptr, importance_pitch_floats, importance_stride_floats, d_occ_ptr, occ_pitch, occ_stride,
+                           d_out_ptr, out_row_pitch_floats, out_plane_stride_floats, out_flow_stride_floats, d_hole_ptr,
+                           hole_pitch, hole_stride, d_coverage_ptr, coverage_pitch_floats, coverage_stride_floats, d_work_ptr,
+                           work_bytes)
+        self._check(self._L.dfx_flow_project_device(self._h, C.byref(d)))
+
+    def flow_project(self, flows, t: float = 1.0, scale: float | None = None, importance=None, occ=None,
+                     min_weight: float = 0.25, coverage: bool = False):
+        """Flows carried forward along themselves to time t and written where they land, times `scale`
+        (dfx_flow_project_device): scale None is -t, the flow from time t back to the first frame; 1 - t the flow on to the
+        second; t = 1 with scale -1 the inverse flow.
+
+        flows: (N, 2, H, W) float32.  importance: optional (N, H, W) float32, > 0 counts, how much a source weighs against the
+        others landing on the same pixel.  occ: optional (N, H, W) uint8, nonzero = the source pixel is skipped.  min_weight:
+        the share of one full-weight source below which a target is a hole (0.25: a choice, see include/dfx.h).  Returns
+        (out, hole[, coverage]): (N, 2, H, W) float32 with +0 in the holes, (N, H, W) uint8 with 1 in the holes (the polarity
+        flow_median's fill and flow_chain's occ take), and with coverage=True (N, H, W) float32, the summed weight in
+        full-weight sources."""
+        t, scale, min_weight = _project_settings(t, scale, min_weight)
+        H, W = self.height, self.width
+        fl = np.asarray(flows)
+        if fl.dtype != np.float32 or fl.ndim != 4 or fl.shape[1:] != (2, H, W):
+            raise ValueError("flows must be (N, 2, H, W) float32")
+        fl = np.ascontiguousarray(fl)
+        n = fl.shape[0]
+        if importance is not None:
+            importance = np.asarray(importance)
+            if importance.dtype != np.float32 or importance.shape != (n, H, W):
+                raise ValueError("importance must be (N, H, W) float32")
+            importance = np.ascontiguousarray(importance)
+        if occ is not None:
+            occ = np.asarray(occ)
+            if occ.dtype != np.uint8 or occ.shape != (n, H, W):
+                raise ValueError("occ must be (N, H, W) uint8")
+            occ = np.ascontiguousarray(occ)
+        out = np.empty((n, 2, H, W), np.float32)
+        hole = np.empty((n, H, W), np.uint8)
+        cov = np.empty((n, H, W), np.float32) if coverage else None
+        if n:
+            per = self.flow_project_work_bytes()
+            wb = per * min(n, 8)
+            bufs = self._dev_bufs([fl.nbytes, importance.nbytes if importance is not None else 0,
+                                   occ.nbytes if occ is not None else 0, out.nbytes, hole.nbytes, cov.nbytes if coverage else 0, wb])
+            try:
+                src, dimp, docc, dst, dhole, dcov, work = bufs
+                self._check(self._L.dfx_memcpy_h2d(self._h, src, fl.ctypes.data, fl.nbytes))
+                if importance is not None:
+                    self._check(self._L.dfx_memcpy_h2d(self._h, dimp, importance.ctypes.data, importance.nbytes))
+                if occ is not None:
+                    self._check(self._L.dfx_memcpy_h2d(self._h, docc, occ.ctypes.data, occ.nbytes))
+                self.flow_project_device(src, W, H * W, 2 * H * W, n, work, wb, t, scale, min_weight, dst, W, H * W, 2 * H * W,
+                                         dhole, W, H * W, dcov if coverage else None, W, H * W,
+                                         dimp if importance is not None else None, W, H * W,
+                                         docc if occ is not None else None, W, H * W)
+                self._check(self._L.dfx_memcpy_d2h(self._h, out.ctypes.data, dst, out.nbytes))
+                self._check(self._L.dfx_memcpy_d2h(self._h, hole.ctypes.data, dhole, hole.nbytes))
+                if coverage:
+                    self._check(self._L.dfx_memcpy_d2h(self._h, cov.ctypes.data, dcov, cov.nbytes))
+            finally:
+                self._dev_free(bufs)
+        return (out, hole, cov) if coverage else (out, hole)
+
+    def flow_invert(self, flows, **kw):
+        """The inverse flow by forward projection: flow_project(flows, t=1, scale=-1, **kw)."""
+        return self.flow_project(flows, t=1.0, scale=-1.0, **kw)
+
+    def flow_project_tensor(self, flows, t: float = 1.0, scale: float | None = None, importance=None, occ=None,
+                            min_weight: float = 0.25, coverage: bool = False, out=None, work=None):
+        """flow_project for torch tensors on this handle's device, read and written where they lie.
+
+        flows: (N, 2, H, W) torch.float32 with a contiguous innermost dimension, e.g. what flow_tensor returns; every stride is
+        taken from the tensor, so a slice of a larger tensor is read without a copy.  importance: optional (N, H, W)
+        torch.float32; occ: optional (N, H, W) torch.uint8.  out: optional (N, 2, H, W) float32 tensor for the result, not
+        `flows` itself.  work: optional contiguous tensor of any dtype to use as the workspace, 8-byte aligned and at least
+        flow_project_work_bytes() large (more takes more flows per wave of launches); without it one for min(N, 8) flows is
+        allocated through torch.  Returns (out, hole[, coverage]): hole an (N, H, W) uint8 tensor, coverage an (N, H, W)
+        float32 tensor.
+
+        Torch's current stream on that device is synchronised before the call; the call returns with its device work
+        complete.  Raises ValueError before the library is reached for a wrong setting, dtype, device, shape or stride."""
+        import torch
+
+        t, scale, min_weight = _project_settings(t, scale, min_weight)
+        H, W = self.height, self.width
+
+        def planes(x, what):  # (row pitch, plane stride, flow stride) of an (N, 2, H, W) float32 tensor
+            if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.dim() != 4 or tuple(x.shape[1:]) != (2, H, W):
+                raise ValueError(f"{what} must be an (N, 2, H, W) torch.float32 tensor")
+            st = x.stride()
+            pitch = st[2] if H > 1 else W
+            plane, flow = st[1], (st[0] if x.shape[0] > 1 else 2 * st[1])
+            if (st[3] != 1 and W > 1) or pitch < W or plane < H * pitch or flow < 2 * plane:
+                raise ValueError(f"{what}: the innermost dimension must be contiguous and rows, planes and flows must not overlap")
+            return pitch, plane, flow
+
+        geom = planes(flows, "flows")
+        n, dev = flows.shape[0], flows.device
+
+        def plane(x, what, dtype):  # (row pitch, stride) of an (N, H, W) tensor
+            if not isinstance(x, torch.Tensor) or x.dtype != dtype or tuple(x.shape) != (n, H, W):
+                raise ValueError(f"{what} must be an (N, H, W) {dtype} tensor")
+            st = x.stride()
+            pitch = st[1] if H > 1 else W
+            g = (pitch, st[0] if n > 1 else H * pitch)
+            if (st[2] != 1 and W > 1) or g[0] < W or g[1] < H * g[0]:
+                raise ValueError(f"{what}: the innermost dimension must be contiguous and rows and planes must not overlap")
+            return g
+
+        igeom = plane(importance, "importance", torch.float32) if importance is not None else (0, 0)
+        cgeom = plane(occ, "occ", torch.uint8) if occ is not None else (0, 0)
+        if out is not None:
+            ogeom = planes(out, "out")
+            if out.shape[0] != n:
+                raise ValueError("out must be an (N, 2, H, W) torch.float32 tensor")
+            if out.data_ptr() == flows.data_ptr() and n:
+                raise ValueError("out must not be flows: a projection cannot run in place")
+        per = PROJECT_WORDS * 8 * H * W
+        if work is not None:
+            if not isinstance(work, torch.Tensor) or not work.is_contiguous():
+                raise ValueError("work must be a contiguous torch tensor")
+            work_bytes = work.numel() * work.element_size()
+            if work_bytes < per:
+                raise ValueError(f"work must hold at least {per} bytes (flow_project_work_bytes)")
+        if dev.type != "cuda" or (dev.index is not None and dev.index != getattr(self, "_device", dev.index)):
+            raise ValueError("flows must be on this handle's device")
+        if any(x.device != dev for x in (importance, occ, out, work) if x is not None):
+            raise ValueError("importance, occ, out and work must be on the flows' device")
+        if work is not None and work.data_ptr() % 8 != 0:
+            raise ValueError("work must be 8-byte aligned")
+        if out is None:
+            out = torch.empty((n, 2, H, W), dtype=torch.float32, device=dev)
+            ogeom = (W, H * W, 2 * H * W)
+        hole = torch.empty((n, H, W), dtype=torch.uint8, device=dev)
+        cov = torch.empty((n, H, W), dtype=torch.float32, device=dev) if coverage else None
+        if n:
+            if work is None:
+                work = torch.empty((per * min(n, 8) // 8,), dtype=torch.int64, device=dev)
+                work_bytes = work.numel() * 8
+            torch.cuda.current_stream(dev).synchronize()
+            self.flow_project_device(flows.data_ptr(), *geom, n, work.data_ptr(), work_bytes, t, scale, min_weight,
+                                     out.data_ptr(), *ogeom, hole.data_ptr(), W, H * W,
+                                     cov.data_ptr() if coverage else None, W, H * W,
+                                     importance.data_ptr() if importance is not None else None, *igeom,
+                                     occ.data_ptr() if occ is not None else None, *cgeom)
+        return (out, hole, cov) if coverage else (out, hole)
 
     def flow_tensor_bidir(self, frames, step: int, check: bool = True, alpha1: float = 0.01, alpha2: float = 0.5, out=None):
         """flow_tensor for both directions and the occlusion masks: (fwd, bwd, occ_fwd, occ_bwd) as torch tensors on the
