@@ -12,6 +12,7 @@
 #include "flow_project_kernels.h"
 #include "flow_median_kernels.h"
 #include "global_motion_kernels.h"
+#include "interpolate_kernels.h"
 #include "jpeg_kernels.h"
 #include "prepare_kernels.h"
 #include "quantize_kernels.h"
@@ -910,11 +911,7 @@ int dfx_flow_project_device(dfx_handle h, const dfx_project_desc *d) {
     a.n = d->n, a.w = h->W, a.h = h->H;
     a.t = d->t;
     a.sc = (double)d->scale / 256.0;
-    {
-        // Wmin = max(1, llrint(min_weight * 2^24)), at most 2^63 (a min_weight no sum can reach makes every pixel a hole)
-        const double m = (double)d->min_weight * 16777216.0;
-        a.wmin = m >= 9223372036854775808.0 ? (1ull << 63) : std::max<unsigned long long>(1ull, (unsigned long long)std::llrint(m));
-    }
+    a.wmin = fp_wmin(d->min_weight);
     a.row_pitch = (long long)d->row_pitch_floats, a.plane_stride = (long long)d->plane_stride_floats;
     a.flow_stride = (long long)d->flow_stride_floats;
     a.imp_pitch = (long long)d->importance_pitch_floats, a.imp_stride = (long long)d->importance_stride_floats;
@@ -924,6 +921,82 @@ int dfx_flow_project_device(dfx_handle h, const dfx_project_desc *d) {
     a.hole_pitch = (long long)d->hole_pitch, a.hole_stride = (long long)d->hole_stride;
     a.cov_pitch = (long long)d->coverage_pitch_floats, a.cov_stride = (long long)d->coverage_stride_floats;
     fp_launch(h->stream, a, (long long)(d->work_bytes / per_flow));
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return DFX_OK;
+}
+
+// ---- frame interpolation at time t from two frames and their flows (interpolate_kernels.hip) ----
+size_t dfx_interpolate_work_bytes(dfx_handle h, const dfx_interp_desc *d) {
+    if (!h || !d)
+        return 0;
+    return interp_work_bytes(h->W, h->H, d->fill_passes);
+}
+
+int dfx_interpolate_device(dfx_handle h, const dfx_interp_desc *d) {
+    if (!h)
+        return DFX_ERR_INVALID;
+    (void)dfx_finish_tails(h, 0, -1);
+    if (h->algo == DFX_ALGO_FRAMES)
+        return dfx_fail(h, DFX_ERR_UNSUPPORTED, "a DFX_ALGO_FRAMES handle computes no flow");
+    if (!d)
+        return dfx_fail(h, DFX_ERR_INVALID, "NULL descriptor");
+    if (d->n < 0)
+        return dfx_fail(h, DFX_ERR_INVALID, "n must be >= 0");
+    if (d->n == 0)
+        return DFX_OK;
+    if (!d->d_img0 || !d->d_img1 || !d->d_fwd || !d->d_work)
+        return dfx_fail(h, DFX_ERR_INVALID, "NULL device images, forward flows or workspace");
+    if (!d->d_out && !d->d_source)
+        return dfx_fail(h, DFX_ERR_INVALID, "nothing asked for: d_out and d_source are both NULL");
+    if (d->d_occ_bwd && !d->d_bwd)
+        return dfx_fail(h, DFX_ERR_INVALID, "d_occ_bwd needs d_bwd");
+    if (!std::isfinite(d->t) || !(d->t > 0.0f) || !(d->t < 1.0f))
+        return dfx_fail(h, DFX_ERR_INVALID, "t must be finite and inside (0, 1)");
+    if (!std::isfinite(d->min_weight) || !(d->min_weight >= 0.0f))
+        return dfx_fail(h, DFX_ERR_INVALID, "min_weight must be finite and >= 0");
+    if (d->fill_passes < 0 || d->fill_passes > INTERP_MAX_PASSES)
+        return dfx_fail(h, DFX_ERR_INVALID, "fill_passes must be 0 .. 16");
+    if (d->ksize != 3 && d->ksize != 5)
+        return dfx_fail(h, DFX_ERR_INVALID, "ksize must be 3 or 5");
+    if (d->out_dtype != DFX_PLANAR_F32 && d->out_dtype != DFX_WARP_U8)
+        return dfx_fail(h, DFX_ERR_INVALID, "out_dtype must be DFX_PLANAR_F32 or DFX_WARP_U8");
+    if (d->channels != 1 && d->channels != 3)
+        return dfx_fail(h, DFX_ERR_INVALID, "channels must be 1 or 3");
+    if (d->channels == 3 && d->layout != DFX_SRC_INTERLEAVED && d->layout != DFX_SRC_PLANAR)
+        return dfx_fail(h, DFX_ERR_INVALID, "layout must be DFX_SRC_INTERLEAVED or DFX_SRC_PLANAR");
+    if ((size_t)d->d_work % 8 != 0)
+        return dfx_fail(h, DFX_ERR_INVALID, "d_work must be 8-byte aligned");
+    if (d->work_bytes < dfx_interpolate_work_bytes(h, d))
+        return dfx_fail(h, DFX_ERR_INVALID, "work_bytes must be at least dfx_interpolate_work_bytes");
+    const bool planes = d->channels == 3 && d->layout == DFX_SRC_PLANAR, il3 = d->channels == 3 && !planes;
+    if (warp_image_strides_bad(h, il3, planes, d->img_pitch, d->img_plane_stride, d->img_image_stride))
+        return dfx_fail(h, DFX_ERR_INVALID, "images: a pitch or stride smaller than what it spans");
+    if (planar_strides_bad(h, d->row_pitch_floats, d->plane_stride_floats, d->flow_stride_floats))
+        return dfx_fail(h, DFX_ERR_INVALID, kPlanarStrides);
+    if ((d->d_occ_fwd || d->d_occ_bwd) && fb_occ_bad(h, d->occ_pitch, d->occ_stride))
+        return dfx_fail(h, DFX_ERR_INVALID, kFbOcc);
+    if (d->d_out && warp_image_strides_bad(h, il3, planes, d->out_pitch, d->out_plane_stride, d->out_image_stride))
+        return dfx_fail(h, DFX_ERR_INVALID, "interpolated images: a pitch or stride smaller than what it spans");
+    if (d->d_source && fb_occ_bad(h, d->source_pitch, d->source_stride))
+        return dfx_fail(h, DFX_ERR_INVALID, "source planes: source_pitch >= W and source_stride >= H * source_pitch are required");
+    HIPCHK(h, hipSetDevice(h->device));
+    InterpArgs a{};
+    a.img0 = d->d_img0, a.img1 = d->d_img1, a.fwd = d->d_fwd, a.bwd = d->d_bwd;
+    a.occ_fwd = d->d_occ_fwd, a.occ_bwd = d->d_occ_bwd;
+    a.out = d->d_out, a.source = d->d_source, a.work = d->d_work, a.work_bytes = d->work_bytes;
+    a.n = d->n, a.w = h->W, a.h = h->H;
+    a.channels = d->channels, a.planar = planes ? 1 : 0, a.out_dtype = d->out_dtype;
+    a.t = d->t, a.min_weight = d->min_weight, a.fill_passes = d->fill_passes, a.ksize = d->ksize;
+    a.img_pitch = (long long)d->img_pitch, a.img_plane = (long long)d->img_plane_stride;
+    a.img_image = (long long)d->img_image_stride;
+    a.row_pitch = (long long)d->row_pitch_floats, a.plane_stride = (long long)d->plane_stride_floats;
+    a.flow_stride = (long long)d->flow_stride_floats;
+    a.occ_pitch = (long long)d->occ_pitch, a.occ_stride = (long long)d->occ_stride;
+    a.out_pitch = (long long)d->out_pitch, a.out_plane = (long long)d->out_plane_stride;
+    a.out_image = (long long)d->out_image_stride;
+    a.source_pitch = (long long)d->source_pitch, a.source_stride = (long long)d->source_stride;
+    interp_launch(h->stream, a);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return DFX_OK;

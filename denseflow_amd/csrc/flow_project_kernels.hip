@@ -254,16 +254,33 @@ void fp_scatter_as(hipStream_t s, const FpArgs &a) {
                        s, a);
 }
 
-} // namespace
-
-void fp_launch(hipStream_t s, const FpArgs &args, long long flows_per_wave) {
-    if (args.n <= 0 || args.w <= 0 || args.h <= 0 || flows_per_wave <= 0)
-        return;
+// which accesses of the normalising pass take a lane's 4 pixels at once
+FpWide fp_wide(const FpArgs &args) {
     FpWide wide;
     wide.work = ((size_t)args.work & 15) == 0 && (args.w & 1) == 0;
     wide.out = args.out && dfx_planar_vec(args.out, args.out_stride, args.out_plane, args.out_pitch) == 4;
     wide.hole = args.hole && (((u64)(size_t)args.hole | (u64)args.hole_pitch | (u64)args.hole_stride) & 3) == 0;
     wide.cov = args.cov && dfx_planar_vec(args.cov, args.cov_stride, 0, args.cov_pitch) == 4;
+    return wide;
+}
+
+void fp_normalise(hipStream_t s, const FpArgs &a, const FpWide &wide) {
+    hipLaunchKernelGGL(k_fp_normalise, dim3((unsigned)((a.w + 255) / 256), (unsigned)((a.h + 3) / 4), (unsigned)a.n), dim3(256), 0, s, a,
+                       wide);
+}
+
+} // namespace
+
+void fp_renormalise(hipStream_t s, const FpArgs &args) {
+    if (args.n <= 0 || args.n > 65535 || args.w <= 0 || args.h <= 0)
+        return;
+    fp_normalise(s, args, fp_wide(args));
+}
+
+void fp_launch(hipStream_t s, const FpArgs &args, long long flows_per_wave) {
+    if (args.n <= 0 || args.w <= 0 || args.h <= 0 || flows_per_wave <= 0)
+        return;
+    const FpWide wide = fp_wide(args);
     const long long per_flow = (long long)args.w * args.h * FP_WORDS; // words
     const int chunk = (int)std::min<long long>(flows_per_wave, 65535);  // grid.z holds at most 65535 flows
     for (int i0 = 0; i0 < args.n; i0 += chunk) {
@@ -294,7 +311,6 @@ void fp_launch(hipStream_t s, const FpArgs &args, long long flows_per_wave) {
             else
                 fp_scatter_as<false, false>(s, a);
         }
-        hipLaunchKernelGGL(k_fp_normalise, dim3((unsigned)((a.w + 255) / 256), (unsigned)((a.h + 3) / 4), (unsigned)a.n), dim3(256), 0, s,
-                           a, wide);
+        fp_normalise(s, a, wide);
     }
 }

@@ -271,6 +271,43 @@ class DfxProjectDesc(C.Structure):
     ]
 
 
+class DfxInterpDesc(C.Structure):
+    """dfx_interp_desc of include/dfx.h, field for field."""
+    _fields_ = [
+        ("d_img0", C.c_void_p),
+        ("d_img1", C.c_void_p),
+        ("channels", C.c_int),
+        ("layout", C.c_int),
+        ("img_pitch", C.c_size_t),
+        ("img_plane_stride", C.c_size_t),
+        ("img_image_stride", C.c_size_t),
+        ("d_fwd", C.c_void_p),
+        ("d_bwd", C.c_void_p),
+        ("row_pitch_floats", C.c_size_t),
+        ("plane_stride_floats", C.c_size_t),
+        ("flow_stride_floats", C.c_size_t),
+        ("n", C.c_int),
+        ("t", C.c_float),
+        ("min_weight", C.c_float),
+        ("fill_passes", C.c_int),
+        ("ksize", C.c_int),
+        ("d_occ_fwd", C.c_void_p),
+        ("d_occ_bwd", C.c_void_p),
+        ("occ_pitch", C.c_size_t),
+        ("occ_stride", C.c_size_t),
+        ("out_dtype", C.c_int),
+        ("d_out", C.c_void_p),
+        ("out_pitch", C.c_size_t),
+        ("out_plane_stride", C.c_size_t),
+        ("out_image_stride", C.c_size_t),
+        ("d_source", C.c_void_p),
+        ("source_pitch", C.c_size_t),
+        ("source_stride", C.c_size_t),
+        ("d_work", C.c_void_p),
+        ("work_bytes", C.c_size_t),
+    ]
+
+
 # ------------------------------------------------------------------------------------------ build
 
 def library_path() -> str:
@@ -379,6 +416,11 @@ def load_library():
         L.dfx_flow_project_device.restype = i
         L.dfx_flow_project_work_bytes.argtypes = [vp]
         L.dfx_flow_project_work_bytes.restype = sz
+    if hasattr(L, "dfx_interpolate_device"):  # a library built before the frame interpolation (DFX_LIBRARY A/B) still loads
+        L.dfx_interpolate_device.argtypes = [vp, C.POINTER(DfxInterpDesc)]
+        L.dfx_interpolate_device.restype = i
+        L.dfx_interpolate_work_bytes.argtypes = [vp, C.POINTER(DfxInterpDesc)]
+        L.dfx_interpolate_work_bytes.restype = sz
     if hasattr(L, "dfxi_probe_planar_value_as"):  # test hook (selftest.hip)
         L.dfxi_probe_planar_value_as.argtypes = [i, i, vp, C.c_float, vp, sz]
         L.dfxi_probe_planar_value_as.restype = i
@@ -626,6 +668,42 @@ def _project_settings(t, scale, min_weight):
     if not mw32 >= 0:
         raise ValueError("min_weight must be >= 0")
     return float(t32), float(scale32), float(mw32)
+
+
+INTERP_MAX_PASSES = 16
+
+
+def _interp_settings(t, min_weight, fill_passes, ksize):
+    """(t, min_weight, fill_passes, ksize), t and min_weight as float32 values, checked as dfx_interpolate_device checks
+    them, before the library is reached."""
+    def real(v, name):
+        if isinstance(v, (bool, str)) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise ValueError(f"{name} must be a number")
+        with np.errstate(over="ignore"):
+            v32 = np.float32(v)
+        if not np.isfinite(v32):
+            raise ValueError(f"{name} must be finite")
+        return v32
+
+    t32 = real(t, "t")
+    if not (t32 > 0 and t32 < 1):
+        raise ValueError("t must be inside (0, 1)")
+    mw32 = real(min_weight, "min_weight")
+    if not mw32 >= 0:
+        raise ValueError("min_weight must be >= 0")
+    if isinstance(fill_passes, bool) or not isinstance(fill_passes, (int, np.integer)) or not 0 <= fill_passes <= INTERP_MAX_PASSES:
+        raise ValueError("fill_passes must be an integer 0 .. 16")
+    if isinstance(ksize, bool) or not isinstance(ksize, (int, np.integer)) or ksize not in (3, 5):
+        raise ValueError("ksize must be 3 or 5")
+    return float(t32), float(mw32), int(fill_passes), int(ksize)
+
+
+def _interp_work_bytes(w, h, fill_passes):
+    """interp_work_bytes of denseflow_amd/csrc/interpolate_kernels.hip: what dfx_interpolate_work_bytes returns for one pair."""
+    up16 = lambda b: (b + 15) & ~15  # noqa: E731
+    pp = ((w + 3) & ~3) * h
+    sums, g, hole = up16(w * h * PROJECT_WORDS * 8), up16(16 * pp), up16(2 * pp)
+    return sums + g * (2 if fill_passes > 0 else 1) + hole * (1 + (fill_passes > 0) + (fill_passes > 1)) + 8
 
 
 def _warp_border(border):
@@ -2035,6 +2113,236 @@ class FlowEngine:
                                      importance.data_ptr() if importance is not None else None, *igeom,
                                      occ.data_ptr() if occ is not None else None, *cgeom)
         return (out, hole, cov) if coverage else (out, hole)
+
+    # -- frame interpolation at time t from two frames and their flows (dfx_interpolate_device) ----
+    def interpolate_work_bytes(self, fill_passes: int = 3) -> int:
+        """The bytes of workspace one pair of this handle's size needs with that many fill passes
+        (dfx_interpolate_work_bytes; 0 for fill_passes outside 0 .. 16)."""
+        d = DfxInterpDesc()
+        d.fill_passes = int(fill_passes)
+        return int(self._L.dfx_interpolate_work_bytes(self._h, C.byref(d)))
+
+    def interpolate_device(self, d_img0_ptr: int, d_img1_ptr: int, channels: int, layout: int, img_pitch: int,
+                           img_plane_stride: int, img_image_stride: int, d_fwd_ptr: int, d_bwd_ptr: int | None,
+                           row_pitch_floats: int, plane_stride_floats: int, flow_stride_floats: int, n: int, d_work_ptr: int,
+                           work_bytes: int, t: float = 0.5, min_weight: float = 0.25, fill_passes: int = 3, ksize: int = 3,
+                           d_occ_fwd_ptr: int | None = None, d_occ_bwd_ptr: int | None = None, occ_pitch: int = 0,
+                           occ_stride: int = 0, out_dtype: int = WARP_U8, d_out_ptr: int | None = None, out_pitch: int = 0,
+                           out_plane_stride: int = 0, out_image_stride: int = 0, d_source_ptr: int | None = None,
+                           source_pitch: int = 0, source_stride: int = 0):
+        """n pairs of 8-bit images and their planar float32 flows that are already in device memory: the fields of
+        dfx_interp_desc (include/dfx.h) as arguments, codes and raw pointers as the header gives them."""
+        d = DfxInterpDesc(d_img0_ptr, d_img1_ptr, int(channels), int(layout), img_pitch, img_plane_stride, img_image_stride,
+                          d_fwd_ptr, d_bwd_ptr, row_pitch_floats, plane_stride_floats, flow_stride_floats, int(n), t,
+                          min_weight, int(fill_passes), int(ksize), d_occ_fwd_ptr, d_occ_bwd_ptr, occ_pitch, occ_stride,
+                          int(out_dtype), d_out_ptr, out_pitch, out_plane_stride, out_image_stride, d_source_ptr, source_pitch,
+                          source_stride, d_work_ptr, work_bytes)
+        self._check(self._L.dfx_interpolate_device(self._h, C.byref(d)))
+
+    def interpolate(self, img0, img1, fwd, bwd=None, t: float = 0.5, occ_fwd=None, occ_bwd=None, fill_passes: int = 3,
+                    ksize: int = 3, min_weight: float = 0.25, layout: str = "hwc", dtype=np.uint8, want_source: bool = False):
+        """The frames at time t between img0[i] (time 0) and img1[i] (time 1), from the frames and their flows
+        (dfx_interpolate_device): the forward flow is projected to time t, the holes of the projection are filled, both
+        frames are warped to time t and blended, each pixel from the frames in which it is visible.
+
+        img0, img1: uint8, (n, H, W), (n, H, W, 3) or, with layout="chw", (n, 3, H, W).  fwd: (n, 2, H, W) float32, the flows
+        img0 -> img1; bwd: optionally the flows img1 -> img0.  occ_fwd / occ_bwd: optional (n, H, W) uint8 occlusion masks
+        of those flows as fb_check gives them (occ_bwd needs bwd).  fill_passes (0 .. 16), ksize (3 or 5) and min_weight
+        are choices (3, 3 and 0.25 by default: see include/dfx.h).  dtype: np.uint8 (rounded to nearest even) or np.float32.
+        want_source: also return the (n, H, W) uint8 plane that says where each pixel came from: 0 both frames, 1 frame 0
+        only, 2 frame 1 only, 3 neither (the plain blend of the pixel's own bytes), + 4 where only the filled flows reached
+        it.  Returns out in the images' shape, or (out, source)."""
+        t, min_weight, fill_passes, ksize = _interp_settings(t, min_weight, fill_passes, ksize)
+        l = _warp_layout(layout)
+        code, np_dt = _warp_dtype(dtype)
+        if code not in (WARP_U8, PLANAR_F32):
+            raise ValueError("dtype must be np.uint8 or np.float32")
+        a0, ch = self._warp_images(img0, l, "img0")
+        a1, _ = self._warp_images(img1, l, "img1")
+        if a1.shape != a0.shape:
+            raise ValueError("img1 must have the shape of img0")
+        n = a0.shape[0]
+        H, W = self.height, self.width
+
+        def flows_in(f, what):
+            f = np.asarray(f)
+            if f.dtype != np.float32 or f.shape != (n, 2, H, W):
+                raise ValueError(f"{what} must be (n, 2, H, W) float32, one flow per pair")
+            return np.ascontiguousarray(f)
+
+        def mask_in(m, what):
+            m = np.asarray(m)
+            if m.dtype != np.uint8 or m.shape != (n, H, W):
+                raise ValueError(f"{what} must be (n, H, W) uint8")
+            return np.ascontiguousarray(m)
+
+        fwd = flows_in(fwd, "fwd")
+        bwd = flows_in(bwd, "bwd") if bwd is not None else None
+        if occ_bwd is not None and bwd is None:
+            raise ValueError("occ_bwd needs bwd")
+        occ_fwd = mask_in(occ_fwd, "occ_fwd") if occ_fwd is not None else None
+        occ_bwd = mask_in(occ_bwd, "occ_bwd") if occ_bwd is not None else None
+        out = np.empty(a0.shape, np_dt)
+        source = np.empty((n, H, W), np.uint8) if want_source else None
+        if n:
+            planes = ch == 3 and l == 1
+            pitch = W * (1 if ch == 1 or planes else 3)
+            plane = H * W if planes else 0
+            image = ch * H * W
+            wb = _interp_work_bytes(W, H, fill_passes) * min(n, 8)
+            ins = [x for x in (a0, a1, fwd, bwd, occ_fwd, occ_bwd) if x is not None]
+            outs = [out] + ([source] if want_source else [])
+            bufs = self._dev_bufs([x.nbytes for x in ins + outs] + [wb])
+            try:
+                for p, x in zip(bufs, ins):
+                    self._check(self._L.dfx_memcpy_h2d(self._h, p, x.ctypes.data, x.nbytes))
+                at = {id(x): p for p, x in zip(bufs, ins + outs)}
+                ptr = lambda x: None if x is None else at[id(x)]  # noqa: E731
+                self.interpolate_device(ptr(a0), ptr(a1), ch, l if ch == 3 else 0, pitch, plane, image, ptr(fwd), ptr(bwd), W,
+                                        H * W, 2 * H * W, n, bufs[-1], wb, t, min_weight, fill_passes, ksize, ptr(occ_fwd),
+                                        ptr(occ_bwd), W, H * W, code, ptr(out), pitch, plane, image, ptr(source), W, H * W)
+                for x in outs:
+                    self._check(self._L.dfx_memcpy_d2h(self._h, x.ctypes.data, at[id(x)], x.nbytes))
+            finally:
+                self._dev_free(bufs)
+        return (out, source) if want_source else out
+
+    def interpolate_tensor(self, img0, img1, fwd, bwd=None, t: float = 0.5, occ_fwd=None, occ_bwd=None, fill_passes: int = 3,
+                           ksize: int = 3, min_weight: float = 0.25, layout: str | None = None, dtype=None,
+                           want_source: bool = False, out=None, work=None):
+        """interpolate for torch tensors on this handle's device, read and written where they lie.
+
+        img0, img1: torch.uint8 tensors of equal shape and strides, (n, H, W), (n, 3, H, W) or (n, H, W, 3); the memory layout
+        and every stride are taken from img0 as warp_tensor takes them, so frames[:-s] and frames[s:] of one clip are read
+        without a copy.  fwd, bwd: (n, 2, H, W) torch.float32 with equal strides and a contiguous innermost dimension, e.g.
+        what flow_tensor_bidir returns; occ_fwd, occ_bwd: (n, H, W) torch.uint8 with equal strides.  dtype: torch.uint8
+        (default) or torch.float32.  out: optional tensor of that dtype and the images' shape and memory layout.  work:
+        optional contiguous tensor of any dtype to use as the workspace, 8-byte aligned and at least
+        interpolate_work_bytes(fill_passes) large (more takes more pairs per wave of launches); without it one for min(n, 8)
+        pairs is allocated through torch.  Returns out, or (out, source) with want_source, source an (n, H, W) uint8 tensor.
+
+        Torch's current stream on that device is synchronised before the call; the call returns with its device work
+        complete.  Raises ValueError before the library is reached for a wrong setting, dtype, device, shape or stride."""
+        import torch
+
+        t, min_weight, fill_passes, ksize = _interp_settings(t, min_weight, fill_passes, ksize)
+        codes = {torch.uint8: WARP_U8, torch.float32: PLANAR_F32}
+        tdt = torch.uint8 if dtype is None else dtype
+        if tdt not in codes:
+            raise ValueError("dtype must be torch.uint8 or torch.float32")
+        if layout is not None:
+            _warp_layout(layout)
+        for x, what in ((img0, "img0"), (img1, "img1")):
+            if not isinstance(x, torch.Tensor) or x.dtype != torch.uint8:
+                raise ValueError(f"{what} must be a torch.uint8 tensor")
+        H, W = self.height, self.width
+        ch, mem, pitch, plane, image, chw = self._warp_tensor_images(img0, layout, "img0")
+        n, dev = img0.shape[0], img0.device
+        if img1.shape != img0.shape or (n and img1.stride() != img0.stride()):
+            raise ValueError("img1 must have the shape and the strides of img0")
+
+        def planes(x, what):  # (row pitch, plane stride, flow stride) of an (n, 2, H, W) float32 tensor
+            if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or tuple(x.shape) != (n, 2, H, W):
+                raise ValueError(f"{what} must be an (n, 2, H, W) torch.float32 tensor, one flow per pair")
+            st = x.stride()
+            p = st[2] if H > 1 else W
+            g = (p, st[1], st[0] if n > 1 else 2 * st[1])
+            if (st[3] != 1 and W > 1) or g[0] < W or g[1] < H * g[0] or g[2] < 2 * g[1]:
+                raise ValueError(f"{what}: the innermost dimension must be contiguous and rows, planes and flows must not overlap")
+            return g
+
+        def mask(x, what):  # (row pitch, stride) of an (n, H, W) uint8 tensor
+            if not isinstance(x, torch.Tensor) or x.dtype != torch.uint8 or tuple(x.shape) != (n, H, W):
+                raise ValueError(f"{what} must be an (n, H, W) torch.uint8 tensor")
+            st = x.stride()
+            p = st[1] if H > 1 else W
+            g = (p, st[0] if n > 1 else H * p)
+            if (st[2] != 1 and W > 1) or g[0] < W or g[1] < H * g[0]:
+                raise ValueError(f"{what}: the innermost dimension must be contiguous and rows and masks must not overlap")
+            return g
+
+        geom = planes(fwd, "fwd")
+        if bwd is not None and planes(bwd, "bwd") != geom:
+            raise ValueError("bwd must have the strides of fwd")
+        if occ_bwd is not None and bwd is None:
+            raise ValueError("occ_bwd needs bwd")
+        ogeom = (0, 0)
+        if occ_fwd is not None:
+            ogeom = mask(occ_fwd, "occ_fwd")
+        if occ_bwd is not None:
+            g = mask(occ_bwd, "occ_bwd")
+            if occ_fwd is not None and g != ogeom:
+                raise ValueError("occ_bwd must have the strides of occ_fwd")
+            ogeom = g
+        if out is not None:
+            if not isinstance(out, torch.Tensor) or out.dtype != tdt or out.shape != img0.shape:
+                raise ValueError(f"out must be a {tdt} tensor of the images' shape")
+            och, omem, out_pitch, out_plane, out_image, _ = self._warp_tensor_images(out, layout, "out")
+            if (och, omem) != (ch, mem):
+                raise ValueError("out must lie in memory as the images do (interleaved or planar)")
+        per = _interp_work_bytes(W, H, fill_passes)
+        if work is not None:
+            if not isinstance(work, torch.Tensor) or not work.is_contiguous():
+                raise ValueError("work must be a contiguous torch tensor")
+            work_bytes = work.numel() * work.element_size()
+            if work_bytes < per:
+                raise ValueError(f"work must hold at least {per} bytes (interpolate_work_bytes)")
+        if dev.type != "cuda" or (dev.index is not None and dev.index != getattr(self, "_device", dev.index)):
+            raise ValueError("img0 must be on this handle's device")
+        if any(x.device != dev for x in (img1, fwd, bwd, occ_fwd, occ_bwd, out, work) if x is not None):
+            raise ValueError("img1, the flows, the masks, out and work must be on img0's device")
+        if work is not None and work.data_ptr() % 8 != 0:
+            raise ValueError("work must be 8-byte aligned")
+        if out is None:
+            if ch == 3 and mem == 0:  # interleaved memory, whatever the shape's order
+                base = torch.empty((n, H, W, 3), dtype=tdt, device=dev)
+                out = base.permute(0, 3, 1, 2) if chw else base
+                out_pitch, out_plane, out_image = 3 * W, 0, 3 * H * W
+            elif ch == 3:
+                base = torch.empty((n, 3, H, W), dtype=tdt, device=dev)
+                out = base if chw else base.permute(0, 2, 3, 1)
+                out_pitch, out_plane, out_image = W, H * W, 3 * H * W
+            else:
+                out = torch.empty((n, H, W), dtype=tdt, device=dev)
+                out_pitch, out_plane, out_image = W, 0, H * W
+        source = torch.empty((n, H, W), dtype=torch.uint8, device=dev) if want_source else None
+        if n:
+            if work is None:
+                work = torch.empty(((per * min(n, 8) + 7) // 8,), dtype=torch.int64, device=dev)
+                work_bytes = work.numel() * 8
+            torch.cuda.current_stream(dev).synchronize()
+            ptr = lambda x: x.data_ptr() if x is not None else None  # noqa: E731
+            self.interpolate_device(img0.data_ptr(), img1.data_ptr(), ch, mem, pitch, plane, image, fwd.data_ptr(), ptr(bwd),
+                                    *geom, n, work.data_ptr(), work_bytes, t, min_weight, fill_passes, ksize, ptr(occ_fwd),
+                                    ptr(occ_bwd), *ogeom, codes[tdt], out.data_ptr(), out_pitch, out_plane, out_image,
+                                    ptr(source), W, H * W)
+        return (out, source) if want_source else out
+
+    def interpolate_frames(self, frames, step: int = 1, ts=(0.5,), fill_passes: int = 3, ksize: int = 3,
+                           min_weight: float = 0.25, alpha1: float = 0.01, alpha2: float = 0.5):
+        """The in-between frames of a clip of gray frames: for every pair (i, i + step) of calc_optflows' pair rule, the
+        frames at the times `ts` between frame i (time 0) and frame i + step (time 1).  One calc_optflows_bidir with the
+        forward-backward masks, then one interpolate per t.  frames: N uint8 frames (H, W); step >= 1.  Returns an
+        (M, len(ts), H, W) uint8 array, M = max(N - step, 0)."""
+        step = int(step)
+        if step < 1:
+            raise ValueError("step must be >= 1")
+        ts = tuple(ts)
+        for t in ts:
+            _interp_settings(t, min_weight, fill_passes, ksize)
+        frames = [np.ascontiguousarray(f, dtype=np.uint8) for f in frames]
+        if any(f.shape != self._frame_shape() for f in frames):
+            raise ValueError("frame shape does not match the engine")
+        H, W = self.height, self.width
+        m = max(len(frames) - step, 0)
+        res = np.empty((m, len(ts), H, W), np.uint8)
+        if m == 0 or not ts:
+            return res
+        fwd, bwd, occ_f, occ_b = self.calc_optflows_bidir(frames, step, True, alpha1, alpha2)
+        clip = np.stack(frames)
+        for k, t in enumerate(ts):
+            res[:, k] = self.interpolate(clip[:m], clip[step:], fwd, bwd, t, occ_f, occ_b, fill_passes, ksize, min_weight)
+        return res
 
     def flow_tensor_bidir(self, frames, step: int, check: bool = True, alpha1: float = 0.01, alpha2: float = 0.5, out=None):
         """flow_tensor for both directions and the occlusion masks: (fwd, bwd, occ_fwd, occ_bwd) as torch tensors on the
