@@ -57,9 +57,7 @@ __device__ __forceinline__ float lane_from_right(float v) {
 
 // The interior tiles' primal differences: a - (a of lane - 1) and b - (b of lane - 1) for both halves, one v_subrev_f32 with
 // a DPP source each (lane 0: a - 0).  Inline assembly because the compiler packs the scalar subtractions back into
-// v_pk_add_f32 (SLP), which takes no DPP operand, and then keeps a v_mov_b32_dpp per half.  (The dual's u_right - u stays
-// compiler-generated: its result feeds v_max_f32 / v_min_f32, which would need a canonicalising v_max_f32 per half after
-// inline assembly — 8 VALU more per iteration than the DPP moves cost.)
+// v_pk_add_f32 (SLP), which takes no DPP operand, and then keeps a v_mov_b32_dpp per half.
 // s_nop 1: a DPP instruction reading a VGPR that a VALU instruction wrote needs two wait states in between.
 __device__ __forceinline__ void sub_from_left(f2 a, f2 b, f2 &da, f2 &db) {
     float r0, r1, r2, r3;
@@ -68,6 +66,39 @@ __device__ __forceinline__ void sub_from_left(f2 a, f2 b, f2 &da, f2 &db) {
         "v_subrev_f32_dpp %1, %5, %5 wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
         "v_subrev_f32_dpp %2, %6, %6 wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
         "v_subrev_f32_dpp %3, %7, %7 wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1"
+        : "=&v"(r0), "=&v"(r1), "=&v"(r2), "=&v"(r3)
+        : "v"(a.x), "v"(a.y), "v"(b.x), "v"(b.y));
+    da = pk_set(r0, r1);
+    db = pk_set(r2, r3);
+}
+
+// The interior tiles' dual differences: (a of lane + 1) - a and (b of lane + 1) - b for both halves, one v_sub_f32 with a DPP
+// source each (lane 63: 0 - a) instead of a v_mov_b32_dpp per half and a packed subtraction.  The same IEEE subtraction per
+// half.  Its results feed the max / min of the CUDA hypot reading, and in front of its own v_max_f32 / v_min_f32 the compiler
+// puts a canonicalising v_max_f32 per half after inline assembly (it cannot know that a difference is never a signalling
+// NaN): pk_dual<HYP, true> therefore forms max / min in assembly as well (pk_abs_max_min).
+//
+// What the loop costs now (profiles/tvl1_loop_diet/, static, interior tile, a role without skips, per iteration = 4 float2s of
+// two rows each): 550 vector instructions in k_tvl1_step_fused<true, 0> (581 before), 539 in k_tvl1_warp_head<0> (570), of
+// them 332 packed and 32 with a DPP source; 17 / 16 ds_*; 108 / 121 s_nop (87 / 103).  Three reductions made the difference,
+// each bit-identical and measured alone against the parent on one MI355X (bench.py --steps 20 --warmup 5, three alternations,
+// parent 540.6 - 541.2 pairs/s): the square root inside pk_dual_denominator without its NaN guard 543.5 - 545.5 (+0.7 %), that
+// and its half reciprocal root unrefined 547.6 - 549.3 (+1.4 %), this subtraction 541.9 - 543.9 (+0.4 %); all three on another
+// box 544.9 - 545.7 against 533.7 - 534.9 (+2.1 %).  Rejected: pk_threshold's two compares and two selects per half as one compare
+// of |rho| against l_t * grad, one v_bfi_b32 (l_t with the sign of the quotient) and one select — 8 vector instructions fewer
+// per iteration, bit-identical on 2^22 operands and at every boundary, but 540.4 - 542.1 alone (+0.07 %: inside the parent's
+// spread) and nothing on top of the others; it is valid for lambda >= 0 only, which the engine does not require, so it
+// needed a second path for such handles.  Not kept.
+#ifndef TVL1_DPP_USUB
+#define TVL1_DPP_USUB 1 // 0: v_mov_b32_dpp + compiler-generated subtractions (A/B switch for measurements)
+#endif
+__device__ __forceinline__ void sub_right_minus_self(f2 a, f2 b, f2 &da, f2 &db) {
+    float r0, r1, r2, r3;
+    asm("s_nop 1\n\t"
+        "v_sub_f32_dpp %0, %4, %4 wave_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+        "v_sub_f32_dpp %1, %5, %5 wave_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+        "v_sub_f32_dpp %2, %6, %6 wave_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+        "v_sub_f32_dpp %3, %7, %7 wave_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1"
         : "=&v"(r0), "=&v"(r1), "=&v"(r2), "=&v"(r3)
         : "v"(a.x), "v"(a.y), "v"(b.x), "v"(b.y));
     da = pk_set(r0, r1);
@@ -357,7 +388,10 @@ __device__ __forceinline__ double tile_iterate_trap(const Tvl1LevelCtx &c, TileS
             }
             // u_right - u: per half with the DPP source in the interior lean form, packed otherwise — the same bits
             f2 u1x, u2x;
-            if (LK && INTERIOR) {
+            constexpr bool USUB = LK && INTERIOR && TVL1_DPP_USUB && MATH != 1 && MATH != TVL1_HYP_LIBM;
+            if (USUB) {
+                sub_right_minus_self(T.u1[j], T.u2[j], u1x, u2x);
+            } else if (LK && INTERIOR) {
                 u1x = pk_set(lane_from_right(T.u1[j].x) - T.u1[j].x, lane_from_right(T.u1[j].y) - T.u1[j].y);
                 u2x = pk_set(lane_from_right(T.u2[j].x) - T.u2[j].x, lane_from_right(T.u2[j].y) - T.u2[j].y);
             } else {
@@ -365,8 +399,8 @@ __device__ __forceinline__ double tile_iterate_trap(const Tvl1LevelCtx &c, TileS
                 u2x = u2r - T.u2[j];
             }
             if (MATH != 1) {
-                pk_dual<MATH>(T.p11[j], T.p12[j], u1x, u1d - T.u1[j], taut, taut_s);
-                pk_dual<MATH>(T.p21[j], T.p22[j], u2x, u2d - T.u2[j], taut, taut_s);
+                pk_dual<MATH, USUB, LK>(T.p11[j], T.p12[j], u1x, u1d - T.u1[j], taut, taut_s);
+                pk_dual<MATH, USUB, LK>(T.p21[j], T.p22[j], u2x, u2d - T.u2[j], taut, taut_s);
             } else {
                 pk_dual_fast(T.p11[j], T.p12[j], u1x, u1d - T.u1[j], taut);
                 pk_dual_fast(T.p21[j], T.p22[j], u2x, u2d - T.u2[j], taut);
