@@ -7,6 +7,7 @@ inside libdfx.so.  There is no CPU fallback: a missing library or GPU raises.
 
 Tensor consumers: FlowEngine.calc_optflows_planar (numpy) and FlowEngine.flow_tensor (torch tensors in, an
 (M, 2, H, W) float32 torch tensor out, optionally bounded to [-1, 1]); torch is imported only inside flow_tensor.
+FlowEngine.flow_colour / flow_colour_tensor draw flows as colour images on the Middlebury wheel (colour_wheel()).
 """
 from .engine import (  # noqa: F401
     DfxError,
@@ -17,6 +18,7 @@ from .engine import (  # noqa: F401
     FlowEngine,
     algo_from_name,
     build_library,
+    colour_wheel,
     device_count,
     library_path,
     load_library,
@@ -31,6 +33,7 @@ __all__ = [
     "FlowEngine",
     "algo_from_name",
     "build_library",
+    "colour_wheel",
     "device_count",
     "library_path",
     "load_library",

@@ -9,6 +9,7 @@
 #include "dfx_pipeline.h"
 #include "fb_check_kernels.h"
 #include "flow_chain_kernels.h"
+#include "flow_colour_kernels.h"
 #include "flow_project_kernels.h"
 #include "flow_median_kernels.h"
 #include "global_motion_kernels.h"
@@ -997,6 +998,74 @@ int dfx_interpolate_device(dfx_handle h, const dfx_interp_desc *d) {
     a.out_image = (long long)d->out_image_stride;
     a.source_pitch = (long long)d->source_pitch, a.source_stride = (long long)d->source_stride;
     interp_launch(h->stream, a);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return DFX_OK;
+}
+
+// ---- flows as colour images: the Middlebury wheel, unknown pixels marked (flow_colour_kernels.hip) ----
+int dfx_flow_colour_device(dfx_handle h, const dfx_colour_desc *d) {
+    if (!h)
+        return DFX_ERR_INVALID;
+    (void)dfx_finish_tails(h, 0, -1);
+    if (h->algo == DFX_ALGO_FRAMES)
+        return dfx_fail(h, DFX_ERR_UNSUPPORTED, "a DFX_ALGO_FRAMES handle computes no flow");
+    if (!d)
+        return dfx_fail(h, DFX_ERR_INVALID, "NULL descriptor");
+    if (d->n < 0)
+        return dfx_fail(h, DFX_ERR_INVALID, "n must be >= 0");
+    if (d->n == 0)
+        return DFX_OK;
+    if (!d->d_flow || !d->d_out)
+        return dfx_fail(h, DFX_ERR_INVALID, "NULL device flows or colour images");
+    if (d->norm != DFX_COLOUR_NORM_FIXED && d->norm != DFX_COLOUR_NORM_FLOW && d->norm != DFX_COLOUR_NORM_BATCH)
+        return dfx_fail(h, DFX_ERR_INVALID, "norm must be DFX_COLOUR_NORM_FIXED, DFX_COLOUR_NORM_FLOW or DFX_COLOUR_NORM_BATCH");
+    if (d->norm == DFX_COLOUR_NORM_FIXED && !(std::isfinite(d->max_rad) && d->max_rad >= 1e-6f && d->max_rad <= 1e9f))
+        return dfx_fail(h, DFX_ERR_INVALID, "max_rad must be finite and in [1e-6, 1e9]");
+    if (d->norm != DFX_COLOUR_NORM_FIXED && !d->d_max2)
+        return dfx_fail(h, DFX_ERR_INVALID, "a measured norm needs d_max2");
+    if (d->order != DFX_SRC_BGR && d->order != DFX_SRC_RGB)
+        return dfx_fail(h, DFX_ERR_INVALID, "order must be DFX_SRC_BGR or DFX_SRC_RGB");
+    if (d->layout != DFX_SRC_INTERLEAVED && d->layout != DFX_SRC_PLANAR)
+        return dfx_fail(h, DFX_ERR_INVALID, "layout must be DFX_SRC_INTERLEAVED or DFX_SRC_PLANAR");
+    if (planar_strides_bad(h, d->row_pitch_floats, d->plane_stride_floats, d->flow_stride_floats))
+        return dfx_fail(h, DFX_ERR_INVALID, kPlanarStrides);
+    if (d->d_mask && fb_occ_bad(h, d->mask_pitch, d->mask_stride))
+        return dfx_fail(h, DFX_ERR_INVALID, "mask planes: mask_pitch >= W and mask_stride >= H * mask_pitch are required");
+    const bool planes = d->layout == DFX_SRC_PLANAR;
+    if (warp_image_strides_bad(h, !planes, planes, d->out_pitch, d->out_plane_stride, d->out_image_stride))
+        return dfx_fail(h, DFX_ERR_INVALID, "colour images: a pitch or stride smaller than what it spans");
+    bool fplanes = false;
+    if (d->d_frame) {
+        if (d->frame_channels != 1 && d->frame_channels != 3)
+            return dfx_fail(h, DFX_ERR_INVALID, "frame_channels must be 1 or 3");
+        if (d->frame_channels == 3 && d->frame_layout != DFX_SRC_INTERLEAVED && d->frame_layout != DFX_SRC_PLANAR)
+            return dfx_fail(h, DFX_ERR_INVALID, "frame_layout must be DFX_SRC_INTERLEAVED or DFX_SRC_PLANAR");
+        fplanes = d->frame_channels == 3 && d->frame_layout == DFX_SRC_PLANAR;
+        if (warp_image_strides_bad(h, d->frame_channels == 3 && !fplanes, fplanes, d->frame_pitch, d->frame_plane_stride,
+                                   d->frame_image_stride))
+            return dfx_fail(h, DFX_ERR_INVALID, "frames: a pitch or stride smaller than what it spans");
+        if (d->alpha256 < 0 || d->alpha256 > 256)
+            return dfx_fail(h, DFX_ERR_INVALID, "alpha256 must be 0 .. 256");
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    FlowvisArgs a{};
+    a.flow = d->d_flow, a.mask = d->d_mask, a.max2 = d->d_max2, a.out = d->d_out, a.frame = d->d_frame;
+    a.n = d->n, a.w = h->W, a.h = h->H;
+    a.row_pitch = (long long)d->row_pitch_floats, a.plane_stride = (long long)d->plane_stride_floats;
+    a.flow_stride = (long long)d->flow_stride_floats;
+    a.mask_pitch = (long long)d->mask_pitch, a.mask_stride = (long long)d->mask_stride;
+    a.out_pitch = (long long)d->out_pitch, a.out_plane = (long long)d->out_plane_stride;
+    a.out_image = (long long)d->out_image_stride;
+    a.norm = d->norm, a.max_rad = d->max_rad;
+    a.bgr = d->order == DFX_SRC_BGR ? 1 : 0, a.planar = planes ? 1 : 0;
+    a.unknown[0] = d->unknown[0], a.unknown[1] = d->unknown[1], a.unknown[2] = d->unknown[2];
+    if (d->d_frame) {
+        a.frame_channels = d->frame_channels, a.frame_planar = fplanes ? 1 : 0, a.alpha256 = d->alpha256;
+        a.frame_pitch = (long long)d->frame_pitch, a.frame_plane = (long long)d->frame_plane_stride;
+        a.frame_image = (long long)d->frame_image_stride;
+    }
+    flowvis_launch(h->stream, a);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return DFX_OK;

@@ -308,6 +308,37 @@ class DfxInterpDesc(C.Structure):
     ]
 
 
+class DfxColourDesc(C.Structure):
+    """dfx_colour_desc of include/dfx.h, field for field."""
+    _fields_ = [
+        ("d_flow", C.c_void_p),
+        ("row_pitch_floats", C.c_size_t),
+        ("plane_stride_floats", C.c_size_t),
+        ("flow_stride_floats", C.c_size_t),
+        ("n", C.c_int),
+        ("d_mask", C.c_void_p),
+        ("mask_pitch", C.c_size_t),
+        ("mask_stride", C.c_size_t),
+        ("norm", C.c_int),
+        ("max_rad", C.c_float),
+        ("d_max2", C.c_void_p),
+        ("order", C.c_int),
+        ("layout", C.c_int),
+        ("d_out", C.c_void_p),
+        ("out_pitch", C.c_size_t),
+        ("out_plane_stride", C.c_size_t),
+        ("out_image_stride", C.c_size_t),
+        ("unknown", C.c_uint8 * 3),
+        ("d_frame", C.c_void_p),
+        ("frame_channels", C.c_int),
+        ("frame_layout", C.c_int),
+        ("frame_pitch", C.c_size_t),
+        ("frame_plane_stride", C.c_size_t),
+        ("frame_image_stride", C.c_size_t),
+        ("alpha256", C.c_int),
+    ]
+
+
 # ------------------------------------------------------------------------------------------ build
 
 def library_path() -> str:
@@ -421,6 +452,9 @@ def load_library():
         L.dfx_interpolate_device.restype = i
         L.dfx_interpolate_work_bytes.argtypes = [vp, C.POINTER(DfxInterpDesc)]
         L.dfx_interpolate_work_bytes.restype = sz
+    if hasattr(L, "dfx_flow_colour_device"):  # a library built before the colour coding (DFX_LIBRARY A/B) still loads
+        L.dfx_flow_colour_device.argtypes = [vp, C.POINTER(DfxColourDesc)]
+        L.dfx_flow_colour_device.restype = i
     if hasattr(L, "dfxi_probe_planar_value_as"):  # test hook (selftest.hip)
         L.dfxi_probe_planar_value_as.argtypes = [i, i, vp, C.c_float, vp, sz]
         L.dfxi_probe_planar_value_as.restype = i
@@ -704,6 +738,53 @@ def _interp_work_bytes(w, h, fill_passes):
     pp = ((w + 3) & ~3) * h
     sums, g, hole = up16(w * h * PROJECT_WORDS * 8), up16(16 * pp), up16(2 * pp)
     return sums + g * (2 if fill_passes > 0 else 1) + hole * (1 + (fill_passes > 0) + (fill_passes > 1)) + 8
+
+
+COLOUR_NORMS = {"fixed": 0, "flow": 1, "batch": 2}  # DFX_COLOUR_NORM_FIXED / _FLOW / _BATCH
+COLOUR_WHEEL_SEGMENTS = (("RY", 15), ("YG", 6), ("GC", 4), ("CB", 11), ("BM", 13), ("MR", 6))
+
+
+def colour_wheel() -> np.ndarray:
+    """The (55, 3) uint8 RGB colour wheel of Baker et al. 2011 that dfx_flow_colour_device interpolates on (include/dfx.h)."""
+    rows = []
+    for name, length in COLOUR_WHEEL_SEGMENTS:
+        for j in range(length):
+            q = 255 * j // length
+            rows.append({"RY": (255, q, 0), "YG": (255 - q, 255, 0), "GC": (0, 255, q), "CB": (0, 255 - q, 255),
+                         "BM": (q, 0, 255), "MR": (255, 0, 255 - q)}[name])
+    return np.array(rows, np.uint8)
+
+
+def _colour_settings(norm, max_rad, order, layout, unknown, alpha):
+    """(norm code, max_rad, order code, layout code, unknown bytes, alpha256), checked as dfx_flow_colour_device checks them,
+    before the library is reached.  max_rad belongs to norm="fixed" and to it alone."""
+    if not isinstance(norm, str) or norm not in COLOUR_NORMS:
+        raise ValueError('norm must be "fixed", "flow" or "batch"')
+    code = COLOUR_NORMS[norm]
+    rad = 0.0
+    if code == 0:
+        if isinstance(max_rad, (bool, str)) or not isinstance(max_rad, (int, float, np.integer, np.floating)):
+            raise ValueError('max_rad must be a number with norm="fixed"')
+        with np.errstate(over="ignore"):
+            r32 = np.float32(max_rad)
+        if not (np.isfinite(r32) and np.float32(1e-6) <= r32 <= np.float32(1e9)):
+            raise ValueError("max_rad must be finite and in [1e-6, 1e9]")
+        rad = float(r32)
+    elif max_rad is not None:
+        raise ValueError('max_rad applies to norm="fixed" only')
+    if not isinstance(order, str) or order not in SRC_ORDERS:
+        raise ValueError('order must be "bgr" or "rgb"')
+    lay = _warp_layout(layout)
+    try:
+        unk = tuple(int(c) for c in unknown)
+        ok = len(unk) == 3 and all(0 <= c <= 255 and int(u) == u and not isinstance(u, bool) for c, u in zip(unk, unknown))
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError("unknown must be three integers 0 .. 255")
+    if isinstance(alpha, (bool, str)) or not isinstance(alpha, (int, float, np.integer, np.floating)) or not 0 <= alpha <= 1:
+        raise ValueError("alpha must be a number in [0, 1]")
+    return code, rad, SRC_ORDERS[order], lay, unk, int(round(float(alpha) * 256))
 
 
 def _warp_border(border):
@@ -2343,6 +2424,168 @@ class FlowEngine:
         for k, t in enumerate(ts):
             res[:, k] = self.interpolate(clip[:m], clip[step:], fwd, bwd, t, occ_f, occ_b, fill_passes, ksize, min_weight)
         return res
+
+    # -- flows as colour images: the Middlebury wheel, unknown pixels marked (dfx_flow_colour_device) ----
+    def flow_colour_device(self, d_flow_ptr: int, row_pitch_floats: int, plane_stride_floats: int, flow_stride_floats: int,
+                           n: int, d_out_ptr: int, out_pitch: int, out_plane_stride: int, out_image_stride: int,
+                           norm: int = 1, max_rad: float = 0.0, d_max2_ptr: int | None = None, order: int = 1,
+                           layout: int = 0, unknown=(0, 0, 0), d_mask_ptr: int | None = None, mask_pitch: int = 0,
+                           mask_stride: int = 0, d_frame_ptr: int | None = None, frame_channels: int = 0,
+                           frame_layout: int = 0, frame_pitch: int = 0, frame_plane_stride: int = 0,
+                           frame_image_stride: int = 0, alpha256: int = 256):
+        """n planar float32 flows that are already in device memory, as colour images: the fields of dfx_colour_desc
+        (include/dfx.h) as arguments, codes and raw pointers as the header gives them."""
+        d = DfxColourDesc(d_flow_ptr, row_pitch_floats, plane_stride_floats, flow_stride_floats, int(n), d_mask_ptr, mask_pitch,
+                          mask_stride, int(norm), float(max_rad), d_max2_ptr, int(order), int(layout), d_out_ptr, out_pitch,
+                          out_plane_stride, out_image_stride, (C.c_uint8 * 3)(*[int(c) for c in unknown]), d_frame_ptr,
+                          int(frame_channels), int(frame_layout), frame_pitch, frame_plane_stride, frame_image_stride,
+                          int(alpha256))
+        self._check(self._L.dfx_flow_colour_device(self._h, C.byref(d)))
+
+    def flow_colour(self, flows, norm: str = "flow", max_rad: float | None = None, mask=None, order: str = "rgb",
+                    layout: str = "hwc", unknown=(0, 0, 0), frame=None, alpha: float = 0.5, return_max: bool = False):
+        """Flows as colour images on the Middlebury wheel (Baker et al. 2011; dfx_flow_colour_device): hue from the direction,
+        saturation from the magnitude over a radius R.
+
+        flows: (n, 2, H, W) float32.  norm "flow": R is the largest magnitude of the known pixels of each flow; "batch": of
+        all n flows (torchvision's flow_to_image rule); "fixed": R = max_rad, longer vectors are darkened.  mask: optional
+        (n, H, W) uint8, nonzero = unknown (an occlusion mask, a hole plane, a mask_out).  Unknown pixels — masked, NaN,
+        infinite or beyond 1e9 — get the colour `unknown` (in the output's channel order) and do not enter R.  order "rgb" or
+        "bgr"; layout "hwc": (n, H, W, 3) uint8, "chw": (n, 3, H, W).  frame: optional uint8 frames to blend over, (n, H, W)
+        gray or 3 channels in the output's order and layout; alpha is the weight of the colours, alpha256 =
+        int(round(alpha * 256)).  return_max: also return the radii sqrt(M2) as an (n,) float32 array and sqrt(MB2)."""
+        code, rad, ocode, lay, unk, a256 = _colour_settings(norm, max_rad, order, layout, unknown, alpha)
+        H, W = self.height, self.width
+        fl = np.asarray(flows)
+        if fl.dtype != np.float32 or fl.ndim != 4 or fl.shape[1:] != (2, H, W):
+            raise ValueError("flows must be (n, 2, H, W) float32")
+        fl = np.ascontiguousarray(fl)
+        n = fl.shape[0]
+        if mask is not None:
+            mask = np.asarray(mask)
+            if mask.dtype != np.uint8 or mask.shape != (n, H, W):
+                raise ValueError("mask must be (n, H, W) uint8")
+            mask = np.ascontiguousarray(mask)
+        fch = 0
+        if frame is not None:
+            frame = np.asarray(frame)
+            if frame.dtype != np.uint8 or frame.shape not in ((n, H, W), (n, 3, H, W) if lay else (n, H, W, 3)):
+                raise ValueError("frame must be uint8, (n, H, W) or the images' shape")
+            frame = np.ascontiguousarray(frame)
+            fch = 1 if frame.ndim == 3 else 3
+        out = np.empty((n, 3, H, W) if lay else (n, H, W, 3), np.uint8)
+        m2 = np.zeros(n + 1, np.float32)
+        if n:
+            want_max = code != 0 or return_max
+            bufs = self._dev_bufs([fl.nbytes, out.nbytes, m2.nbytes, mask.nbytes if mask is not None else 0,
+                                   frame.nbytes if frame is not None else 0])
+            try:
+                self._check(self._L.dfx_memcpy_h2d(self._h, bufs[0], fl.ctypes.data, fl.nbytes))
+                if mask is not None:
+                    self._check(self._L.dfx_memcpy_h2d(self._h, bufs[3], mask.ctypes.data, mask.nbytes))
+                if frame is not None:
+                    self._check(self._L.dfx_memcpy_h2d(self._h, bufs[4], frame.ctypes.data, frame.nbytes))
+                geom = (W, H * W, 3 * H * W) if lay else (3 * W, 0, 3 * H * W)
+                fgeom = (W, 0, H * W) if fch == 1 else geom
+                self.flow_colour_device(bufs[0], W, H * W, 2 * H * W, n, bufs[1], *geom, code, rad,
+                                        bufs[2] if want_max else None, ocode, lay, unk,
+                                        bufs[3] if mask is not None else None, W, H * W,
+                                        bufs[4] if frame is not None else None, fch, lay, *fgeom, a256)
+                self._check(self._L.dfx_memcpy_d2h(self._h, out.ctypes.data, bufs[1], out.nbytes))
+                if want_max:
+                    self._check(self._L.dfx_memcpy_d2h(self._h, m2.ctypes.data, bufs[2], m2.nbytes))
+            finally:
+                self._dev_free(bufs)
+        if return_max:
+            r = np.sqrt(m2)
+            return out, r[:n], r[n]
+        return out
+
+    def flow_colour_tensor(self, flows, norm: str = "flow", max_rad: float | None = None, mask=None, order: str = "rgb",
+                           layout: str = "hwc", unknown=(0, 0, 0), frame=None, alpha: float = 0.5, return_max: bool = False,
+                           out=None):
+        """flow_colour for torch tensors on this handle's device, read and written where they lie.
+
+        flows: (n, 2, H, W) torch.float32 with a contiguous innermost dimension, e.g. what flow_tensor returns; every stride is
+        taken from the tensor, so a slice of a larger tensor is read without a copy.  mask: optional (n, H, W) torch.uint8.
+        frame: optional torch.uint8, (n, H, W), (n, 3, H, W) or (n, H, W, 3), interleaved or planar in memory under either
+        shape, channels in the output's order.  out: optional torch.uint8 tensor of shape (n, H, W, 3) (layout "hwc") or
+        (n, 3, H, W) ("chw"), interleaved or planar in memory; otherwise the images are allocated contiguous in that shape.
+        return_max: also return the radii sqrt(M2) as an (n,) float32 tensor and sqrt(MB2) as a 0-d tensor.
+        norm="batch", order="rgb", layout="chw" is torchvision's flow_to_image up to the unknown-pixel rule and the
+        polynomial angle.
+
+        Torch's current stream on that device is synchronised before the call; the call returns with its device work
+        complete.  Raises ValueError before the library is reached for a wrong setting, dtype, device, shape or stride."""
+        import torch
+
+        code, rad, ocode, lay, unk, a256 = _colour_settings(norm, max_rad, order, layout, unknown, alpha)
+        H, W = self.height, self.width
+        if not isinstance(flows, torch.Tensor) or flows.dtype != torch.float32 or flows.dim() != 4 or \
+                tuple(flows.shape[1:]) != (2, H, W):
+            raise ValueError("flows must be an (n, 2, H, W) torch.float32 tensor")
+        n, dev = flows.shape[0], flows.device
+        sf = flows.stride()
+        row_pitch = sf[2] if H > 1 else W
+        flow_plane, flow_stride = sf[1], (sf[0] if n > 1 else 2 * sf[1])
+        if (sf[3] != 1 and W > 1) or row_pitch < W or flow_plane < H * row_pitch or flow_stride < 2 * flow_plane:
+            raise ValueError("flows: the innermost dimension must be contiguous and rows, planes and flows must not overlap")
+        mask_pitch = mask_stride = 0
+        if mask is not None:
+            if not isinstance(mask, torch.Tensor) or mask.dtype != torch.uint8 or tuple(mask.shape) != (n, H, W):
+                raise ValueError("mask must be an (n, H, W) torch.uint8 tensor")
+            sm = mask.stride()
+            mask_pitch = sm[1] if H > 1 else W
+            mask_stride = sm[0] if n > 1 else H * mask_pitch
+            if (sm[2] != 1 and W > 1) or mask_pitch < W or mask_stride < H * mask_pitch:
+                raise ValueError("mask: the innermost dimension must be contiguous and rows and masks must not overlap")
+        fch, fmem, fgeom = 0, 0, (0, 0, 0)
+        if frame is not None:
+            if not isinstance(frame, torch.Tensor) or frame.dtype != torch.uint8 or frame.dim() < 3 or frame.shape[0] != n:
+                raise ValueError("frame must be a torch.uint8 tensor, (n, H, W), (n, 3, H, W) or (n, H, W, 3)")
+            fch, fmem, fp, fpl, fim, _ = self._warp_tensor_images(frame, layout, "frame")
+            fgeom = (fp, fpl, fim)
+        shape = (n, 3, H, W) if lay else (n, H, W, 3)
+        if out is not None:
+            if not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or tuple(out.shape) != shape:
+                raise ValueError(f"out must be a torch.uint8 tensor of shape {shape}")
+            _, omem, op, opl, oim, _ = self._warp_tensor_images(out, layout, "out")
+        if dev.type != "cuda" or (dev.index is not None and dev.index != getattr(self, "_device", dev.index)):
+            raise ValueError("flows must be on this handle's device")
+        if any(t.device != dev for t in (mask, frame, out) if t is not None):
+            raise ValueError("mask, frame and out must be on the flows' device")
+        if out is None:
+            out = torch.empty(shape, dtype=torch.uint8, device=dev)
+            omem, op, opl, oim = (1, W, H * W, 3 * H * W) if lay else (0, 3 * W, 0, 3 * H * W)
+        want_max = code != 0 or return_max
+        m2 = torch.zeros(n + 1, dtype=torch.float32, device=dev) if want_max else None
+        torch.cuda.current_stream(dev).synchronize()
+        if n:
+            self.flow_colour_device(flows.data_ptr(), row_pitch, flow_plane, flow_stride, n, out.data_ptr(), op, opl, oim,
+                                    code, rad, m2.data_ptr() if want_max else None, ocode, omem, unk,
+                                    mask.data_ptr() if mask is not None else None, mask_pitch, mask_stride,
+                                    frame.data_ptr() if frame is not None else None, fch, fmem, *fgeom, a256)
+        if return_max:
+            r = torch.sqrt(m2)
+            return out, r[:n], r[n]
+        return out
+
+    def flow_colour_key(self, size: int):
+        """The usual legend disc as a (size, size, 3) uint8 RGB image: flow_colour of the radial flow u = x - c, v = y - c
+        with c = (size - 1) / 2, everything outside the disc of radius c masked (black).  The handle's own size does not
+        matter: a size x size handle of the same algorithm and device is used for the call where it differs."""
+        if isinstance(size, bool) or not isinstance(size, (int, np.integer)) or size < 1:
+            raise ValueError("size must be a positive integer")
+        size = int(size)
+        c = np.float32(size - 1) / np.float32(2)
+        d = np.arange(size, dtype=np.float32) - c
+        u, v = np.broadcast_to(d[None, :], (size, size)), np.broadcast_to(d[:, None], (size, size))
+        flow = np.stack([u, v]).astype(np.float32)[None]
+        mask = ((u * u + v * v) > c * c).astype(np.uint8)[None]
+        if (self.width, self.height) == (size, size):
+            return self.flow_colour(flow, mask=mask)[0]
+        with FlowEngine(size, size, self.algorithm, device=self._device) as eng:
+            return eng.flow_colour(flow, mask=mask)[0]
 
     def flow_tensor_bidir(self, frames, step: int, check: bool = True, alpha1: float = 0.01, alpha2: float = 0.5, out=None):
         """flow_tensor for both directions and the occlusion masks: (fwd, bwd, occ_fwd, occ_bwd) as torch tensors on the
