@@ -540,9 +540,49 @@ namespace {
 // alpha1 / alpha2 of the check: finite and not negative
 inline bool fb_alpha_ok(float a) { return std::isfinite(a) && a >= 0.0f; }
 const char *const kFbAlpha = "alpha1 and alpha2 must be finite and >= 0";
-const char *const kFbOcc = "mask planes: occ_pitch >= W and occ_stride >= H * occ_pitch are required";
-inline bool fb_occ_bad(dfx_handle h, size_t occ_pitch, size_t occ_stride) {
-    return occ_pitch < (size_t)h->W || occ_pitch > ((size_t)1 << 40) || occ_stride < occ_pitch * (size_t)h->H;
+const char *const kPlanarStridesOut = "output flows: out_row_pitch_floats >= W, out_plane_stride_floats >= H * out_row_pitch_floats "
+                                      "and out_flow_stride_floats >= 2 * out_plane_stride_floats are required";
+
+// The stride rule of one plane per item — a mask or any other (n, H, W) plane of bytes or floats: DFX_OK where the plane is
+// absent or its strides span it, else the refusal.  The text names the descriptor's fields: "<what> planes:
+// <field>_pitch<unit> >= W ...", unit "_floats" where the strides count floats.
+int plane_check(dfx_handle h, bool present, size_t pitch, size_t stride, const char *what, const char *field,
+                const char *unit = "") {
+    if (!present || !(pitch < (size_t)h->W || pitch > ((size_t)1 << 40) || stride < pitch * (size_t)h->H))
+        return DFX_OK;
+    const std::string p = std::string(field) + "_pitch" + unit, s = std::string(field) + "_stride" + unit;
+    return dfx_fail(h, DFX_ERR_INVALID, std::string(what) + " planes: " + p + " >= W and " + s + " >= H * " + p + " are required");
+}
+
+// What every call on finished flows opens with.  True: go on.  False: return *status, a refusal or — an empty batch —
+// DFX_OK.  has_desc: the descriptor is not NULL (a call without one says true).
+bool post_begin(dfx_handle h, bool has_desc, int n, int *status) {
+    *status = DFX_ERR_INVALID;
+    if (!h)
+        return false;
+    (void)dfx_finish_tails(h, 0, -1);
+    if (h->algo == DFX_ALGO_FRAMES)
+        *status = dfx_fail(h, DFX_ERR_UNSUPPORTED, "a DFX_ALGO_FRAMES handle computes no flow");
+    else if (!has_desc)
+        *status = dfx_fail(h, DFX_ERR_INVALID, "NULL descriptor");
+    else if (n < 0)
+        *status = dfx_fail(h, DFX_ERR_INVALID, "n must be >= 0");
+    else
+        *status = DFX_OK;
+    return *status == DFX_OK && n != 0;
+}
+extern "C++" { // (this file is one extern "C" block, which takes no template)
+template <class Desc>
+bool post_begin(dfx_handle h, const Desc *d, int *status) {
+    return post_begin(h, d != nullptr, d ? d->n : 0, status);
+}
+}
+
+// ... and what it closes with: the launches' errors, the stream drained.
+int post_finish(dfx_handle h) {
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return DFX_OK;
 }
 } // namespace
 
@@ -571,8 +611,8 @@ int dfx_calc_batch_bidir_device(dfx_handle h, const uint8_t *d_frames, size_t pi
         return dfx_fail(h, DFX_ERR_INVALID, "pitch/stride smaller than a frame");
     if (M > 0 && planar_strides_bad(h, row_pitch_floats, plane_stride_floats, flow_stride_floats))
         return dfx_fail(h, DFX_ERR_INVALID, kPlanarStrides);
-    if (M > 0 && check && fb_occ_bad(h, occ_pitch, occ_stride))
-        return dfx_fail(h, DFX_ERR_INVALID, kFbOcc);
+    if (int e = plane_check(h, M > 0 && check, occ_pitch, occ_stride, "mask", "occ"))
+        return e;
     OutSpec out;
     out.planar = out.bidir = true;
     out.elem = DFX_PLANAR_F32;
@@ -587,24 +627,17 @@ int dfx_fb_check_device(dfx_handle h, const float *d_fwd, const float *d_bwd, si
                         size_t plane_stride_floats, size_t flow_stride_floats, int n, float alpha1, float alpha2,
                         uint8_t *d_occ, size_t occ_pitch, size_t occ_stride, float *d_err, size_t err_pitch_floats,
                         size_t err_stride_floats) {
-    if (!h)
-        return DFX_ERR_INVALID;
-    (void)dfx_finish_tails(h, 0, -1);
-    if (h->algo == DFX_ALGO_FRAMES)
-        return dfx_fail(h, DFX_ERR_UNSUPPORTED, "a DFX_ALGO_FRAMES handle computes no flow");
-    if (n < 0)
-        return dfx_fail(h, DFX_ERR_INVALID, "n must be >= 0");
-    if (n == 0)
-        return DFX_OK;
+    int st;
+    if (!post_begin(h, true, n, &st))
+        return st;
     if (!d_fwd || !d_bwd || !d_occ)
         return dfx_fail(h, DFX_ERR_INVALID, "NULL device flows or mask planes");
     if (planar_strides_bad(h, row_pitch_floats, plane_stride_floats, flow_stride_floats))
         return dfx_fail(h, DFX_ERR_INVALID, kPlanarStrides);
-    if (fb_occ_bad(h, occ_pitch, occ_stride))
-        return dfx_fail(h, DFX_ERR_INVALID, kFbOcc);
-    if (d_err && (err_pitch_floats < (size_t)h->W || err_pitch_floats > ((size_t)1 << 40) ||
-                  err_stride_floats < err_pitch_floats * (size_t)h->H))
-        return dfx_fail(h, DFX_ERR_INVALID, "err planes: err_pitch_floats >= W and err_stride_floats >= H * err_pitch_floats are required");
+    if (int e = plane_check(h, true, occ_pitch, occ_stride, "mask", "occ"))
+        return e;
+    if (int e = plane_check(h, d_err != nullptr, err_pitch_floats, err_stride_floats, "err", "err", "_floats"))
+        return e;
     if (!fb_alpha_ok(alpha1) || !fb_alpha_ok(alpha2))
         return dfx_fail(h, DFX_ERR_INVALID, kFbAlpha);
     HIPCHK(h, hipSetDevice(h->device));
@@ -617,9 +650,7 @@ int dfx_fb_check_device(dfx_handle h, const float *d_fwd, const float *d_bwd, si
     a.err_pitch = (long long)err_pitch_floats, a.err_stride = (long long)err_stride_floats;
     a.alpha1 = alpha1, a.alpha2 = alpha2;
     fb_check_launch(h->stream, a);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return DFX_OK;
+    return post_finish(h);
 }
 
 // ---- the backward warp of 8-bit images by a flow (warp_kernels.hip) ----
@@ -636,17 +667,9 @@ bool warp_image_strides_bad(dfx_handle h, bool interleaved3, bool planes, size_t
 } // namespace
 
 int dfx_warp_device(dfx_handle h, const dfx_warp_desc *d) {
-    if (!h)
-        return DFX_ERR_INVALID;
-    (void)dfx_finish_tails(h, 0, -1);
-    if (h->algo == DFX_ALGO_FRAMES)
-        return dfx_fail(h, DFX_ERR_UNSUPPORTED, "a DFX_ALGO_FRAMES handle computes no flow");
-    if (!d)
-        return dfx_fail(h, DFX_ERR_INVALID, "NULL descriptor");
-    if (d->n < 0)
-        return dfx_fail(h, DFX_ERR_INVALID, "n must be >= 0");
-    if (d->n == 0)
-        return DFX_OK;
+    int st;
+    if (!post_begin(h, d, &st))
+        return st;
     if (!d->d_src || !d->d_flow)
         return dfx_fail(h, DFX_ERR_INVALID, "NULL device images or flows");
     if (!d->d_out && !d->d_valid && !d->d_stats)
@@ -668,10 +691,10 @@ int dfx_warp_device(dfx_handle h, const dfx_warp_desc *d) {
         return dfx_fail(h, DFX_ERR_INVALID, kPlanarStrides);
     if (d->d_out && warp_image_strides_bad(h, il3, planes, d->out_pitch, d->out_plane_stride, d->out_image_stride))
         return dfx_fail(h, DFX_ERR_INVALID, "warped images: a pitch or stride smaller than what it spans");
-    if (d->d_occ && fb_occ_bad(h, d->occ_pitch, d->occ_stride))
-        return dfx_fail(h, DFX_ERR_INVALID, kFbOcc);
-    if (d->d_valid && fb_occ_bad(h, d->valid_pitch, d->valid_stride))
-        return dfx_fail(h, DFX_ERR_INVALID, "valid planes: valid_pitch >= W and valid_stride >= H * valid_pitch are required");
+    if (int e = plane_check(h, d->d_occ != nullptr, d->occ_pitch, d->occ_stride, "mask", "occ"))
+        return e;
+    if (int e = plane_check(h, d->d_valid != nullptr, d->valid_pitch, d->valid_stride, "valid", "valid"))
+        return e;
     HIPCHK(h, hipSetDevice(h->device));
     WarpArgs a{};
     a.src = d->d_src, a.ref = d->d_ref, a.flow = d->d_flow, a.out = d->d_out, a.occ = d->d_occ, a.valid = d->d_valid;
@@ -687,24 +710,14 @@ int dfx_warp_device(dfx_handle h, const dfx_warp_desc *d) {
     a.occ_pitch = (long long)d->occ_pitch, a.occ_stride = (long long)d->occ_stride;
     a.valid_pitch = (long long)d->valid_pitch, a.valid_stride = (long long)d->valid_stride;
     warp_launch(h->stream, a);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return DFX_OK;
+    return post_finish(h);
 }
 
 // ---- the global (camera) motion of a flow: robust fit and removal (global_motion_kernels.hip) ----
 int dfx_global_motion_device(dfx_handle h, const dfx_gm_desc *d) {
-    if (!h)
-        return DFX_ERR_INVALID;
-    (void)dfx_finish_tails(h, 0, -1);
-    if (h->algo == DFX_ALGO_FRAMES)
-        return dfx_fail(h, DFX_ERR_UNSUPPORTED, "a DFX_ALGO_FRAMES handle computes no flow");
-    if (!d)
-        return dfx_fail(h, DFX_ERR_INVALID, "NULL descriptor");
-    if (d->n < 0)
-        return dfx_fail(h, DFX_ERR_INVALID, "n must be >= 0");
-    if (d->n == 0)
-        return DFX_OK;
+    int st;
+    if (!post_begin(h, d, &st))
+        return st;
     if (!d->d_flow || !d->d_result)
         return dfx_fail(h, DFX_ERR_INVALID, "NULL device flows or result records");
     if ((size_t)d->d_result % 8 != 0)
@@ -719,13 +732,12 @@ int dfx_global_motion_device(dfx_handle h, const dfx_gm_desc *d) {
         return dfx_fail(h, DFX_ERR_INVALID, "growth must be finite and >= 1");
     if (planar_strides_bad(h, d->row_pitch_floats, d->plane_stride_floats, d->flow_stride_floats))
         return dfx_fail(h, DFX_ERR_INVALID, kPlanarStrides);
-    if (d->d_mask && fb_occ_bad(h, d->mask_pitch, d->mask_stride))
-        return dfx_fail(h, DFX_ERR_INVALID, "mask planes: mask_pitch >= W and mask_stride >= H * mask_pitch are required");
+    if (int e = plane_check(h, d->d_mask != nullptr, d->mask_pitch, d->mask_stride, "mask", "mask"))
+        return e;
     if (d->d_out && planar_strides_bad(h, d->out_row_pitch_floats, d->out_plane_stride_floats, d->out_flow_stride_floats))
-        return dfx_fail(h, DFX_ERR_INVALID, "output flows: out_row_pitch_floats >= W, out_plane_stride_floats >= H * out_row_pitch_floats "
-                                            "and out_flow_stride_floats >= 2 * out_plane_stride_floats are required");
-    if (d->d_moving && fb_occ_bad(h, d->moving_pitch, d->moving_stride))
-        return dfx_fail(h, DFX_ERR_INVALID, "moving planes: moving_pitch >= W and moving_stride >= H * moving_pitch are required");
+        return dfx_fail(h, DFX_ERR_INVALID, kPlanarStridesOut);
+    if (int e = plane_check(h, d->d_moving != nullptr, d->moving_pitch, d->moving_stride, "moving", "moving"))
+        return e;
     if (h->W > GM_MAX_SIDE || h->H > GM_MAX_SIDE)
         return dfx_fail(h, DFX_ERR_UNSUPPORTED, "the integer sums are bounded for frames of at most 8192 x 8192");
     HIPCHK(h, hipSetDevice(h->device));
@@ -740,24 +752,14 @@ int dfx_global_motion_device(dfx_handle h, const dfx_gm_desc *d) {
     a.out_stride = (long long)d->out_flow_stride_floats;
     a.moving_pitch = (long long)d->moving_pitch, a.moving_stride = (long long)d->moving_stride;
     gm_launch(h->stream, a);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return DFX_OK;
+    return post_finish(h);
 }
 
 // ---- median filter and occlusion fill of flows, mask-aware (flow_median_kernels.hip) ----
 int dfx_flow_median_device(dfx_handle h, const dfx_median_desc *d) {
-    if (!h)
-        return DFX_ERR_INVALID;
-    (void)dfx_finish_tails(h, 0, -1);
-    if (h->algo == DFX_ALGO_FRAMES)
-        return dfx_fail(h, DFX_ERR_UNSUPPORTED, "a DFX_ALGO_FRAMES handle computes no flow");
-    if (!d)
-        return dfx_fail(h, DFX_ERR_INVALID, "NULL descriptor");
-    if (d->n < 0)
-        return dfx_fail(h, DFX_ERR_INVALID, "n must be >= 0");
-    if (d->n == 0)
-        return DFX_OK;
+    int st;
+    if (!post_begin(h, d, &st))
+        return st;
     if (!d->d_flow || !d->d_out)
         return dfx_fail(h, DFX_ERR_INVALID, "NULL device flows or output flows");
     if (d->ksize != 3 && d->ksize != 5)
@@ -771,12 +773,11 @@ int dfx_flow_median_device(dfx_handle h, const dfx_median_desc *d) {
     if (planar_strides_bad(h, d->row_pitch_floats, d->plane_stride_floats, d->flow_stride_floats))
         return dfx_fail(h, DFX_ERR_INVALID, kPlanarStrides);
     if (planar_strides_bad(h, d->out_row_pitch_floats, d->out_plane_stride_floats, d->out_flow_stride_floats))
-        return dfx_fail(h, DFX_ERR_INVALID, "output flows: out_row_pitch_floats >= W, out_plane_stride_floats >= H * out_row_pitch_floats "
-                                            "and out_flow_stride_floats >= 2 * out_plane_stride_floats are required");
-    if (d->d_mask && fb_occ_bad(h, d->mask_pitch, d->mask_stride))
-        return dfx_fail(h, DFX_ERR_INVALID, "mask planes: mask_pitch >= W and mask_stride >= H * mask_pitch are required");
-    if (d->d_mask_out && fb_occ_bad(h, d->mask_out_pitch, d->mask_out_stride))
-        return dfx_fail(h, DFX_ERR_INVALID, "output mask planes: mask_out_pitch >= W and mask_out_stride >= H * mask_out_pitch are required");
+        return dfx_fail(h, DFX_ERR_INVALID, kPlanarStridesOut);
+    if (int e = plane_check(h, d->d_mask != nullptr, d->mask_pitch, d->mask_stride, "mask", "mask"))
+        return e;
+    if (int e = plane_check(h, d->d_mask_out != nullptr, d->mask_out_pitch, d->mask_out_stride, "output mask", "mask_out"))
+        return e;
     HIPCHK(h, hipSetDevice(h->device));
     FmArgs a{};
     a.flow = d->d_flow, a.mask = d->d_mask, a.out = d->d_out, a.mask_out = d->d_mask_out;
@@ -789,13 +790,12 @@ int dfx_flow_median_device(dfx_handle h, const dfx_median_desc *d) {
     a.out_stride = (long long)d->out_flow_stride_floats;
     a.mask_out_pitch = (long long)d->mask_out_pitch, a.mask_out_stride = (long long)d->mask_out_stride;
     fm_launch(h->stream, a);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return DFX_OK;
+    return post_finish(h);
 }
 
 // ---- adjacent flows chained into long-range flows and dense trajectories (flow_chain_kernels.hip) ----
 int dfx_flow_chain_device(dfx_handle h, const dfx_chain_desc *d) {
+    // post_begin's checks by hand: anchors < 0 is refused between n < 0 and the empty batch
     if (!h)
         return DFX_ERR_INVALID;
     (void)dfx_finish_tails(h, 0, -1);
@@ -829,12 +829,11 @@ int dfx_flow_chain_device(dfx_handle h, const dfx_chain_desc *d) {
     if (planar_strides_bad(h, d->row_pitch_floats, d->plane_stride_floats, d->flow_stride_floats))
         return dfx_fail(h, DFX_ERR_INVALID, kPlanarStrides);
     if (planar_strides_bad(h, d->out_row_pitch_floats, d->out_plane_stride_floats, d->out_flow_stride_floats))
-        return dfx_fail(h, DFX_ERR_INVALID, "output flows: out_row_pitch_floats >= W, out_plane_stride_floats >= H * out_row_pitch_floats "
-                                            "and out_flow_stride_floats >= 2 * out_plane_stride_floats are required");
-    if (d->d_occ && fb_occ_bad(h, d->occ_pitch, d->occ_stride))
-        return dfx_fail(h, DFX_ERR_INVALID, kFbOcc);
-    if (d->d_valid && fb_occ_bad(h, d->valid_pitch, d->valid_stride))
-        return dfx_fail(h, DFX_ERR_INVALID, "valid planes: valid_pitch >= W and valid_stride >= H * valid_pitch are required");
+        return dfx_fail(h, DFX_ERR_INVALID, kPlanarStridesOut);
+    if (int e = plane_check(h, d->d_occ != nullptr, d->occ_pitch, d->occ_stride, "mask", "occ"))
+        return e;
+    if (int e = plane_check(h, d->d_valid != nullptr, d->valid_pitch, d->valid_stride, "valid", "valid"))
+        return e;
     HIPCHK(h, hipSetDevice(h->device));
     FcArgs a{};
     a.flow = d->d_flow, a.occ = d->d_occ, a.out = d->d_out, a.valid = d->d_valid;
@@ -848,9 +847,7 @@ int dfx_flow_chain_device(dfx_handle h, const dfx_chain_desc *d) {
     a.out_stride = (long long)d->out_flow_stride_floats;
     a.valid_pitch = (long long)d->valid_pitch, a.valid_stride = (long long)d->valid_stride;
     fc_launch(h->stream, a);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return DFX_OK;
+    return post_finish(h);
 }
 
 // ---- forward projection of flows: inverse and time-t flows, holes marked (flow_project_kernels.hip) ----
@@ -861,17 +858,9 @@ size_t dfx_flow_project_work_bytes(dfx_handle h) {
 }
 
 int dfx_flow_project_device(dfx_handle h, const dfx_project_desc *d) {
-    if (!h)
-        return DFX_ERR_INVALID;
-    (void)dfx_finish_tails(h, 0, -1);
-    if (h->algo == DFX_ALGO_FRAMES)
-        return dfx_fail(h, DFX_ERR_UNSUPPORTED, "a DFX_ALGO_FRAMES handle computes no flow");
-    if (!d)
-        return dfx_fail(h, DFX_ERR_INVALID, "NULL descriptor");
-    if (d->n < 0)
-        return dfx_fail(h, DFX_ERR_INVALID, "n must be >= 0");
-    if (d->n == 0)
-        return DFX_OK;
+    int st;
+    if (!post_begin(h, d, &st))
+        return st;
     if (!d->d_flow || !d->d_work)
         return dfx_fail(h, DFX_ERR_INVALID, "NULL device flows or workspace");
     if (!d->d_out && !d->d_hole && !d->d_coverage)
@@ -891,19 +880,18 @@ int dfx_flow_project_device(dfx_handle h, const dfx_project_desc *d) {
         return dfx_fail(h, DFX_ERR_INVALID, "work_bytes must be at least dfx_flow_project_work_bytes");
     if (planar_strides_bad(h, d->row_pitch_floats, d->plane_stride_floats, d->flow_stride_floats))
         return dfx_fail(h, DFX_ERR_INVALID, kPlanarStrides);
-    if (d->d_importance && fb_occ_bad(h, d->importance_pitch_floats, d->importance_stride_floats))
-        return dfx_fail(h, DFX_ERR_INVALID, "importance planes: importance_pitch_floats >= W and importance_stride_floats >= H * "
-                                            "importance_pitch_floats are required");
-    if (d->d_occ && fb_occ_bad(h, d->occ_pitch, d->occ_stride))
-        return dfx_fail(h, DFX_ERR_INVALID, kFbOcc);
+    if (int e = plane_check(h, d->d_importance != nullptr, d->importance_pitch_floats, d->importance_stride_floats, "importance",
+                            "importance", "_floats"))
+        return e;
+    if (int e = plane_check(h, d->d_occ != nullptr, d->occ_pitch, d->occ_stride, "mask", "occ"))
+        return e;
     if (d->d_out && planar_strides_bad(h, d->out_row_pitch_floats, d->out_plane_stride_floats, d->out_flow_stride_floats))
-        return dfx_fail(h, DFX_ERR_INVALID, "output flows: out_row_pitch_floats >= W, out_plane_stride_floats >= H * out_row_pitch_floats "
-                                            "and out_flow_stride_floats >= 2 * out_plane_stride_floats are required");
-    if (d->d_hole && fb_occ_bad(h, d->hole_pitch, d->hole_stride))
-        return dfx_fail(h, DFX_ERR_INVALID, "hole planes: hole_pitch >= W and hole_stride >= H * hole_pitch are required");
-    if (d->d_coverage && fb_occ_bad(h, d->coverage_pitch_floats, d->coverage_stride_floats))
-        return dfx_fail(h, DFX_ERR_INVALID, "coverage planes: coverage_pitch_floats >= W and coverage_stride_floats >= H * "
-                                            "coverage_pitch_floats are required");
+        return dfx_fail(h, DFX_ERR_INVALID, kPlanarStridesOut);
+    if (int e = plane_check(h, d->d_hole != nullptr, d->hole_pitch, d->hole_stride, "hole", "hole"))
+        return e;
+    if (int e = plane_check(h, d->d_coverage != nullptr, d->coverage_pitch_floats, d->coverage_stride_floats, "coverage", "coverage",
+                            "_floats"))
+        return e;
     HIPCHK(h, hipSetDevice(h->device));
     FpArgs a{};
     a.flow = d->d_flow, a.imp = d->d_importance, a.occ = d->d_occ;
@@ -922,9 +910,7 @@ int dfx_flow_project_device(dfx_handle h, const dfx_project_desc *d) {
     a.hole_pitch = (long long)d->hole_pitch, a.hole_stride = (long long)d->hole_stride;
     a.cov_pitch = (long long)d->coverage_pitch_floats, a.cov_stride = (long long)d->coverage_stride_floats;
     fp_launch(h->stream, a, (long long)(d->work_bytes / per_flow));
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return DFX_OK;
+    return post_finish(h);
 }
 
 // ---- frame interpolation at time t from two frames and their flows (interpolate_kernels.hip) ----
@@ -935,17 +921,9 @@ size_t dfx_interpolate_work_bytes(dfx_handle h, const dfx_interp_desc *d) {
 }
 
 int dfx_interpolate_device(dfx_handle h, const dfx_interp_desc *d) {
-    if (!h)
-        return DFX_ERR_INVALID;
-    (void)dfx_finish_tails(h, 0, -1);
-    if (h->algo == DFX_ALGO_FRAMES)
-        return dfx_fail(h, DFX_ERR_UNSUPPORTED, "a DFX_ALGO_FRAMES handle computes no flow");
-    if (!d)
-        return dfx_fail(h, DFX_ERR_INVALID, "NULL descriptor");
-    if (d->n < 0)
-        return dfx_fail(h, DFX_ERR_INVALID, "n must be >= 0");
-    if (d->n == 0)
-        return DFX_OK;
+    int st;
+    if (!post_begin(h, d, &st))
+        return st;
     if (!d->d_img0 || !d->d_img1 || !d->d_fwd || !d->d_work)
         return dfx_fail(h, DFX_ERR_INVALID, "NULL device images, forward flows or workspace");
     if (!d->d_out && !d->d_source)
@@ -975,12 +953,12 @@ int dfx_interpolate_device(dfx_handle h, const dfx_interp_desc *d) {
         return dfx_fail(h, DFX_ERR_INVALID, "images: a pitch or stride smaller than what it spans");
     if (planar_strides_bad(h, d->row_pitch_floats, d->plane_stride_floats, d->flow_stride_floats))
         return dfx_fail(h, DFX_ERR_INVALID, kPlanarStrides);
-    if ((d->d_occ_fwd || d->d_occ_bwd) && fb_occ_bad(h, d->occ_pitch, d->occ_stride))
-        return dfx_fail(h, DFX_ERR_INVALID, kFbOcc);
+    if (int e = plane_check(h, d->d_occ_fwd || d->d_occ_bwd, d->occ_pitch, d->occ_stride, "mask", "occ"))
+        return e;
     if (d->d_out && warp_image_strides_bad(h, il3, planes, d->out_pitch, d->out_plane_stride, d->out_image_stride))
         return dfx_fail(h, DFX_ERR_INVALID, "interpolated images: a pitch or stride smaller than what it spans");
-    if (d->d_source && fb_occ_bad(h, d->source_pitch, d->source_stride))
-        return dfx_fail(h, DFX_ERR_INVALID, "source planes: source_pitch >= W and source_stride >= H * source_pitch are required");
+    if (int e = plane_check(h, d->d_source != nullptr, d->source_pitch, d->source_stride, "source", "source"))
+        return e;
     HIPCHK(h, hipSetDevice(h->device));
     InterpArgs a{};
     a.img0 = d->d_img0, a.img1 = d->d_img1, a.fwd = d->d_fwd, a.bwd = d->d_bwd;
@@ -998,24 +976,14 @@ int dfx_interpolate_device(dfx_handle h, const dfx_interp_desc *d) {
     a.out_image = (long long)d->out_image_stride;
     a.source_pitch = (long long)d->source_pitch, a.source_stride = (long long)d->source_stride;
     interp_launch(h->stream, a);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return DFX_OK;
+    return post_finish(h);
 }
 
 // ---- flows as colour images: the Middlebury wheel, unknown pixels marked (flow_colour_kernels.hip) ----
 int dfx_flow_colour_device(dfx_handle h, const dfx_colour_desc *d) {
-    if (!h)
-        return DFX_ERR_INVALID;
-    (void)dfx_finish_tails(h, 0, -1);
-    if (h->algo == DFX_ALGO_FRAMES)
-        return dfx_fail(h, DFX_ERR_UNSUPPORTED, "a DFX_ALGO_FRAMES handle computes no flow");
-    if (!d)
-        return dfx_fail(h, DFX_ERR_INVALID, "NULL descriptor");
-    if (d->n < 0)
-        return dfx_fail(h, DFX_ERR_INVALID, "n must be >= 0");
-    if (d->n == 0)
-        return DFX_OK;
+    int st;
+    if (!post_begin(h, d, &st))
+        return st;
     if (!d->d_flow || !d->d_out)
         return dfx_fail(h, DFX_ERR_INVALID, "NULL device flows or colour images");
     if (d->norm != DFX_COLOUR_NORM_FIXED && d->norm != DFX_COLOUR_NORM_FLOW && d->norm != DFX_COLOUR_NORM_BATCH)
@@ -1030,8 +998,8 @@ int dfx_flow_colour_device(dfx_handle h, const dfx_colour_desc *d) {
         return dfx_fail(h, DFX_ERR_INVALID, "layout must be DFX_SRC_INTERLEAVED or DFX_SRC_PLANAR");
     if (planar_strides_bad(h, d->row_pitch_floats, d->plane_stride_floats, d->flow_stride_floats))
         return dfx_fail(h, DFX_ERR_INVALID, kPlanarStrides);
-    if (d->d_mask && fb_occ_bad(h, d->mask_pitch, d->mask_stride))
-        return dfx_fail(h, DFX_ERR_INVALID, "mask planes: mask_pitch >= W and mask_stride >= H * mask_pitch are required");
+    if (int e = plane_check(h, d->d_mask != nullptr, d->mask_pitch, d->mask_stride, "mask", "mask"))
+        return e;
     const bool planes = d->layout == DFX_SRC_PLANAR;
     if (warp_image_strides_bad(h, !planes, planes, d->out_pitch, d->out_plane_stride, d->out_image_stride))
         return dfx_fail(h, DFX_ERR_INVALID, "colour images: a pitch or stride smaller than what it spans");
@@ -1066,9 +1034,7 @@ int dfx_flow_colour_device(dfx_handle h, const dfx_colour_desc *d) {
         a.frame_image = (long long)d->frame_image_stride;
     }
     flowvis_launch(h->stream, a);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return DFX_OK;
+    return post_finish(h);
 }
 
 // ---- caller-supplied initial flows (TVL1's useInitialFlow, Farneback's OPTFLOW_USE_INITIAL_FLOW) ----

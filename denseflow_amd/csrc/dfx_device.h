@@ -112,6 +112,11 @@ static inline int dfx_planar_vec(const void *base, long long flow_stride, long l
                                     ((unsigned long long)plane_stride * e) | ((unsigned long long)row_pitch * e);
     return (bits & (4 * e - 1)) == 0 ? 4 : (bits & (2 * e - 1)) == 0 ? 2 : 1;
 }
+// byte planes (masks, 8-bit images): whether a lane's 4 bytes go in one access — the plane is there, and its base and every
+// stride (in bytes; a stride the layout does not have is 0) are multiples of 4
+static inline bool dfx_bytes4(const void *base, long long s0, long long s1 = 0, long long s2 = 0) {
+    return base && (((unsigned long long)(size_t)base | (unsigned long long)s0 | (unsigned long long)s1 | (unsigned long long)s2) & 3) == 0;
+}
 
 // ------------------------------------------------------------------------------------------------
 // Caller-supplied initial flows (dfx_calc_batch_init*): one W x H field per pair of a launch, raw pixels, in the caller's

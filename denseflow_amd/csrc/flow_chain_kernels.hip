@@ -228,10 +228,6 @@ void fc_launch_as(hipStream_t s, const FcArgs &a, const FcWide &wide) {
                        dim3(256), 0, s, a, wide);
 }
 
-inline bool fc_bytes4(const void *base, long long s0, long long s1) {
-    return base && (((unsigned long long)(size_t)base | (unsigned long long)s0 | (unsigned long long)s1) & 3) == 0;
-}
-
 } // namespace
 
 void fc_launch(hipStream_t s, const FcArgs &args) {
@@ -241,9 +237,9 @@ void fc_launch(hipStream_t s, const FcArgs &args) {
     // a lane's 4 elements in one access: the base and every stride a multiple of that access
     FcWide wide;
     wide.flow = dfx_planar_vec(args.flow, args.flow_stride, args.plane_stride, args.row_pitch) == 4;
-    wide.occ = fc_bytes4(args.occ, args.occ_pitch, args.occ_stride);
+    wide.occ = dfx_bytes4(args.occ, args.occ_pitch, args.occ_stride);
     wide.out = dfx_planar_vec(args.out, args.out_stride, args.out_plane, args.out_pitch) == 4;
-    wide.valid = fc_bytes4(args.valid, args.valid_pitch, args.valid_stride);
+    wide.valid = dfx_bytes4(args.valid, args.valid_pitch, args.valid_stride);
     wide.pair = FC_PAIR_TAPS && args.w >= 2;
     // grid.z holds at most 65535 anchors: more than that go in several launches
     const int chunk = 65535;

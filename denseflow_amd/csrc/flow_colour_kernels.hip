@@ -300,10 +300,6 @@ void flowvis_colour_as(hipStream_t s, const dim3 &grid, const FlowvisArgs &a, co
         hipLaunchKernelGGL((k_flowvis_colour<MASKED, IL, false>), grid, dim3(256), 0, s, a, wide);
 }
 
-inline bool fv_bytes4(const void *base, long long s0, long long s1, long long s2) {
-    return base && (((unsigned long long)(size_t)base | (unsigned long long)s0 | (unsigned long long)s1 | (unsigned long long)s2) & 3) == 0;
-}
-
 } // namespace
 
 void flowvis_launch(hipStream_t s, const FlowvisArgs &args) {
@@ -312,10 +308,10 @@ void flowvis_launch(hipStream_t s, const FlowvisArgs &args) {
     // a lane's 4 elements in one access: the base and every stride a multiple of that access
     FlowvisWide wide;
     wide.flow = dfx_planar_vec(args.flow, args.flow_stride, args.plane_stride, args.row_pitch) == 4;
-    wide.mask = fv_bytes4(args.mask, args.mask_pitch, args.mask_stride, 0);
-    wide.out = fv_bytes4(args.out, args.out_pitch, args.out_image, args.planar ? args.out_plane : 0);
-    wide.frame = fv_bytes4(args.frame, args.frame_pitch, args.frame_image,
-                           args.frame_channels == 3 && args.frame_planar ? args.frame_plane : 0);
+    wide.mask = dfx_bytes4(args.mask, args.mask_pitch, args.mask_stride, 0);
+    wide.out = dfx_bytes4(args.out, args.out_pitch, args.out_image, args.planar ? args.out_plane : 0);
+    wide.frame = dfx_bytes4(args.frame, args.frame_pitch, args.frame_image,
+                            args.frame_channels == 3 && args.frame_planar ? args.frame_plane : 0);
     if (args.max2)
         (void)hipMemsetAsync(args.max2, 0, ((size_t)args.n + 1) * sizeof(float), s);
     // grid.z holds at most 65535 flows: more than that go in several launches, every measuring launch before the first colour launch

@@ -277,10 +277,6 @@ __global__ __launch_bounds__(256, K == 3 ? 8 : (MASKED ? 5 : 6)) void k_flow_med
     }
 }
 
-inline bool fm_bytes4(const void *base, long long s0, long long s1) {
-    return base && (((unsigned long long)(size_t)base | (unsigned long long)s0 | (unsigned long long)s1) & 3) == 0;
-}
-
 template <int K>
 void fm_launch_k(hipStream_t s, const FmArgs &a, const FmWide &wide, dim3 grid) {
     if (!a.mask)
@@ -298,9 +294,9 @@ void fm_launch(hipStream_t s, const FmArgs &args) {
         return;
     FmWide wide;
     wide.flow = dfx_planar_vec(args.flow, args.flow_stride, args.plane_stride, args.row_pitch) == 4;
-    wide.mask = fm_bytes4(args.mask, args.mask_pitch, args.mask_stride);
+    wide.mask = dfx_bytes4(args.mask, args.mask_pitch, args.mask_stride);
     wide.out = dfx_planar_vec(args.out, args.out_stride, args.out_plane, args.out_pitch) == 4;
-    wide.mask_out = fm_bytes4(args.mask_out, args.mask_out_pitch, args.mask_out_stride);
+    wide.mask_out = dfx_bytes4(args.mask_out, args.mask_out_pitch, args.mask_out_stride);
     // grid.z holds at most 65535 flows: more than that go in several launches
     const int chunk = 65535;
     for (int i0 = 0; i0 < args.n; i0 += chunk) {

@@ -308,10 +308,6 @@ void gm_round(hipStream_t s, const GmArgs &a, const GmWide &wide, dim3 grid, int
         hipLaunchKernelGGL((k_gm_accumulate<MODEL, false>), grid, dim3(256), 0, s, a, wide, round, tt);
 }
 
-inline bool gm_bytes4(const void *base, long long s0, long long s1) {
-    return base && (((unsigned long long)(size_t)base | (unsigned long long)s0 | (unsigned long long)s1) & 3) == 0;
-}
-
 } // namespace
 
 void gm_launch(hipStream_t s, const GmArgs &args) {
@@ -319,9 +315,9 @@ void gm_launch(hipStream_t s, const GmArgs &args) {
         return;
     GmWide wide;
     wide.flow = dfx_planar_vec(args.flow, args.flow_stride, args.plane_stride, args.row_pitch) == 4;
-    wide.mask = gm_bytes4(args.mask, args.mask_pitch, args.mask_stride);
+    wide.mask = dfx_bytes4(args.mask, args.mask_pitch, args.mask_stride);
     wide.out = args.out && dfx_planar_vec(args.out, args.out_stride, args.out_plane, args.out_pitch) == 4;
-    wide.moving = gm_bytes4(args.moving, args.moving_pitch, args.moving_stride);
+    wide.moving = dfx_bytes4(args.moving, args.moving_pitch, args.moving_stride);
     (void)hipMemsetAsync(args.result, 0, (size_t)args.n * sizeof(dfx_gm_result), s);
     // t_k = thr multiplied rounds - 1 - k times by growth, in float32
     float tt[GM_MAX_ROUNDS];

@@ -269,10 +269,6 @@ void warp_launch_as(hipStream_t s, const WarpArgs &a, const WarpWide &wide) {
         hipLaunchKernelGGL((k_warp<C, IL, false>), dim3(gx, (unsigned)((a.h + 3) / 4), (unsigned)a.n), dim3(256), 0, s, a, wide);
 }
 
-inline bool warp_bytes4(const void *base, long long s0, long long s1, long long s2) {
-    return base && (((unsigned long long)(size_t)base | (unsigned long long)s0 | (unsigned long long)s1 | (unsigned long long)s2) & 3) == 0;
-}
-
 } // namespace
 
 void warp_launch(hipStream_t s, const WarpArgs &args) {
@@ -283,10 +279,10 @@ void warp_launch(hipStream_t s, const WarpArgs &args) {
     // a lane's 4 elements in one access: the base and every stride a multiple of that access
     WarpWide wide;
     wide.flow = dfx_planar_vec(args.flow, args.flow_stride, args.plane_stride, args.row_pitch) == 4;
-    wide.ref = warp_bytes4(args.ref, args.src_pitch, args.src_image, planes ? args.src_plane : 0);
+    wide.ref = dfx_bytes4(args.ref, args.src_pitch, args.src_image, planes ? args.src_plane : 0);
     wide.out = args.out && dfx_planar_vec(args.out, args.out_image, planes ? args.out_plane : 0, args.out_pitch, eb) == 4;
-    wide.occ = warp_bytes4(args.occ, args.occ_pitch, args.occ_stride, 0);
-    wide.valid = warp_bytes4(args.valid, args.valid_pitch, args.valid_stride, 0);
+    wide.occ = dfx_bytes4(args.occ, args.occ_pitch, args.occ_stride, 0);
+    wide.valid = dfx_bytes4(args.valid, args.valid_pitch, args.valid_stride, 0);
     if (args.stats)
         (void)hipMemsetAsync(args.stats, 0, (size_t)args.n * 2 * sizeof(unsigned long long), s);
     // grid.z holds at most 65535 images: more than that go in several launches

@@ -7,6 +7,7 @@ one at src/denseflow_gpu.cpp:307-342).  Errors carry the reference's message tex
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 import subprocess
@@ -809,6 +810,57 @@ def _warp_dtype(dtype):
         raise ValueError('dtype must be np.uint8, np.float32, np.float16 or "bfloat16"') from None
 
 
+# -- what the calls on finished flows (fb_check .. flow_colour) share: how flows and per-item planes lie in memory.  A
+# dimension of extent 1 takes its stride from the dense layout, not from the tensor (torch leaves such a stride arbitrary).
+def _flow_geometry(t, H, W, what, lead="M", n=None, tail=""):
+    """(row pitch, plane stride, flow stride), in floats, of a torch.float32 tensor of flows (lead, 2, H, W), read from its
+    strides; with n, there must be exactly n flows.  `lead` and `tail` only word the refusal."""
+    import torch
+
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 4 or tuple(t.shape[1:]) != (2, H, W) or \
+            (n is not None and t.shape[0] != n):
+        raise ValueError(f"{what} must be an ({lead}, 2, H, W) torch.float32 tensor{tail}")
+    st = t.stride()
+    pitch = st[2] if H > 1 else W
+    plane, flow = st[1], (st[0] if t.shape[0] > 1 else 2 * st[1])
+    if (st[3] != 1 and W > 1) or pitch < W or plane < H * pitch or flow < 2 * plane:
+        raise ValueError(f"{what}: the innermost dimension must be contiguous and rows, planes and flows must not overlap")
+    return pitch, plane, flow
+
+
+def _plane_geometry(t, n, H, W, dtype, what, lead="M", noun="masks"):
+    """(row pitch, stride), in elements, of a torch tensor of n planes (n, H, W) of that dtype — masks, weights — read from
+    its strides.  `lead` and `noun` only word the refusals."""
+    import torch
+
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != (n, H, W):
+        raise ValueError(f"{what} must be an ({lead}, H, W) {dtype} tensor")
+    st = t.stride()
+    pitch = st[1] if H > 1 else W
+    stride = st[0] if n > 1 else H * pitch
+    if (st[2] != 1 and W > 1) or pitch < W or stride < H * pitch:
+        raise ValueError(f"{what}: the innermost dimension must be contiguous and rows and {noun} must not overlap")
+    return pitch, stride
+
+
+def _np_flows(a, H, W, what="flows", lead="M", n=None, tail=""):
+    """Flows given to a numpy wrapper as a contiguous (lead, 2, H, W) float32 array; with n, exactly n flows."""
+    a = np.asarray(a)
+    if a.dtype != np.float32 or a.ndim != 4 or a.shape[1:] != (2, H, W) or (n is not None and a.shape[0] != n):
+        raise ValueError(f"{what} must be ({lead}, 2, H, W) float32{tail}")
+    return np.ascontiguousarray(a)
+
+
+def _np_planes(a, n, H, W, dtype, what, lead="M"):
+    """An optional (n, H, W) array of that dtype given to a numpy wrapper, contiguous; None stays None."""
+    if a is None:
+        return None
+    a = np.asarray(a)
+    if a.dtype != dtype or a.shape != (n, H, W):
+        raise ValueError(f"{what} must be ({lead}, H, W) {np.dtype(dtype).name}")
+    return np.ascontiguousarray(a)
+
+
 def _source_codes(channels, order, layout):
     if order not in SRC_ORDERS:
         raise ValueError('order must be "bgr" or "rgb"')
@@ -1233,8 +1285,7 @@ class FlowEngine:
             out_plane_stride, flow_stride = so[1], (so[0] if m > 1 else 2 * so[1])
             if so[3] != 1 or row_pitch < self.width or out_plane_stride < self.height * row_pitch or flow_stride < 2 * out_plane_stride:
                 raise ValueError("out: the innermost dimension must be contiguous and rows, planes and flows must not overlap")
-        if dev.type != "cuda" or (dev.index is not None and dev.index != getattr(self, "_device", dev.index)):
-            raise ValueError("frames must be on this handle's device")
+        self._check_devices(frames, "frames must be on this handle's device")
         if init is not None:
             if not isinstance(init, torch.Tensor) or init.dtype != torch.float32 or init.device != dev:
                 raise ValueError("init must be a torch.float32 tensor on the frames' device")
@@ -1342,6 +1393,35 @@ class FlowEngine:
         for p in ptrs:
             self._L.dfx_device_free(self._h, p)
 
+    @contextlib.contextmanager
+    def _staged(self, ins, outs, scratch=()):
+        """The device side of a numpy wrapper's call: buffers for the arrays `ins` and `outs` (None entries allowed) and for
+        the `scratch` byte sizes, the inputs uploaded; yields the device pointers in that order, None for an absent array;
+        on a clean exit the outputs are downloaded; the buffers are freed either way."""
+        arrays = list(ins) + list(outs)
+        bufs = self._dev_bufs([x.nbytes for x in arrays if x is not None] + list(scratch))
+        try:
+            free = iter(bufs)
+            ptrs = [None if x is None else next(free) for x in arrays]
+            for p, x in zip(ptrs, ins):
+                if x is not None:
+                    self._check(self._L.dfx_memcpy_h2d(self._h, p, x.ctypes.data, x.nbytes))
+            yield ptrs + list(free)
+            for p, x in zip(ptrs[len(ins):], outs):
+                if x is not None:
+                    self._check(self._L.dfx_memcpy_d2h(self._h, x.ctypes.data, p, x.nbytes))
+        finally:
+            self._dev_free(bufs)
+
+    def _check_devices(self, first, first_msg, others=(), others_msg=""):
+        """ValueError(first_msg) unless the torch tensor `first` is on this handle's device, ValueError(others_msg) unless
+        the `others` (None entries allowed) are on first's."""
+        dev = first.device
+        if dev.type != "cuda" or (dev.index is not None and dev.index != getattr(self, "_device", dev.index)):
+            raise ValueError(first_msg)
+        if any(t is not None and t.device != dev for t in others):
+            raise ValueError(others_msg)
+
     def calc_optflows_bidir(self, frames_gray, step: int, check: bool = True, alpha1: float = 0.01, alpha2: float = 0.5):
         """Both directions of every pair of a FlowBuffer, every frame uploaded and built once: (fwd, bwd, occ_fwd, occ_bwd),
         two (M, 2, H, W) float32 arrays — fwd what calc_optflows_planar gives for `step`, bwd what it gives for -step — and
@@ -1390,17 +1470,8 @@ class FlowEngine:
         occ = np.empty((n, H, W), np.uint8)
         err = np.empty((n, H, W), np.float32) if want_err else None
         if n:
-            bufs = self._dev_bufs([fwd.nbytes, bwd.nbytes, occ.nbytes] + ([err.nbytes] if want_err else []))
-            try:
-                self._check(self._L.dfx_memcpy_h2d(self._h, bufs[0], fwd.ctypes.data, fwd.nbytes))
-                self._check(self._L.dfx_memcpy_h2d(self._h, bufs[1], bwd.ctypes.data, bwd.nbytes))
-                self.fb_check_device(bufs[0], bufs[1], W, H * W, 2 * H * W, n, alpha1, alpha2, bufs[2], W, H * W,
-                                     bufs[3] if want_err else None, W, H * W)
-                self._check(self._L.dfx_memcpy_d2h(self._h, occ.ctypes.data, bufs[2], occ.nbytes))
-                if want_err:
-                    self._check(self._L.dfx_memcpy_d2h(self._h, err.ctypes.data, bufs[3], err.nbytes))
-            finally:
-                self._dev_free(bufs)
+            with self._staged((fwd, bwd), (occ, err)) as (d_fwd, d_bwd, d_occ, d_err):
+                self.fb_check_device(d_fwd, d_bwd, W, H * W, 2 * H * W, n, alpha1, alpha2, d_occ, W, H * W, d_err, W, H * W)
         return (occ, err) if want_err else occ
 
     # -- the backward warp of 8-bit images by a flow, its valid mask and photometric statistics (dfx_warp_device) ----
@@ -1433,10 +1504,7 @@ class FlowEngine:
         raise ValueError(f"{what} must be (n, H, W), (n, H, W, 3) or, with layout=\"chw\", (n, 3, H, W)")
 
     def _warp_flows(self, flows, n):
-        f = np.asarray(flows)
-        if f.dtype != np.float32 or f.shape != (n, 2, self.height, self.width):
-            raise ValueError("flows must be (n, 2, H, W) float32, one flow per image")
-        return np.ascontiguousarray(f)
+        return _np_flows(flows, self.height, self.width, lead="n", n=n, tail=", one flow per image")
 
     def warp(self, images, flows, border: str = "zero", dtype=np.uint8, layout: str = "hwc", ref=None, occ=None,
              want_valid: bool = False, want_stats: bool = False):
@@ -1461,11 +1529,7 @@ class FlowEngine:
             ref, _ = self._warp_images(ref, l, "ref")
             if ref.shape != img.shape:
                 raise ValueError("ref must have the shape of images")
-        if occ is not None:
-            occ = np.asarray(occ)
-            if occ.dtype != np.uint8 or occ.shape != (n, H, W):
-                raise ValueError("occ must be (n, H, W) uint8")
-            occ = np.ascontiguousarray(occ)
+        occ = _np_planes(occ, n, H, W, np.uint8, "occ", "n")
         out = np.empty(img.shape, np_dt)
         valid = np.empty((n, H, W), np.uint8) if want_valid else None
         stats = np.zeros((n, 2), np.uint64) if want_stats else None
@@ -1474,20 +1538,9 @@ class FlowEngine:
             pitch = W * (1 if ch == 1 or planes else 3)
             plane = H * W if planes else 0
             image = ch * H * W
-            ins = [img, fl] + [x for x in (ref, occ) if x is not None]
-            outs = [out] + [x for x in (valid, stats) if x is not None]
-            bufs = self._dev_bufs([x.nbytes for x in ins + outs])
-            try:
-                for p, x in zip(bufs, ins):
-                    self._check(self._L.dfx_memcpy_h2d(self._h, p, x.ctypes.data, x.nbytes))
-                at = {id(x): p for p, x in zip(bufs, ins + outs)}
-                ptr = lambda x: None if x is None else at[id(x)]  # noqa: E731
-                self.warp_device(ptr(img), ch, l if ch == 3 else 0, pitch, plane, image, ptr(fl), W, H * W, 2 * H * W, n, b, code,
-                                 ptr(out), pitch, plane, image, ptr(ref), ptr(occ), W, H * W, ptr(valid), W, H * W, ptr(stats))
-                for x in outs:
-                    self._check(self._L.dfx_memcpy_d2h(self._h, x.ctypes.data, at[id(x)], x.nbytes))
-            finally:
-                self._dev_free(bufs)
+            with self._staged((img, fl, ref, occ), (out, valid, stats)) as (d_img, d_fl, d_ref, d_occ, d_out, d_valid, d_stats):
+                self.warp_device(d_img, ch, l if ch == 3 else 0, pitch, plane, image, d_fl, W, H * W, 2 * H * W, n, b, code,
+                                 d_out, pitch, plane, image, d_ref, d_occ, W, H * W, d_valid, W, H * W, d_stats)
         res = (out,) + ((valid,) if want_valid else ()) + ((stats,) if want_stats else ())
         return res if len(res) > 1 else out
 
@@ -1509,27 +1562,15 @@ class FlowEngine:
         ch = 1 if fr.ndim == 3 else 3
         m = max(fr.shape[0] - abs(step), 0)
         fl = self._warp_flows(flows, m)
-        if occ is not None:
-            occ = np.asarray(occ)
-            if occ.dtype != np.uint8 or occ.shape != (m, H, W):
-                raise ValueError("occ must be (M, H, W) uint8")
-            occ = np.ascontiguousarray(occ)
+        occ = _np_planes(occ, m, H, W, np.uint8, "occ")
         stats = np.zeros((m, 2), np.uint64)
         if m:
             fb = ch * H * W
-            bufs = self._dev_bufs([fr.nbytes, fl.nbytes, stats.nbytes] + ([occ.nbytes] if occ is not None else []))
-            try:
-                self._check(self._L.dfx_memcpy_h2d(self._h, bufs[0], fr.ctypes.data, fr.nbytes))
-                self._check(self._L.dfx_memcpy_h2d(self._h, bufs[1], fl.ctypes.data, fl.nbytes))
-                if occ is not None:
-                    self._check(self._L.dfx_memcpy_h2d(self._h, bufs[3], occ.ctypes.data, occ.nbytes))
+            with self._staged((fr, fl, occ), (stats,)) as (d_fr, d_fl, d_occ, d_stats):
                 first_a, first_b = (0, step) if step > 0 else (-step, 0)  # flow 0 is frame first_a -> frame first_b
-                self.warp_device(bufs[0].value + first_b * fb, ch, 0, W * ch, 0, fb, bufs[1], W, H * W, 2 * H * W, m,
-                                 d_ref_ptr=bufs[0].value + first_a * fb, d_occ_ptr=bufs[3] if occ is not None else None,
-                                 occ_pitch=W, occ_stride=H * W, d_stats_ptr=bufs[2])
-                self._check(self._L.dfx_memcpy_d2h(self._h, stats.ctypes.data, bufs[2], stats.nbytes))
-            finally:
-                self._dev_free(bufs)
+                self.warp_device(d_fr.value + first_b * fb, ch, 0, W * ch, 0, fb, d_fl, W, H * W, 2 * H * W, m,
+                                 d_ref_ptr=d_fr.value + first_a * fb, d_occ_ptr=d_occ, occ_pitch=W, occ_stride=H * W,
+                                 d_stats_ptr=d_stats)
         cnt, sad = stats[:, 0].astype(np.float64), stats[:, 1].astype(np.float64)
         with np.errstate(divide="ignore", invalid="ignore"):
             return np.where(cnt > 0, sad / (cnt * ch), np.nan)
@@ -1543,10 +1584,7 @@ class FlowEngine:
         n = t.shape[0] if t.dim() else 0
         st = t.stride()
         if t.dim() == 3 and tuple(t.shape[1:]) == (H, W):
-            pitch = st[1] if H > 1 else W
-            image = st[0] if n > 1 else H * pitch
-            if (st[2] != 1 and W > 1) or pitch < W or image < H * pitch:
-                raise ValueError(f"{what}: the innermost dimension must be contiguous and rows and images must not overlap")
+            pitch, image = _plane_geometry(t, n, H, W, t.dtype, what, noun="images")
             return 1, 0, pitch, 0, image, False
         chw, hwc = tuple(t.shape[1:]) == (3, H, W), tuple(t.shape[1:]) == (H, W, 3)
         if t.dim() != 4 or not (chw or hwc):
@@ -1602,13 +1640,7 @@ class FlowEngine:
         ch, mem, pitch, plane, image, chw = self._warp_tensor_images(images, layout, "images")
         n = images.shape[0]
         dev = images.device
-        if not isinstance(flows, torch.Tensor) or flows.dtype != torch.float32 or tuple(flows.shape) != (n, 2, H, W):
-            raise ValueError("flows must be an (n, 2, H, W) torch.float32 tensor, one flow per image")
-        sf = flows.stride()
-        row_pitch = sf[2] if H > 1 else W
-        flow_plane, flow_stride = sf[1], (sf[0] if n > 1 else 2 * sf[1])
-        if (sf[3] != 1 and W > 1) or row_pitch < W or flow_plane < H * row_pitch or flow_stride < 2 * flow_plane:
-            raise ValueError("flows: the innermost dimension must be contiguous and rows, planes and flows must not overlap")
+        row_pitch, flow_plane, flow_stride = _flow_geometry(flows, H, W, "flows", "n", n, ", one flow per image")
         if want_stats and ref is None:
             raise ValueError("want_stats needs ref")
         if ref is not None:
@@ -1616,24 +1648,15 @@ class FlowEngine:
                 raise ValueError("ref must be a torch.uint8 tensor of the images' shape")
         occ_pitch = occ_stride = 0
         if occ is not None:
-            if not isinstance(occ, torch.Tensor) or occ.dtype != torch.uint8 or tuple(occ.shape) != (n, H, W):
-                raise ValueError("occ must be an (n, H, W) torch.uint8 tensor")
-            so = occ.stride()
-            occ_pitch = so[1] if H > 1 else W
-            occ_stride = so[0] if n > 1 else H * occ_pitch
-            if (so[2] != 1 and W > 1) or occ_pitch < W or occ_stride < H * occ_pitch:
-                raise ValueError("occ: the innermost dimension must be contiguous and rows and masks must not overlap")
+            occ_pitch, occ_stride = _plane_geometry(occ, n, H, W, torch.uint8, "occ", "n")
         if out is not None:
             if not isinstance(out, torch.Tensor) or out.dtype != tdt or out.shape != images.shape:
                 raise ValueError(f"out must be a {tdt} tensor of the images' shape")
             och, omem, out_pitch, out_plane, out_image, _ = self._warp_tensor_images(out, layout, "out")
             if (och, omem) != (ch, mem):
                 raise ValueError("out must lie in memory as the images do (interleaved or planar)")
-        others = [t for t in (flows, ref, occ, out) if t is not None]
-        if dev.type != "cuda" or (dev.index is not None and dev.index != getattr(self, "_device", dev.index)):
-            raise ValueError("images must be on this handle's device")
-        if any(t.device != dev for t in others):
-            raise ValueError("flows, ref, occ and out must be on the images' device")
+        self._check_devices(images, "images must be on this handle's device", (flows, ref, occ, out),
+                            "flows, ref, occ and out must be on the images' device")
         if out is None:
             if ch == 3 and mem == 0:  # interleaved memory, whatever the shape's order
                 base = torch.empty((n, H, W, 3), dtype=tdt, device=dev)
@@ -1687,32 +1710,15 @@ class FlowEngine:
         "rounds"."""
         code, rounds, thr, growth = _gm_settings(model, rounds, thr, growth)
         H, W = self.height, self.width
-        fl = np.asarray(flows)
-        if fl.dtype != np.float32 or fl.ndim != 4 or fl.shape[1:] != (2, H, W):
-            raise ValueError("flows must be (M, 2, H, W) float32")
-        fl = np.ascontiguousarray(fl)
+        fl = _np_flows(flows, H, W)
         m = fl.shape[0]
-        if mask is not None:
-            mask = np.asarray(mask)
-            if mask.dtype != np.uint8 or mask.shape != (m, H, W):
-                raise ValueError("mask must be (M, H, W) uint8")
-            mask = np.ascontiguousarray(mask)
+        mask = _np_planes(mask, m, H, W, np.uint8, "mask")
         out, moving = np.empty_like(fl), np.empty((m, H, W), np.uint8)
         rec = np.zeros(m, GM_RESULT_DTYPE)
         if m:
-            ins = [fl] + ([mask] if mask is not None else [])
-            bufs = self._dev_bufs([x.nbytes for x in ins] + [out.nbytes, moving.nbytes, rec.nbytes])
-            try:
-                for p, x in zip(bufs, ins):
-                    self._check(self._L.dfx_memcpy_h2d(self._h, p, x.ctypes.data, x.nbytes))
-                d_out, d_moving, d_rec = bufs[-3:]
-                self.global_motion_device(bufs[0], W, H * W, 2 * H * W, m, d_rec, code, rounds, thr, growth,
-                                          bufs[1] if mask is not None else None, W, H * W, d_out, W, H * W, 2 * H * W,
-                                          d_moving, W, H * W)
-                for x, p in ((out, d_out), (moving, d_moving), (rec, d_rec)):
-                    self._check(self._L.dfx_memcpy_d2h(self._h, x.ctypes.data, p, x.nbytes))
-            finally:
-                self._dev_free(bufs)
+            with self._staged((fl, mask), (out, moving, rec)) as (d_fl, d_mask, d_out, d_moving, d_rec):
+                self.global_motion_device(d_fl, W, H * W, 2 * H * W, m, d_rec, code, rounds, thr, growth, d_mask, W, H * W,
+                                          d_out, W, H * W, 2 * H * W, d_moving, W, H * W)
         return rec["a"].copy(), out, moving, _gm_info(rec)
 
     def global_motion_tensor(self, flows, mask=None, model: str = "affine", rounds: int = 5, thr: float = 0.5,
@@ -1732,38 +1738,18 @@ class FlowEngine:
 
         code, rounds, thr, growth = _gm_settings(model, rounds, thr, growth)
         H, W = self.height, self.width
-
-        def planes(t, what):  # (row pitch, plane stride, flow stride) of an (M, 2, H, W) float32 tensor
-            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 4 or tuple(t.shape[1:]) != (2, H, W):
-                raise ValueError(f"{what} must be an (M, 2, H, W) torch.float32 tensor")
-            st = t.stride()
-            pitch = st[2] if H > 1 else W
-            plane, flow = st[1], (st[0] if t.shape[0] > 1 else 2 * st[1])
-            if (st[3] != 1 and W > 1) or pitch < W or plane < H * pitch or flow < 2 * plane:
-                raise ValueError(f"{what}: the innermost dimension must be contiguous and rows, planes and flows must not overlap")
-            return pitch, plane, flow
-
-        row_pitch, flow_plane, flow_stride = planes(flows, "flows")
+        row_pitch, flow_plane, flow_stride = _flow_geometry(flows, H, W, "flows")
         m, dev = flows.shape[0], flows.device
         mask_pitch = mask_stride = 0
         if mask is not None:
-            if not isinstance(mask, torch.Tensor) or mask.dtype != torch.uint8 or tuple(mask.shape) != (m, H, W):
-                raise ValueError("mask must be an (M, H, W) torch.uint8 tensor")
-            sm = mask.stride()
-            mask_pitch = sm[1] if H > 1 else W
-            mask_stride = sm[0] if m > 1 else H * mask_pitch
-            if (sm[2] != 1 and W > 1) or mask_pitch < W or mask_stride < H * mask_pitch:
-                raise ValueError("mask: the innermost dimension must be contiguous and rows and masks must not overlap")
+            mask_pitch, mask_stride = _plane_geometry(mask, m, H, W, torch.uint8, "mask")
         if out is not None:
-            out_pitch, out_plane, out_stride = planes(out, "out")
+            out_pitch, out_plane, out_stride = _flow_geometry(out, H, W, "out")
             if out.shape[0] != m:
                 raise ValueError("out must be an (M, 2, H, W) torch.float32 tensor")
             if out.data_ptr() == flows.data_ptr() and (out_pitch, out_plane, out_stride) != (row_pitch, flow_plane, flow_stride):
                 raise ValueError("out: in place needs the strides of flows")
-        if dev.type != "cuda" or (dev.index is not None and dev.index != getattr(self, "_device", dev.index)):
-            raise ValueError("flows must be on this handle's device")
-        if any(t.device != dev for t in (mask, out) if t is not None):
-            raise ValueError("mask and out must be on the flows' device")
+        self._check_devices(flows, "flows must be on this handle's device", (mask, out), "mask and out must be on the flows' device")
         if out is None:
             out = torch.empty((m, 2, H, W), dtype=torch.float32, device=dev)
             out_pitch, out_plane, out_stride = W, H * W, 2 * H * W
@@ -1804,40 +1790,29 @@ class FlowEngine:
         where a pixel had no unmasked sample in its window (it keeps its input), None without a mask."""
         ksize, code, passes = _median_settings(ksize, mode, passes, mask is not None)
         H, W = self.height, self.width
-        fl = np.asarray(flows)
-        if fl.dtype != np.float32 or fl.ndim != 4 or fl.shape[1:] != (2, H, W):
-            raise ValueError("flows must be (M, 2, H, W) float32")
-        fl = np.ascontiguousarray(fl)
+        fl = _np_flows(flows, H, W)
         m = fl.shape[0]
-        if mask is not None:
-            mask = np.asarray(mask)
-            if mask.dtype != np.uint8 or mask.shape != (m, H, W):
-                raise ValueError("mask must be (M, H, W) uint8")
-            mask = np.ascontiguousarray(mask)
+        mask = _np_planes(mask, m, H, W, np.uint8, "mask")
         out = np.empty_like(fl)
         mask_out = np.empty((m, H, W), np.uint8) if mask is not None else None
         if m:
-            mb = mask.nbytes if mask is not None else 0
-            bufs = self._dev_bufs([fl.nbytes, fl.nbytes, mb, mb])
-            try:
-                src, dst, msrc, mdst = bufs
-                self._check(self._L.dfx_memcpy_h2d(self._h, src, fl.ctypes.data, fl.nbytes))
-                if mask is not None:
-                    self._check(self._L.dfx_memcpy_h2d(self._h, msrc, mask.ctypes.data, mb))
+            # the passes alternate between two flow buffers and two mask buffers, so the results are fetched by hand from
+            # whichever the last pass wrote
+            spare = [fl.nbytes, mask.nbytes if mask is not None else 0]
+            with self._staged((fl, mask), (), spare) as (src, msrc, dst, mdst):
+                if mask is None:
+                    mdst = None  # (no mask planes either way)
                 for k in range(passes):
-                    self.flow_median_device(src, W, H * W, 2 * H * W, m, dst, W, H * W, 2 * H * W, ksize, code,
-                                            msrc if mask is not None else None, W, H * W,
-                                            mdst if mask is not None else None, W, H * W)
+                    self.flow_median_device(src, W, H * W, 2 * H * W, m, dst, W, H * W, 2 * H * W, ksize, code, msrc, W, H * W,
+                                            mdst, W, H * W)
                     src, dst, msrc, mdst = dst, src, mdst, msrc
                     if mask is not None and code == MEDIAN_MODES["fill"] and k + 1 < passes:
-                        self._check(self._L.dfx_memcpy_d2h(self._h, mask_out.ctypes.data, msrc, mb))
+                        self._check(self._L.dfx_memcpy_d2h(self._h, mask_out.ctypes.data, msrc, mask.nbytes))
                         if not mask_out.any():
                             break
                 self._check(self._L.dfx_memcpy_d2h(self._h, out.ctypes.data, src, out.nbytes))
                 if mask is not None:
-                    self._check(self._L.dfx_memcpy_d2h(self._h, mask_out.ctypes.data, msrc, mb))
-            finally:
-                self._dev_free(bufs)
+                    self._check(self._L.dfx_memcpy_d2h(self._h, mask_out.ctypes.data, msrc, mask.nbytes))
         return out, mask_out
 
     def flow_median_tensor(self, flows, ksize: int = 5, mask=None, mode: str = "all", passes: int = 1, out=None):
@@ -1856,38 +1831,16 @@ class FlowEngine:
 
         ksize, code, passes = _median_settings(ksize, mode, passes, mask is not None)
         H, W = self.height, self.width
-
-        def planes(t, what):  # (row pitch, plane stride, flow stride) of an (M, 2, H, W) float32 tensor
-            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 4 or tuple(t.shape[1:]) != (2, H, W):
-                raise ValueError(f"{what} must be an (M, 2, H, W) torch.float32 tensor")
-            st = t.stride()
-            pitch = st[2] if H > 1 else W
-            plane, flow = st[1], (st[0] if t.shape[0] > 1 else 2 * st[1])
-            if (st[3] != 1 and W > 1) or pitch < W or plane < H * pitch or flow < 2 * plane:
-                raise ValueError(f"{what}: the innermost dimension must be contiguous and rows, planes and flows must not overlap")
-            return pitch, plane, flow
-
-        geom = planes(flows, "flows")
+        geom = _flow_geometry(flows, H, W, "flows")
         m, dev = flows.shape[0], flows.device
-        mgeom = (0, 0)
-        if mask is not None:
-            if not isinstance(mask, torch.Tensor) or mask.dtype != torch.uint8 or tuple(mask.shape) != (m, H, W):
-                raise ValueError("mask must be an (M, H, W) torch.uint8 tensor")
-            sm = mask.stride()
-            mask_pitch = sm[1] if H > 1 else W
-            mgeom = (mask_pitch, sm[0] if m > 1 else H * mask_pitch)
-            if (sm[2] != 1 and W > 1) or mgeom[0] < W or mgeom[1] < H * mgeom[0]:
-                raise ValueError("mask: the innermost dimension must be contiguous and rows and masks must not overlap")
+        mgeom = _plane_geometry(mask, m, H, W, torch.uint8, "mask") if mask is not None else (0, 0)
         if out is not None:
-            ogeom = planes(out, "out")
+            ogeom = _flow_geometry(out, H, W, "out")
             if out.shape[0] != m:
                 raise ValueError("out must be an (M, 2, H, W) torch.float32 tensor")
             if out.data_ptr() == flows.data_ptr() and m:
                 raise ValueError("out must not be flows: a stencil cannot run in place")
-        if dev.type != "cuda" or (dev.index is not None and dev.index != getattr(self, "_device", dev.index)):
-            raise ValueError("flows must be on this handle's device")
-        if any(t.device != dev for t in (mask, out) if t is not None):
-            raise ValueError("mask and out must be on the flows' device")
+        self._check_devices(flows, "flows must be on this handle's device", (mask, out), "mask and out must be on the flows' device")
         dense, mdense = (W, H * W, 2 * H * W), (W, H * W)
         if out is None:
             out = torch.empty((m, 2, H, W), dtype=torch.float32, device=dev)
@@ -1945,33 +1898,17 @@ class FlowEngine:
         (m * E, 2, H, W) float32 and (m * E, H, W) uint8, E = length for "all" and 1 otherwise; valid is 1 where every link so
         far was sampled inside the frame from unoccluded taps."""
         H, W = self.height, self.width
-        fl = np.asarray(flows)
-        if fl.dtype != np.float32 or fl.ndim != 4 or fl.shape[1:] != (2, H, W):
-            raise ValueError("flows must be (N, 2, H, W) float32")
+        fl = _np_flows(flows, H, W, lead="N")
         n = fl.shape[0]
         length, first, hop, m, anchor_step, ecode, bcode = _chain_settings(n, length, first, hop, anchors, anchor_step, emit, border)
-        fl = np.ascontiguousarray(fl)
-        if occ is not None:
-            occ = np.asarray(occ)
-            if occ.dtype != np.uint8 or occ.shape != (n, H, W):
-                raise ValueError("occ must be (N, H, W) uint8")
-            occ = np.ascontiguousarray(occ)
+        occ = _np_planes(occ, n, H, W, np.uint8, "occ", "N")
         e = length if ecode else 1
         out = np.empty((m * e, 2, H, W), np.float32)
         valid = np.empty((m * e, H, W), np.uint8)
         if m:
-            bufs = self._dev_bufs([fl.nbytes, occ.nbytes if occ is not None else 0, out.nbytes, valid.nbytes])
-            try:
-                src, docc, dst, dval = bufs
-                self._check(self._L.dfx_memcpy_h2d(self._h, src, fl.ctypes.data, fl.nbytes))
-                if occ is not None:
-                    self._check(self._L.dfx_memcpy_h2d(self._h, docc, occ.ctypes.data, occ.nbytes))
+            with self._staged((fl, occ), (out, valid)) as (src, docc, dst, dval):
                 self.flow_chain_device(src, W, H * W, 2 * H * W, n, dst, W, H * W, 2 * H * W, length, first, hop, m, anchor_step,
-                                       ecode, bcode, docc if occ is not None else None, W, H * W, dval, W, H * W)
-                self._check(self._L.dfx_memcpy_d2h(self._h, out.ctypes.data, dst, out.nbytes))
-                self._check(self._L.dfx_memcpy_d2h(self._h, valid.ctypes.data, dval, valid.nbytes))
-            finally:
-                self._dev_free(bufs)
+                                       ecode, bcode, docc, W, H * W, dval, W, H * W)
         return out, valid
 
     def flow_chain_tensor(self, flows, length: int, first: int = 0, hop: int = 1, anchors: int | None = None,
@@ -1988,40 +1925,18 @@ class FlowEngine:
         import torch
 
         H, W = self.height, self.width
-
-        def planes(t, what):  # (row pitch, plane stride, flow stride) of an (M, 2, H, W) float32 tensor
-            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 4 or tuple(t.shape[1:]) != (2, H, W):
-                raise ValueError(f"{what} must be an (N, 2, H, W) torch.float32 tensor")
-            st = t.stride()
-            pitch = st[2] if H > 1 else W
-            plane, flow = st[1], (st[0] if t.shape[0] > 1 else 2 * st[1])
-            if (st[3] != 1 and W > 1) or pitch < W or plane < H * pitch or flow < 2 * plane:
-                raise ValueError(f"{what}: the innermost dimension must be contiguous and rows, planes and flows must not overlap")
-            return pitch, plane, flow
-
-        geom = planes(flows, "flows")
+        geom = _flow_geometry(flows, H, W, "flows", "N")
         n, dev = flows.shape[0], flows.device
         length, first, hop, m, anchor_step, ecode, bcode = _chain_settings(n, length, first, hop, anchors, anchor_step, emit, border)
         e = length if ecode else 1
-        ogeom_occ = (0, 0)
-        if occ is not None:
-            if not isinstance(occ, torch.Tensor) or occ.dtype != torch.uint8 or tuple(occ.shape) != (n, H, W):
-                raise ValueError("occ must be an (N, H, W) torch.uint8 tensor")
-            so = occ.stride()
-            occ_pitch = so[1] if H > 1 else W
-            ogeom_occ = (occ_pitch, so[0] if n > 1 else H * occ_pitch)
-            if (so[2] != 1 and W > 1) or ogeom_occ[0] < W or ogeom_occ[1] < H * ogeom_occ[0]:
-                raise ValueError("occ: the innermost dimension must be contiguous and rows and masks must not overlap")
+        ogeom_occ = _plane_geometry(occ, n, H, W, torch.uint8, "occ", "N") if occ is not None else (0, 0)
         if out is not None:
-            ogeom = planes(out, "out")
+            ogeom = _flow_geometry(out, H, W, "out", "N")
             if out.shape[0] != m * e:
                 raise ValueError("out must be an (m * E, 2, H, W) torch.float32 tensor")
             if out.data_ptr() == flows.data_ptr() and m and n:
                 raise ValueError("out must not be flows: a chain cannot run in place")
-        if dev.type != "cuda" or (dev.index is not None and dev.index != getattr(self, "_device", dev.index)):
-            raise ValueError("flows must be on this handle's device")
-        if any(t.device != dev for t in (occ, out) if t is not None):
-            raise ValueError("occ and out must be on the flows' device")
+        self._check_devices(flows, "flows must be on this handle's device", (occ, out), "occ and out must be on the flows' device")
         if out is None:
             out = torch.empty((m * e, 2, H, W), dtype=torch.float32, device=dev)
             ogeom = (W, H * W, 2 * H * W)
@@ -2069,46 +1984,18 @@ class FlowEngine:
         full-weight sources."""
         t, scale, min_weight = _project_settings(t, scale, min_weight)
         H, W = self.height, self.width
-        fl = np.asarray(flows)
-        if fl.dtype != np.float32 or fl.ndim != 4 or fl.shape[1:] != (2, H, W):
-            raise ValueError("flows must be (N, 2, H, W) float32")
-        fl = np.ascontiguousarray(fl)
+        fl = _np_flows(flows, H, W, lead="N")
         n = fl.shape[0]
-        if importance is not None:
-            importance = np.asarray(importance)
-            if importance.dtype != np.float32 or importance.shape != (n, H, W):
-                raise ValueError("importance must be (N, H, W) float32")
-            importance = np.ascontiguousarray(importance)
-        if occ is not None:
-            occ = np.asarray(occ)
-            if occ.dtype != np.uint8 or occ.shape != (n, H, W):
-                raise ValueError("occ must be (N, H, W) uint8")
-            occ = np.ascontiguousarray(occ)
+        importance = _np_planes(importance, n, H, W, np.float32, "importance", "N")
+        occ = _np_planes(occ, n, H, W, np.uint8, "occ", "N")
         out = np.empty((n, 2, H, W), np.float32)
         hole = np.empty((n, H, W), np.uint8)
         cov = np.empty((n, H, W), np.float32) if coverage else None
         if n:
-            per = self.flow_project_work_bytes()
-            wb = per * min(n, 8)
-            bufs = self._dev_bufs([fl.nbytes, importance.nbytes if importance is not None else 0,
-                                   occ.nbytes if occ is not None else 0, out.nbytes, hole.nbytes, cov.nbytes if coverage else 0, wb])
-            try:
-                src, dimp, docc, dst, dhole, dcov, work = bufs
-                self._check(self._L.dfx_memcpy_h2d(self._h, src, fl.ctypes.data, fl.nbytes))
-                if importance is not None:
-                    self._check(self._L.dfx_memcpy_h2d(self._h, dimp, importance.ctypes.data, importance.nbytes))
-                if occ is not None:
-                    self._check(self._L.dfx_memcpy_h2d(self._h, docc, occ.ctypes.data, occ.nbytes))
+            wb = self.flow_project_work_bytes() * min(n, 8)
+            with self._staged((fl, importance, occ), (out, hole, cov), [wb]) as (src, dimp, docc, dst, dhole, dcov, work):
                 self.flow_project_device(src, W, H * W, 2 * H * W, n, work, wb, t, scale, min_weight, dst, W, H * W, 2 * H * W,
-                                         dhole, W, H * W, dcov if coverage else None, W, H * W,
-                                         dimp if importance is not None else None, W, H * W,
-                                         docc if occ is not None else None, W, H * W)
-                self._check(self._L.dfx_memcpy_d2h(self._h, out.ctypes.data, dst, out.nbytes))
-                self._check(self._L.dfx_memcpy_d2h(self._h, hole.ctypes.data, dhole, hole.nbytes))
-                if coverage:
-                    self._check(self._L.dfx_memcpy_d2h(self._h, cov.ctypes.data, dcov, cov.nbytes))
-            finally:
-                self._dev_free(bufs)
+                                         dhole, W, H * W, dcov, W, H * W, dimp, W, H * W, docc, W, H * W)
         return (out, hole, cov) if coverage else (out, hole)
 
     def flow_invert(self, flows, **kw):
@@ -2133,34 +2020,15 @@ class FlowEngine:
 
         t, scale, min_weight = _project_settings(t, scale, min_weight)
         H, W = self.height, self.width
-
-        def planes(x, what):  # (row pitch, plane stride, flow stride) of an (N, 2, H, W) float32 tensor
-            if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.dim() != 4 or tuple(x.shape[1:]) != (2, H, W):
-                raise ValueError(f"{what} must be an (N, 2, H, W) torch.float32 tensor")
-            st = x.stride()
-            pitch = st[2] if H > 1 else W
-            plane, flow = st[1], (st[0] if x.shape[0] > 1 else 2 * st[1])
-            if (st[3] != 1 and W > 1) or pitch < W or plane < H * pitch or flow < 2 * plane:
-                raise ValueError(f"{what}: the innermost dimension must be contiguous and rows, planes and flows must not overlap")
-            return pitch, plane, flow
-
-        geom = planes(flows, "flows")
+        geom = _flow_geometry(flows, H, W, "flows", "N")
         n, dev = flows.shape[0], flows.device
-
-        def plane(x, what, dtype):  # (row pitch, stride) of an (N, H, W) tensor
-            if not isinstance(x, torch.Tensor) or x.dtype != dtype or tuple(x.shape) != (n, H, W):
-                raise ValueError(f"{what} must be an (N, H, W) {dtype} tensor")
-            st = x.stride()
-            pitch = st[1] if H > 1 else W
-            g = (pitch, st[0] if n > 1 else H * pitch)
-            if (st[2] != 1 and W > 1) or g[0] < W or g[1] < H * g[0]:
-                raise ValueError(f"{what}: the innermost dimension must be contiguous and rows and planes must not overlap")
-            return g
-
-        igeom = plane(importance, "importance", torch.float32) if importance is not None else (0, 0)
-        cgeom = plane(occ, "occ", torch.uint8) if occ is not None else (0, 0)
+        igeom = cgeom = (0, 0)
+        if importance is not None:
+            igeom = _plane_geometry(importance, n, H, W, torch.float32, "importance", "N", "planes")
+        if occ is not None:
+            cgeom = _plane_geometry(occ, n, H, W, torch.uint8, "occ", "N", "planes")
         if out is not None:
-            ogeom = planes(out, "out")
+            ogeom = _flow_geometry(out, H, W, "out", "N")
             if out.shape[0] != n:
                 raise ValueError("out must be an (N, 2, H, W) torch.float32 tensor")
             if out.data_ptr() == flows.data_ptr() and n:
@@ -2172,10 +2040,8 @@ class FlowEngine:
             work_bytes = work.numel() * work.element_size()
             if work_bytes < per:
                 raise ValueError(f"work must hold at least {per} bytes (flow_project_work_bytes)")
-        if dev.type != "cuda" or (dev.index is not None and dev.index != getattr(self, "_device", dev.index)):
-            raise ValueError("flows must be on this handle's device")
-        if any(x.device != dev for x in (importance, occ, out, work) if x is not None):
-            raise ValueError("importance, occ, out and work must be on the flows' device")
+        self._check_devices(flows, "flows must be on this handle's device", (importance, occ, out, work),
+                            "importance, occ, out and work must be on the flows' device")
         if work is not None and work.data_ptr() % 8 != 0:
             raise ValueError("work must be 8-byte aligned")
         if out is None:
@@ -2244,25 +2110,12 @@ class FlowEngine:
             raise ValueError("img1 must have the shape of img0")
         n = a0.shape[0]
         H, W = self.height, self.width
-
-        def flows_in(f, what):
-            f = np.asarray(f)
-            if f.dtype != np.float32 or f.shape != (n, 2, H, W):
-                raise ValueError(f"{what} must be (n, 2, H, W) float32, one flow per pair")
-            return np.ascontiguousarray(f)
-
-        def mask_in(m, what):
-            m = np.asarray(m)
-            if m.dtype != np.uint8 or m.shape != (n, H, W):
-                raise ValueError(f"{what} must be (n, H, W) uint8")
-            return np.ascontiguousarray(m)
-
-        fwd = flows_in(fwd, "fwd")
-        bwd = flows_in(bwd, "bwd") if bwd is not None else None
+        fwd = _np_flows(fwd, H, W, "fwd", "n", n, ", one flow per pair")
+        bwd = _np_flows(bwd, H, W, "bwd", "n", n, ", one flow per pair") if bwd is not None else None
         if occ_bwd is not None and bwd is None:
             raise ValueError("occ_bwd needs bwd")
-        occ_fwd = mask_in(occ_fwd, "occ_fwd") if occ_fwd is not None else None
-        occ_bwd = mask_in(occ_bwd, "occ_bwd") if occ_bwd is not None else None
+        occ_fwd = _np_planes(occ_fwd, n, H, W, np.uint8, "occ_fwd", "n")
+        occ_bwd = _np_planes(occ_bwd, n, H, W, np.uint8, "occ_bwd", "n")
         out = np.empty(a0.shape, np_dt)
         source = np.empty((n, H, W), np.uint8) if want_source else None
         if n:
@@ -2271,21 +2124,11 @@ class FlowEngine:
             plane = H * W if planes else 0
             image = ch * H * W
             wb = _interp_work_bytes(W, H, fill_passes) * min(n, 8)
-            ins = [x for x in (a0, a1, fwd, bwd, occ_fwd, occ_bwd) if x is not None]
-            outs = [out] + ([source] if want_source else [])
-            bufs = self._dev_bufs([x.nbytes for x in ins + outs] + [wb])
-            try:
-                for p, x in zip(bufs, ins):
-                    self._check(self._L.dfx_memcpy_h2d(self._h, p, x.ctypes.data, x.nbytes))
-                at = {id(x): p for p, x in zip(bufs, ins + outs)}
-                ptr = lambda x: None if x is None else at[id(x)]  # noqa: E731
-                self.interpolate_device(ptr(a0), ptr(a1), ch, l if ch == 3 else 0, pitch, plane, image, ptr(fwd), ptr(bwd), W,
-                                        H * W, 2 * H * W, n, bufs[-1], wb, t, min_weight, fill_passes, ksize, ptr(occ_fwd),
-                                        ptr(occ_bwd), W, H * W, code, ptr(out), pitch, plane, image, ptr(source), W, H * W)
-                for x in outs:
-                    self._check(self._L.dfx_memcpy_d2h(self._h, x.ctypes.data, at[id(x)], x.nbytes))
-            finally:
-                self._dev_free(bufs)
+            with self._staged((a0, a1, fwd, bwd, occ_fwd, occ_bwd), (out, source), [wb]) as \
+                    (d_a0, d_a1, d_fwd, d_bwd, d_occ_fwd, d_occ_bwd, d_out, d_source, d_work):
+                self.interpolate_device(d_a0, d_a1, ch, l if ch == 3 else 0, pitch, plane, image, d_fwd, d_bwd, W, H * W,
+                                        2 * H * W, n, d_work, wb, t, min_weight, fill_passes, ksize, d_occ_fwd, d_occ_bwd, W,
+                                        H * W, code, d_out, pitch, plane, image, d_source, W, H * W)
         return (out, source) if want_source else out
 
     def interpolate_tensor(self, img0, img1, fwd, bwd=None, t: float = 0.5, occ_fwd=None, occ_bwd=None, fill_passes: int = 3,
@@ -2321,37 +2164,16 @@ class FlowEngine:
         n, dev = img0.shape[0], img0.device
         if img1.shape != img0.shape or (n and img1.stride() != img0.stride()):
             raise ValueError("img1 must have the shape and the strides of img0")
-
-        def planes(x, what):  # (row pitch, plane stride, flow stride) of an (n, 2, H, W) float32 tensor
-            if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or tuple(x.shape) != (n, 2, H, W):
-                raise ValueError(f"{what} must be an (n, 2, H, W) torch.float32 tensor, one flow per pair")
-            st = x.stride()
-            p = st[2] if H > 1 else W
-            g = (p, st[1], st[0] if n > 1 else 2 * st[1])
-            if (st[3] != 1 and W > 1) or g[0] < W or g[1] < H * g[0] or g[2] < 2 * g[1]:
-                raise ValueError(f"{what}: the innermost dimension must be contiguous and rows, planes and flows must not overlap")
-            return g
-
-        def mask(x, what):  # (row pitch, stride) of an (n, H, W) uint8 tensor
-            if not isinstance(x, torch.Tensor) or x.dtype != torch.uint8 or tuple(x.shape) != (n, H, W):
-                raise ValueError(f"{what} must be an (n, H, W) torch.uint8 tensor")
-            st = x.stride()
-            p = st[1] if H > 1 else W
-            g = (p, st[0] if n > 1 else H * p)
-            if (st[2] != 1 and W > 1) or g[0] < W or g[1] < H * g[0]:
-                raise ValueError(f"{what}: the innermost dimension must be contiguous and rows and masks must not overlap")
-            return g
-
-        geom = planes(fwd, "fwd")
-        if bwd is not None and planes(bwd, "bwd") != geom:
+        geom = _flow_geometry(fwd, H, W, "fwd", "n", n, ", one flow per pair")
+        if bwd is not None and _flow_geometry(bwd, H, W, "bwd", "n", n, ", one flow per pair") != geom:
             raise ValueError("bwd must have the strides of fwd")
         if occ_bwd is not None and bwd is None:
             raise ValueError("occ_bwd needs bwd")
         ogeom = (0, 0)
         if occ_fwd is not None:
-            ogeom = mask(occ_fwd, "occ_fwd")
+            ogeom = _plane_geometry(occ_fwd, n, H, W, torch.uint8, "occ_fwd", "n")
         if occ_bwd is not None:
-            g = mask(occ_bwd, "occ_bwd")
+            g = _plane_geometry(occ_bwd, n, H, W, torch.uint8, "occ_bwd", "n")
             if occ_fwd is not None and g != ogeom:
                 raise ValueError("occ_bwd must have the strides of occ_fwd")
             ogeom = g
@@ -2368,10 +2190,8 @@ class FlowEngine:
             work_bytes = work.numel() * work.element_size()
             if work_bytes < per:
                 raise ValueError(f"work must hold at least {per} bytes (interpolate_work_bytes)")
-        if dev.type != "cuda" or (dev.index is not None and dev.index != getattr(self, "_device", dev.index)):
-            raise ValueError("img0 must be on this handle's device")
-        if any(x.device != dev for x in (img1, fwd, bwd, occ_fwd, occ_bwd, out, work) if x is not None):
-            raise ValueError("img1, the flows, the masks, out and work must be on img0's device")
+        self._check_devices(img0, "img0 must be on this handle's device", (img1, fwd, bwd, occ_fwd, occ_bwd, out, work),
+                            "img1, the flows, the masks, out and work must be on img0's device")
         if work is not None and work.data_ptr() % 8 != 0:
             raise ValueError("work must be 8-byte aligned")
         if out is None:
@@ -2456,16 +2276,9 @@ class FlowEngine:
         int(round(alpha * 256)).  return_max: also return the radii sqrt(M2) as an (n,) float32 array and sqrt(MB2)."""
         code, rad, ocode, lay, unk, a256 = _colour_settings(norm, max_rad, order, layout, unknown, alpha)
         H, W = self.height, self.width
-        fl = np.asarray(flows)
-        if fl.dtype != np.float32 or fl.ndim != 4 or fl.shape[1:] != (2, H, W):
-            raise ValueError("flows must be (n, 2, H, W) float32")
-        fl = np.ascontiguousarray(fl)
+        fl = _np_flows(flows, H, W, lead="n")
         n = fl.shape[0]
-        if mask is not None:
-            mask = np.asarray(mask)
-            if mask.dtype != np.uint8 or mask.shape != (n, H, W):
-                raise ValueError("mask must be (n, H, W) uint8")
-            mask = np.ascontiguousarray(mask)
+        mask = _np_planes(mask, n, H, W, np.uint8, "mask", "n")
         fch = 0
         if frame is not None:
             frame = np.asarray(frame)
@@ -2477,25 +2290,11 @@ class FlowEngine:
         m2 = np.zeros(n + 1, np.float32)
         if n:
             want_max = code != 0 or return_max
-            bufs = self._dev_bufs([fl.nbytes, out.nbytes, m2.nbytes, mask.nbytes if mask is not None else 0,
-                                   frame.nbytes if frame is not None else 0])
-            try:
-                self._check(self._L.dfx_memcpy_h2d(self._h, bufs[0], fl.ctypes.data, fl.nbytes))
-                if mask is not None:
-                    self._check(self._L.dfx_memcpy_h2d(self._h, bufs[3], mask.ctypes.data, mask.nbytes))
-                if frame is not None:
-                    self._check(self._L.dfx_memcpy_h2d(self._h, bufs[4], frame.ctypes.data, frame.nbytes))
+            with self._staged((fl, mask, frame), (out, m2 if want_max else None)) as (d_fl, d_mask, d_frame, d_out, d_m2):
                 geom = (W, H * W, 3 * H * W) if lay else (3 * W, 0, 3 * H * W)
                 fgeom = (W, 0, H * W) if fch == 1 else geom
-                self.flow_colour_device(bufs[0], W, H * W, 2 * H * W, n, bufs[1], *geom, code, rad,
-                                        bufs[2] if want_max else None, ocode, lay, unk,
-                                        bufs[3] if mask is not None else None, W, H * W,
-                                        bufs[4] if frame is not None else None, fch, lay, *fgeom, a256)
-                self._check(self._L.dfx_memcpy_d2h(self._h, out.ctypes.data, bufs[1], out.nbytes))
-                if want_max:
-                    self._check(self._L.dfx_memcpy_d2h(self._h, m2.ctypes.data, bufs[2], m2.nbytes))
-            finally:
-                self._dev_free(bufs)
+                self.flow_colour_device(d_fl, W, H * W, 2 * H * W, n, d_out, *geom, code, rad, d_m2, ocode, lay, unk, d_mask, W,
+                                        H * W, d_frame, fch, lay, *fgeom, a256)
         if return_max:
             r = np.sqrt(m2)
             return out, r[:n], r[n]
@@ -2521,24 +2320,11 @@ class FlowEngine:
 
         code, rad, ocode, lay, unk, a256 = _colour_settings(norm, max_rad, order, layout, unknown, alpha)
         H, W = self.height, self.width
-        if not isinstance(flows, torch.Tensor) or flows.dtype != torch.float32 or flows.dim() != 4 or \
-                tuple(flows.shape[1:]) != (2, H, W):
-            raise ValueError("flows must be an (n, 2, H, W) torch.float32 tensor")
+        row_pitch, flow_plane, flow_stride = _flow_geometry(flows, H, W, "flows", "n")
         n, dev = flows.shape[0], flows.device
-        sf = flows.stride()
-        row_pitch = sf[2] if H > 1 else W
-        flow_plane, flow_stride = sf[1], (sf[0] if n > 1 else 2 * sf[1])
-        if (sf[3] != 1 and W > 1) or row_pitch < W or flow_plane < H * row_pitch or flow_stride < 2 * flow_plane:
-            raise ValueError("flows: the innermost dimension must be contiguous and rows, planes and flows must not overlap")
         mask_pitch = mask_stride = 0
         if mask is not None:
-            if not isinstance(mask, torch.Tensor) or mask.dtype != torch.uint8 or tuple(mask.shape) != (n, H, W):
-                raise ValueError("mask must be an (n, H, W) torch.uint8 tensor")
-            sm = mask.stride()
-            mask_pitch = sm[1] if H > 1 else W
-            mask_stride = sm[0] if n > 1 else H * mask_pitch
-            if (sm[2] != 1 and W > 1) or mask_pitch < W or mask_stride < H * mask_pitch:
-                raise ValueError("mask: the innermost dimension must be contiguous and rows and masks must not overlap")
+            mask_pitch, mask_stride = _plane_geometry(mask, n, H, W, torch.uint8, "mask", "n")
         fch, fmem, fgeom = 0, 0, (0, 0, 0)
         if frame is not None:
             if not isinstance(frame, torch.Tensor) or frame.dtype != torch.uint8 or frame.dim() < 3 or frame.shape[0] != n:
@@ -2550,10 +2336,8 @@ class FlowEngine:
             if not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or tuple(out.shape) != shape:
                 raise ValueError(f"out must be a torch.uint8 tensor of shape {shape}")
             _, omem, op, opl, oim, _ = self._warp_tensor_images(out, layout, "out")
-        if dev.type != "cuda" or (dev.index is not None and dev.index != getattr(self, "_device", dev.index)):
-            raise ValueError("flows must be on this handle's device")
-        if any(t.device != dev for t in (mask, frame, out) if t is not None):
-            raise ValueError("mask, frame and out must be on the flows' device")
+        self._check_devices(flows, "flows must be on this handle's device", (mask, frame, out),
+                            "mask, frame and out must be on the flows' device")
         if out is None:
             out = torch.empty(shape, dtype=torch.uint8, device=dev)
             omem, op, opl, oim = (1, W, H * W, 3 * H * W) if lay else (0, 3 * W, 0, 3 * H * W)
@@ -2634,8 +2418,7 @@ class FlowEngine:
                 raise ValueError("out: the masks' innermost dimension must be contiguous and rows and planes must not overlap")
         elif of is not None or ob is not None:
             raise ValueError("out: the masks must be None with check=False")
-        if dev.type != "cuda" or (dev.index is not None and dev.index != getattr(self, "_device", dev.index)):
-            raise ValueError("frames must be on this handle's device")
+        self._check_devices(frames, "frames must be on this handle's device")
         self._num_pairs(n, step)
         torch.cuda.current_stream(dev).synchronize()
 
