@@ -33,22 +33,27 @@ class BroxEngine final : public AlgoEngine {
   private:
     void destroy();
     int grow_frame_slots(int need, long long elems);
+    DfxSlotBufs slot_bufs(long long elems) { // engine_buffers.h: what a frame slot of `elems` floats needs
+        DfxSlotBufs s;
+        s.add(d_frames, frames_cap, (size_t)elems * sizeof(float));
+        return s;
+    }
+    int slots_held() { return dfx_frame_slots_held(slot_bufs(frame_elems), slots.cap); }
     BroxLevelCtx level_ctx(int l, int nb) const;
     dfx_context *c;
-    // what the buffers hold, in bytes (they only grow: set_size re-plans the engine inside them); slot_ids: entries of
-    // d_frame_slots / h_slots_pinned; pair_cap: pairs d_pairs / h_pairs_pinned hold
+    DfxHipAlloc mem{c};
+    // what the buffers hold, in bytes (they only grow: set_size re-plans the engine inside them)
     size_t frames_cap = 0, planes_cap = 0, sink_cap = 0;
-    int slot_ids = 0, pair_cap = 0;
     std::vector<BLevel> lv;
     long long pyr_elems = 0, frame_elems = 0;
     int n_frame_slots = 0;
     float *d_frames = nullptr;
-    int *d_frame_slots = nullptr, *h_slots_pinned = nullptr;
+    DfxTable<int> slots; // frame-slot ids of build_frames
     int B = 0;
     int n_cu = 0; // compute units of the device: the streaming SOR runs one persistent workgroup on each
     float *d_planes = nullptr;
     long long plane_stride = 0, slot_stride = 0;
-    PairDesc *d_pairs = nullptr, *h_pairs_pinned = nullptr;
+    DfxTable<PairDesc> pairs; // descriptors of run_pairs
     float *d_sor_sink = nullptr; // BroxLevelCtx::sor_sink
     hipEvent_t ev[2] = {nullptr, nullptr};
     uint64_t batch_launches = 0;
@@ -56,17 +61,11 @@ class BroxEngine final : public AlgoEngine {
 
 void BroxEngine::destroy() {
     dfx_free_dev(d_frames);
-    dfx_free_dev(d_frame_slots);
-    dfx_free_host(h_slots_pinned);
+    slots.release(mem);
     dfx_free_dev(d_planes);
-    dfx_free_dev(d_pairs);
+    pairs.release(mem);
     dfx_free_dev(d_sor_sink);
-    dfx_free_host(h_pairs_pinned);
-    for (auto &e : ev)
-        if (e) {
-            (void)hipEventDestroy(e);
-            e = nullptr;
-        }
+    dfx_destroy_events(ev, 2);
 }
 
 int BroxEngine::create() {
@@ -92,7 +91,7 @@ int BroxEngine::create() {
 }
 
 size_t BroxEngine::device_bytes() const {
-    return frames_cap + planes_cap + sink_cap + sizeof(int) * (size_t)slot_ids + sizeof(PairDesc) * (size_t)pair_cap;
+    return frames_cap + planes_cap + sink_cap + sizeof(int) * (size_t)slots.cap + sizeof(PairDesc) * (size_t)pairs.cap;
 }
 
 // Plan (engine_plan.h: host arithmetic) + ensure capacity.  Nothing of the engine changes before the last allocation has
@@ -100,33 +99,15 @@ size_t BroxEngine::device_bytes() const {
 int BroxEngine::set_size(int W, int H) {
     BroxPlan pl;
     brox_plan(pl, W, H, c->prm, BROX_FP_COUNT, BROX_PL_COUNT);
-    size_t free_b = 0, total_b = 0;
-    HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
-    int nB = dfx_plan_fit_batch(pl.batch, pl.per_pair, free_b + device_bytes());
     const size_t slot_bytes = (size_t)pl.slot_stride * sizeof(float);
-    if (dfx_grow_buf(c, d_planes, planes_cap, slot_bytes * nB) != DFX_OK) {
-        if (planes_cap == 0)
-            B = 0; // not even the array it had came back: no FlowBuffer runs until a dfx_set_size succeeds
-        if (planes_cap < slot_bytes)
-            return DFX_ERR_HIP;
-        nB = (int)std::min<size_t>(planes_cap / slot_bytes, (size_t)nB); // what the allocation it had holds
-    }
-    if (nB > pair_cap) {
-        PairDesc *nd = nullptr, *nh = nullptr;
-        if (hipMalloc(&nd, sizeof(PairDesc) * nB) != hipSuccess ||
-            hipHostMalloc(&nh, sizeof(PairDesc) * nB, hipHostMallocDefault) != hipSuccess) {
-            (void)hipGetLastError();
-            dfx_free_dev(nd);
-            return dfx_fail(c, DFX_ERR_HIP, "brox: allocating the pair descriptors failed");
-        }
-        dfx_free_dev(d_pairs);
-        dfx_free_host(h_pairs_pinned);
-        d_pairs = nd, h_pairs_pinned = nh;
-        pair_cap = nB;
-    }
+    int nB = 0;
+    if (const int rc = dfx_fit_pair_slots(mem, pl.batch, pl.per_pair, slot_bytes, device_bytes(), d_planes, planes_cap, B, nB))
+        return rc;
+    if (!dfx_grow_tables(mem, nB, pairs))
+        return dfx_fail(c, DFX_ERR_HIP, "brox: allocating the pair descriptors failed");
     const int rc = grow_frame_slots(nB + 1, pl.frame_elems);
     if (rc != DFX_OK) { // the engine goes on at its old size, on the frame slots the buffer still holds
-        n_frame_slots = std::min(n_frame_slots, std::min(dfx_slots_in(frames_cap, (size_t)frame_elems * sizeof(float)), slot_ids));
+        dfx_settle_frame_slots(n_frame_slots, rc, slots_held());
         return rc;
     }
     lv = pl.lv;
@@ -135,28 +116,16 @@ int BroxEngine::set_size(int W, int H) {
     plane_stride = pl.plane_stride;
     slot_stride = pl.slot_stride;
     B = nB;
-    n_frame_slots = std::min(dfx_slots_in(frames_cap, (size_t)frame_elems * sizeof(float)), slot_ids);
+    dfx_settle_frame_slots(n_frame_slots, DFX_OK, slots_held());
     batch_launches = 0;
     return DFX_OK;
 }
 
 int BroxEngine::grow_frame_slots(int need, long long elems) {
-    const int rc = dfx_grow_buf(c, d_frames, frames_cap, (size_t)need * elems * sizeof(float));
-    if (rc != DFX_OK)
+    if (const int rc = dfx_grow_slot_bufs(mem, slot_bufs(elems), need))
         return rc;
-    if (need > slot_ids) {
-        int *nd = nullptr, *nh = nullptr;
-        if (hipMalloc(&nd, sizeof(int) * need) != hipSuccess ||
-            hipHostMalloc(&nh, sizeof(int) * need, hipHostMallocDefault) != hipSuccess) {
-            (void)hipGetLastError();
-            dfx_free_dev(nd);
-            return dfx_fail(c, DFX_ERR_HIP, "brox: allocating the frame-slot tables failed");
-        }
-        dfx_free_dev(d_frame_slots);
-        dfx_free_host(h_slots_pinned);
-        d_frame_slots = nd, h_slots_pinned = nh;
-        slot_ids = need;
-    }
+    if (!dfx_grow_tables(mem, need, slots))
+        return dfx_fail(c, DFX_ERR_HIP, "brox: allocating the frame-slot tables failed");
     return DFX_OK;
 }
 
@@ -165,7 +134,9 @@ int BroxEngine::ensure_frame_slots(int need) {
         return DFX_OK;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     const int rc = grow_frame_slots(need, frame_elems);
-    n_frame_slots = std::min(dfx_slots_in(frames_cap, (size_t)frame_elems * sizeof(float)), slot_ids);
+    // not dfx_settle_frame_slots: after a failure this engine counts whatever the buffers hold, which is more than it
+    // counted before if an earlier set_size failed behind a buffer it had already grown
+    n_frame_slots = slots_held();
     return rc;
 }
 
@@ -173,8 +144,9 @@ int BroxEngine::build_frames(const unsigned char *d_src, long long src_frame_str
                              const int *h_slots) {
     if (n <= 0)
         return DFX_OK;
-    std::memcpy(h_slots_pinned, h_slots, sizeof(int) * n);
-    HIPCHK(c, hipMemcpyAsync(d_frame_slots, h_slots_pinned, sizeof(int) * n, hipMemcpyHostToDevice, c->stream));
+    int *const d_frame_slots = slots.dev;
+    slots.stage(h_slots, n);
+    HIPCHK(c, hipMemcpyAsync(d_frame_slots, slots.host, slots.bytes(n), hipMemcpyHostToDevice, c->stream));
     const float a255 = (float)(1.0 / 255.0); // the reference's convertTo(CV_32F, 1.0/255.0) (:332-333)
     brox_launch_u8_to_f32(c->stream, d_src, src_frame_stride, src_pitch, d_frame_slots, n, d_frames, frame_elems,
                           lv[0].w, lv[0].h, lv[0].pitch, a255);
@@ -208,7 +180,7 @@ BroxLevelCtx BroxEngine::level_ctx(int l, int nb) const {
     x.planes = d_planes;
     x.plane_stride = plane_stride;
     x.slot_stride = slot_stride;
-    x.pairs = d_pairs;
+    x.pairs = pairs.dev;
     x.n_pairs = nb;
     x.alpha = c->prm.brox_alpha;
     x.gamma = c->prm.brox_gamma;
@@ -223,8 +195,8 @@ int BroxEngine::run_pairs(int nb, const PairDesc *h_pairs, float *d_out, long lo
                           const DfxSeedIn *seed) {
     if (seed) // upstream's BroxOpticalFlow takes no initial flow
         return dfx_fail(c, DFX_ERR_UNSUPPORTED, "brox has no initial flow");
-    std::memcpy(h_pairs_pinned, h_pairs, sizeof(PairDesc) * nb);
-    HIPCHK(c, hipMemcpyAsync(d_pairs, h_pairs_pinned, sizeof(PairDesc) * nb, hipMemcpyHostToDevice, c->stream));
+    pairs.stage(h_pairs, nb);
+    HIPCHK(c, hipMemcpyAsync(pairs.dev, pairs.host, pairs.bytes(nb), hipMemcpyHostToDevice, c->stream));
     const dfx_params &p = c->prm;
     int uv = 0;
     batch_launches = 0;
@@ -291,11 +263,7 @@ int BroxEngine::account(int nb) {
     st.step_algorithmic_bytes += bytes * nb;
     (void)sor_bytes;
     st.pairs += (uint64_t)nb;
-    st.levels = (int)std::min<size_t>(lv.size(), DFX_MAX_LEVELS);
-    for (int l = 0; l < st.levels; ++l) {
-        st.level_w[l] = lv[l].w;
-        st.level_h[l] = lv[l].h;
-    }
+    dfx_stats_levels(st, lv.size(), [&](int l) { return std::make_pair(lv[l].w, lv[l].h); });
     return DFX_OK;
 }
 

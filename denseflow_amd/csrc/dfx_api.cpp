@@ -1574,25 +1574,16 @@ void dfx_destroy(dfx_handle h) {
         dfx_free_host(p);
     dfx_jpeg_free(h->jpeg);
     dfx_free_colour(h);
-    for (auto &e : h->ev_h2d)
-        if (e)
-            (void)hipEventDestroy(e);
-    for (auto &e : h->ev_compute)
-        if (e)
-            (void)hipEventDestroy(e);
-    for (auto &e : h->ev_d2h)
-        if (e)
-            (void)hipEventDestroy(e);
+    dfx_destroy_events(h->ev_h2d, 2);
+    dfx_destroy_events(h->ev_compute, 2);
+    dfx_destroy_events(h->ev_d2h, 2);
     if (h->copy_stream)
         (void)hipStreamDestroy(h->copy_stream);
     if (h->d2h_stream)
         (void)hipStreamDestroy(h->d2h_stream);
-    if (h->ev_block)
-        (void)hipEventDestroy(h->ev_block);
-    if (h->ev_t0)
-        (void)hipEventDestroy(h->ev_t0);
-    if (h->ev_t1)
-        (void)hipEventDestroy(h->ev_t1);
+    dfx_destroy_events(&h->ev_block, 1);
+    dfx_destroy_events(&h->ev_t0, 1);
+    dfx_destroy_events(&h->ev_t1, 1);
     if (h->stream)
         (void)hipStreamDestroy(h->stream);
     delete h;

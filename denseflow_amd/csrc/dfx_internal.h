@@ -21,6 +21,7 @@
 #include "dfx_device.h"
 #include "dfx_handover.h"
 #include "dfx_helper.h"
+#include "engine_buffers.h"
 #include "engine_plan.h"
 
 // An algorithm engine owns every device buffer of one handle.  The common driver (dfx_pipeline.cpp)
@@ -265,8 +266,6 @@ inline int dfx_fail(dfx_context *c, int code, const std::string &msg) {
     return code;
 }
 
-inline int dfx_cv_round(double v) { return (int)std::lrint(v); } // round-half-even
-
 template <class T> inline void dfx_free_dev(T *&p) {
     if (p) {
         (void)hipFree(p);
@@ -280,16 +279,50 @@ template <class T> inline void dfx_free_host(T *&p) {
     }
 }
 
-// Slots of `each` bytes that a buffer of `bytes` holds, as an int.
-inline int dfx_slots_in(size_t bytes, size_t each) {
-    return each ? (int)std::min<size_t>(bytes / each, (size_t)1 << 30) : 0;
+// The allocator policy of engine_buffers.h on HIP: the engines' buffers and tables grow through it.
+struct DfxHipAlloc {
+    dfx_context *c;
+    static int checked(hipError_t e, void **p) {
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            *p = nullptr;
+        }
+        return (int)e;
+    }
+    int dev(void **p, size_t bytes) { return checked(hipMalloc(p, bytes), p); }
+    int pinned(void **p, size_t bytes) { return checked(hipHostMalloc(p, bytes, hipHostMallocDefault), p); }
+    void free_dev(void *p) { (void)hipFree(p); }
+    void free_pinned(void *p) { (void)hipHostFree(p); }
+    int free_bytes(size_t *out) {
+        size_t free_b = 0, total_b = 0;
+        HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
+        *out = free_b;
+        return 0;
+    }
+    void failed(size_t bytes, int code) {
+        char buf[256];
+        snprintf(buf, sizeof buf, "allocating %zu bytes failed: %s", bytes, hipGetErrorString((hipError_t)code));
+        c->set_err(buf);
+    }
+};
+
+inline void dfx_destroy_events(hipEvent_t *ev, size_t n) {
+    for (size_t i = 0; i < n; ++i)
+        if (ev[i]) {
+            (void)hipEventDestroy(ev[i]);
+            ev[i] = nullptr;
+        }
 }
 
-// A buffer that only grows (the engines' set_size): `cap` is what p holds, in bytes.  Large enough: untouched.  Otherwise
-// the old buffer is freed first (a pair-slot array is most of a handle's memory: two of them may not fit) and, should the
-// new allocation fail, allocated again at its old size, so that the owner can go on at the size it had.  host_flags < 0:
-// device memory, otherwise hipHostMalloc with these flags.  Nothing may be using the buffer.
-template <class T> inline int dfx_grow_buf(dfx_context *c, T *&p, size_t &cap, size_t need, int host_flags = -1);
+// The level table of dfx_stats, the tail of every engine's account(): size_of(l) is level l's (width, height).
+template <class F> inline void dfx_stats_levels(dfx_stats &st, size_t n, F size_of) {
+    st.levels = (int)std::min<size_t>(n, DFX_MAX_LEVELS);
+    for (int l = 0; l < st.levels; ++l) {
+        const auto wh = size_of(l);
+        st.level_w[l] = wh.first;
+        st.level_h[l] = wh.second;
+    }
+}
 
 // Grow a set of buffers that is sized for `count` slots to `need`: nothing may use the old ones (deferred tails, device
 // work), and `alloc` — which frees them and allocates the new ones — may fail half-way.
@@ -301,34 +334,6 @@ template <class N, class F> inline int dfx_regrow(dfx_context *c, N &count, N ne
     if (rc == DFX_OK)
         count = need;
     return rc;
-}
-
-template <class T> inline int dfx_grow_buf(dfx_context *c, T *&p, size_t &cap, size_t need, int host_flags) {
-    if (need <= cap)
-        return DFX_OK;
-    const auto alloc = [&](size_t bytes) {
-        return host_flags < 0 ? hipMalloc((void **)&p, bytes) : hipHostMalloc((void **)&p, bytes, (unsigned)host_flags);
-    };
-    if (host_flags < 0)
-        dfx_free_dev(p);
-    else
-        dfx_free_host(p);
-    const hipError_t e = alloc(need);
-    if (e == hipSuccess) {
-        cap = need;
-        return DFX_OK;
-    }
-    (void)hipGetLastError();
-    p = nullptr;
-    if (cap > 0 && alloc(cap) != hipSuccess) {
-        (void)hipGetLastError();
-        p = nullptr;
-        cap = 0;
-    }
-    char buf[256];
-    snprintf(buf, sizeof buf, "allocating %zu bytes failed: %s", need, hipGetErrorString(e));
-    c->set_err(buf);
-    return DFX_ERR_HIP;
 }
 
 // dfx_set_size: the shared staging of dfx_pipeline.cpp re-counted for the context's new W x H (nothing is allocated)

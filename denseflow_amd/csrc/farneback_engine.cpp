@@ -85,12 +85,12 @@ class FarnebackEngine final : public AlgoEngine {
   private:
     void destroy();
     int grow_frame_slots(int need, long long elems, long long plane);
-    int slots_held() const;
+    DfxSlotBufs slot_bufs(long long elems, long long plane);
+    int slots_held() { return dfx_frame_slots_held(slot_bufs(frame_elems, plane_stride), slots.cap); }
     dfx_context *c;
-    // what the buffers hold, in bytes (they only grow: set_size re-plans the engine inside them); slot_ids: entries of
-    // d_frame_slots / h_slots_pinned; pair_cap: pairs d_pairs / h_pairs_pinned hold
+    DfxHipAlloc mem{c};
+    // what the buffers hold, in bytes (they only grow: set_size re-plans the engine inside them)
     size_t gker_cap = 0, R_cap = 0, f32_cap = 0, tmpv_cap = 0, pyr_cap = 0, planes_cap = 0;
-    int slot_ids = 0, pair_cap = 0;
     int nlev = 0; // levels 0..nlev-1 (nlev = numLevelsCropped + 1)
     FLevel lv[DFX_LVL_MAX];
     long long frame_elems = 0;
@@ -100,8 +100,7 @@ class FarnebackEngine final : public AlgoEngine {
 
     int n_frame_slots = 0;
     float *d_R = nullptr;
-    int *d_frame_slots = nullptr;
-    int *h_slots_pinned = nullptr;
+    DfxTable<int> slots; // frame-slot ids of build_frames
     // scratch for frame preparation, sized for n_frame_slots frames
     float *d_f32 = nullptr, *d_tmpv = nullptr, *d_pyr = nullptr;
     int skip_zero_weights = 1, polyexp_rows = 16; // frame-preparation forms, fixed when the engine is created
@@ -114,27 +113,20 @@ class FarnebackEngine final : public AlgoEngine {
     int B = 0;
     float *d_planes = nullptr;
     long long plane_stride = 0, slot_stride = 0;
-    PairDesc *d_pairs = nullptr, *h_pairs_pinned = nullptr;
+    DfxTable<PairDesc> pairs; // descriptors of run_pairs
     hipEvent_t ev_it[DFX_LVL_MAX][2] = {};
 };
 
 void FarnebackEngine::destroy() {
     dfx_free_dev(d_gker);
     dfx_free_dev(d_R);
-    dfx_free_dev(d_frame_slots);
-    dfx_free_host(h_slots_pinned);
+    slots.release(mem);
     dfx_free_dev(d_f32);
     dfx_free_dev(d_tmpv);
     dfx_free_dev(d_pyr);
     dfx_free_dev(d_planes);
-    dfx_free_dev(d_pairs);
-    dfx_free_host(h_pairs_pinned);
-    for (auto &e : ev_it)
-        for (auto &x : e)
-            if (x) {
-                (void)hipEventDestroy(x);
-                x = nullptr;
-            }
+    pairs.release(mem);
+    dfx_destroy_events(&ev_it[0][0], DFX_LVL_MAX * 2);
 }
 
 int FarnebackEngine::create() {
@@ -179,8 +171,8 @@ int FarnebackEngine::create() {
 }
 
 size_t FarnebackEngine::device_bytes() const {
-    return gker_cap + R_cap + f32_cap + tmpv_cap + pyr_cap + planes_cap + sizeof(int) * (size_t)slot_ids +
-           sizeof(PairDesc) * (size_t)pair_cap;
+    return gker_cap + R_cap + f32_cap + tmpv_cap + pyr_cap + planes_cap + sizeof(int) * (size_t)slots.cap +
+           sizeof(PairDesc) * (size_t)pairs.cap;
 }
 
 // Plan (engine_plan.h: host arithmetic) + ensure capacity.  Nothing of the engine changes before the last allocation has
@@ -198,35 +190,17 @@ int FarnebackEngine::set_size(int W, int H) {
                  W, H, pl.fast_max_levels);
         return dfx_fail(c, DFX_ERR_UNSUPPORTED, msg);
     }
-    size_t free_b = 0, total_b = 0;
-    HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
-    int nB = dfx_plan_fit_batch(pl.batch, pl.per_pair, free_b + device_bytes());
     const size_t slot_bytes = (size_t)pl.slot_stride * sizeof(float);
-    if (dfx_grow_buf(c, d_planes, planes_cap, slot_bytes * nB) != DFX_OK) {
-        if (planes_cap == 0)
-            B = 0; // not even the array it had came back: no FlowBuffer runs until a dfx_set_size succeeds
-        if (planes_cap < slot_bytes)
-            return DFX_ERR_HIP;
-        nB = (int)std::min<size_t>(planes_cap / slot_bytes, (size_t)nB); // what the allocation it had holds
-    }
-    if (nB > pair_cap) {
-        PairDesc *nd = nullptr, *nh = nullptr;
-        if (hipMalloc(&nd, sizeof(PairDesc) * nB) != hipSuccess ||
-            hipHostMalloc(&nh, sizeof(PairDesc) * nB, hipHostMallocDefault) != hipSuccess) {
-            (void)hipGetLastError();
-            dfx_free_dev(nd);
-            return dfx_fail(c, DFX_ERR_HIP, "farn: allocating the pair descriptors failed");
-        }
-        dfx_free_dev(d_pairs);
-        dfx_free_host(h_pairs_pinned);
-        d_pairs = nd, h_pairs_pinned = nh;
-        pair_cap = nB;
-    }
-    int rc = dfx_grow_buf(c, d_gker, gker_cap, sizeof(float) * pl.taps.size());
+    int nB = 0;
+    if (const int rc = dfx_fit_pair_slots(mem, pl.batch, pl.per_pair, slot_bytes, device_bytes(), d_planes, planes_cap, B, nB))
+        return rc;
+    if (!dfx_grow_tables(mem, nB, pairs))
+        return dfx_fail(c, DFX_ERR_HIP, "farn: allocating the pair descriptors failed");
+    int rc = dfx_grow(mem, d_gker, gker_cap, sizeof(float) * pl.taps.size());
     if (rc == DFX_OK)
         rc = grow_frame_slots(nB + 1, pl.frame_elems, pl.plane_stride);
     if (rc != DFX_OK) { // the engine goes on at its old size, on the frame slots the buffers still hold
-        n_frame_slots = std::min(n_frame_slots, slots_held());
+        dfx_settle_frame_slots(n_frame_slots, rc, slots_held());
         return rc;
     }
     // the context is idle: the taps of the previous size are no longer read
@@ -242,46 +216,28 @@ int FarnebackEngine::set_size(int W, int H) {
     plane_stride = pl.plane_stride;
     slot_stride = pl.slot_stride;
     B = nB;
-    n_frame_slots = slots_held();
+    dfx_settle_frame_slots(n_frame_slots, DFX_OK, slots_held());
     return DFX_OK;
 }
 
-// frame slots the buffers hold at the current geometry
-int FarnebackEngine::slots_held() const {
-    const size_t pb = (size_t)plane_stride * sizeof(float);
-    int n = std::min(dfx_slots_in(R_cap, (size_t)frame_elems * sizeof(float)), slot_ids);
-    n = std::min(n, std::min(dfx_slots_in(tmpv_cap, 2 * pb), dfx_slots_in(pyr_cap, pb)));
-    if (!skip_zero_weights)
-        n = std::min(n, dfx_slots_in(f32_cap, pb));
-    return n;
+// What a frame slot needs (engine_buffers.h), in the order it is allocated: `elems` floats of R and scratch planes of
+// `plane` floats.
+DfxSlotBufs FarnebackEngine::slot_bufs(long long elems, long long plane) {
+    const size_t pb = (size_t)plane * sizeof(float);
+    DfxSlotBufs s;
+    s.add(d_R, R_cap, (size_t)elems * sizeof(float));
+    if (!skip_zero_weights) // only the cross-check chain converts the frames to a float plane first
+        s.add(d_f32, f32_cap, pb);
+    s.add(d_tmpv, tmpv_cap, 2 * pb);
+    s.add(d_pyr, pyr_cap, pb);
+    return s;
 }
 
-// `need` frame slots of `elems` floats of R and `plane` floats per scratch plane.  A failure leaves every buffer at least
-// as large as it was.
 int FarnebackEngine::grow_frame_slots(int need, long long elems, long long plane) {
-    const size_t pb = (size_t)need * plane * sizeof(float);
-    int rc = dfx_grow_buf(c, d_R, R_cap, (size_t)need * elems * sizeof(float));
-    if (rc == DFX_OK && !skip_zero_weights) // only the cross-check chain converts the frames to a float plane first
-        rc = dfx_grow_buf(c, d_f32, f32_cap, pb);
-    if (rc == DFX_OK)
-        rc = dfx_grow_buf(c, d_tmpv, tmpv_cap, 2 * pb);
-    if (rc == DFX_OK)
-        rc = dfx_grow_buf(c, d_pyr, pyr_cap, pb);
-    if (rc != DFX_OK)
+    if (const int rc = dfx_grow_slot_bufs(mem, slot_bufs(elems, plane), need))
         return rc;
-    if (need > slot_ids) {
-        int *nd = nullptr, *nh = nullptr;
-        if (hipMalloc(&nd, sizeof(int) * need) != hipSuccess ||
-            hipHostMalloc(&nh, sizeof(int) * need, hipHostMallocDefault) != hipSuccess) {
-            (void)hipGetLastError();
-            dfx_free_dev(nd);
-            return dfx_fail(c, DFX_ERR_HIP, "farn: allocating the frame-slot tables failed");
-        }
-        dfx_free_dev(d_frame_slots);
-        dfx_free_host(h_slots_pinned);
-        d_frame_slots = nd, h_slots_pinned = nh;
-        slot_ids = need;
-    }
+    if (!dfx_grow_tables(mem, need, slots))
+        return dfx_fail(c, DFX_ERR_HIP, "farn: allocating the frame-slot tables failed");
     return DFX_OK;
 }
 
@@ -290,6 +246,8 @@ int FarnebackEngine::ensure_frame_slots(int need) {
         return DFX_OK;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     const int rc = grow_frame_slots(need, frame_elems, plane_stride);
+    // not dfx_settle_frame_slots: after a failure this engine counts whatever the buffers hold, which is more than it
+    // counted before if an earlier set_size failed behind buffers it had already grown
     n_frame_slots = slots_held();
     return rc;
 }
@@ -298,8 +256,9 @@ int FarnebackEngine::build_frames(const unsigned char *d_src, long long src_fram
                                   const int *h_slots) {
     if (n <= 0)
         return DFX_OK;
-    std::memcpy(h_slots_pinned, h_slots, sizeof(int) * n);
-    HIPCHK(c, hipMemcpyAsync(d_frame_slots, h_slots_pinned, sizeof(int) * n, hipMemcpyHostToDevice, c->stream));
+    int *const d_frame_slots = slots.dev;
+    slots.stage(h_slots, n);
+    HIPCHK(c, hipMemcpyAsync(d_frame_slots, slots.host, slots.bytes(n), hipMemcpyHostToDevice, c->stream));
     const int W = c->W, H = c->H;
     if (fast_pyr) {
         // B.13, walking UP the pyramid: level 0 is the frame as float, level k one pyrDown of level k - 1.  The levels
@@ -344,8 +303,8 @@ int FarnebackEngine::build_frames(const unsigned char *d_src, long long src_fram
 
 int FarnebackEngine::run_pairs(int nb, const PairDesc *h_pairs, float *d_out, long long out_stride, const DfxPlanarOut *planar,
                                const DfxSeedIn *seed) {
-    std::memcpy(h_pairs_pinned, h_pairs, sizeof(PairDesc) * nb);
-    HIPCHK(c, hipMemcpyAsync(d_pairs, h_pairs_pinned, sizeof(PairDesc) * nb, hipMemcpyHostToDevice, c->stream));
+    pairs.stage(h_pairs, nb);
+    HIPCHK(c, hipMemcpyAsync(pairs.dev, pairs.host, pairs.bytes(nb), hipMemcpyHostToDevice, c->stream));
     const dfx_params &p = c->prm;
     const int half = p.farn_win_size / 2;
     const float box_inv = 1.f / (float)((1 + 2 * half) * (1 + 2 * half));
@@ -366,7 +325,7 @@ int FarnebackEngine::run_pairs(int nb, const PairDesc *h_pairs, float *d_out, lo
     x.planes = d_planes;
     x.plane_stride = plane_stride;
     x.slot_stride = slot_stride;
-    x.pairs = d_pairs;
+    x.pairs = pairs.dev;
     x.n_pairs = nb;
     // M recomputed inside the iteration kernel (round 4) unless the window is not one of the row-stream kernel's or a
     // cross-check form is asked for
@@ -486,11 +445,7 @@ int FarnebackEngine::account(int nb) {
     st.algorithmic_bytes += (bytes + seed_bytes_pair) * nb;
     st.step_algorithmic_bytes += it_bytes * nb;
     st.pairs += (uint64_t)nb;
-    st.levels = nlev;
-    for (int k = 0; k < nlev; ++k) {
-        st.level_w[k] = lv[k].g.w;
-        st.level_h[k] = lv[k].g.h;
-    }
+    dfx_stats_levels(st, nlev, [&](int k) { return std::make_pair(lv[k].g.w, lv[k].g.h); });
     return DFX_OK;
 }
 

@@ -43,42 +43,43 @@ class Tvl1Engine final : public AlgoEngine {
   private:
     void destroy();
     int grow_frame_slots(int need, long long elems);
-    int frame_slots_held(long long elems) const { // frame slots of `elems` floats per pyramid that the buffers hold
-        const size_t least = std::min(pyr_cap[0], std::min(pyr_cap[1], pyr_cap[2]));
-        return elems > 0 ? std::min(dfx_slots_in(least, (size_t)elems * sizeof(float)), slot_ids) : 0;
+    DfxSlotBufs slot_bufs(long long elems) { // engine_buffers.h: a frame slot is `elems` floats in each pyramid
+        DfxSlotBufs s;
+        s.add(dI, pyr_cap[0], (size_t)elems * sizeof(float));
+        s.add(dIx, pyr_cap[1], (size_t)elems * sizeof(float));
+        s.add(dIy, pyr_cap[2], (size_t)elems * sizeof(float));
+        return s;
     }
+    int slots_held() { return dfx_frame_slots_held(slot_bufs(frame_elems), slots.cap); }
     Tvl1LevelCtx level_ctx(int s, int n_pairs) const;
     int steps_per_group(int s, int nb) const;
     int refuse_if_too_large(const Tvl1Plan &pl);
 
     dfx_context *c;
+    DfxHipAlloc mem{c};
     int nlevels = 0;
     Level lv[DFX_LVL_MAX];
     long long frame_elems = 0;
 
     int n_frame_slots = 0;
     float *dI = nullptr, *dIx = nullptr, *dIy = nullptr;
-    int *d_frame_slots = nullptr;
-    int *h_slots_pinned = nullptr;
-    // what the buffers hold (they only grow: set_size re-plans the engine inside them).  pyr_cap: bytes of dI / dIx /
-    // dIy; slot_ids: entries of d_frame_slots / h_slots_pinned; planes_cap / partials_cap: bytes; pair_cap: pairs the
-    // per-pair arrays (state, descriptors, tables) hold.
+    DfxTable<int> slots; // frame-slot ids of build_frames
+    // what the buffers hold, in bytes (they only grow: set_size re-plans the engine inside them); pyr_cap: dI / dIx / dIy
     size_t pyr_cap[3] = {0, 0, 0}, planes_cap = 0, partials_cap = 0;
-    int slot_ids = 0, pair_cap = 0;
 
     int B = 0;
     float *d_planes = nullptr;
     long long plane_stride = 0, slot_stride = 0;
     int n_planes = PL_COUNT; // planes of a pair slot (the plan's: PL_COUNT_GAMMA with the illumination channel)
     bool gamma_on = false;   // dfx_params.tvl1_gamma != 0: a pair slot has the planes of u3 / p31 / p32 and their kernels run
-    Tvl1State *d_state = nullptr;
-    PairDesc *d_pairs = nullptr;
-    PairDesc *h_pairs_pinned = nullptr;
+    // the per-pair arrays: they grow together (dfx_grow_tables), so pairs.cap is the pairs every one of them holds
+    DfxTable<Tvl1State> state{1, false};
+    DfxTable<PairDesc> pairs;                               // descriptors of run_pairs
+    DfxTable<int> iter_tab{DFX_LVL_MAX * TVL1_MAX_WARPS};   // read back after every batch, as are check_tab and work_tab
+    DfxTable<int> check_tab{DFX_LVL_MAX * 2};
+    DfxTable<long long> work_tab{DFX_LVL_MAX * 2};
     double *d_partials = nullptr;
     int partials_stride = 0;
-    int *d_iters_out = nullptr, *d_checks_out = nullptr;
-    int *h_iters = nullptr, *h_checks = nullptr;
-    long long *d_work_out = nullptr, *h_work = nullptr;
     unsigned int *d_level_done = nullptr;
     int *h_done_flag = nullptr, *d_done_flag = nullptr;
     hipEvent_t ev_group[2] = {nullptr, nullptr};
@@ -90,7 +91,7 @@ class Tvl1Engine final : public AlgoEngine {
     int geom = 0;            // 1 = tile columns of the step kernel start at x = 0 (Tvl1LevelCtx::geom)
     bool warp_head = false;  // the warp kernel also runs the head of the loop it starts (k_tvl1_warp_head)
     int launched_steps[DFX_LVL_MAX] = {0};
-    int last_nb = 0; // pairs of the batch whose read-backs h_iters / h_checks hold (set by account)
+    int last_nb = 0; // pairs of the batch whose read-backs iter_tab / check_tab hold (set by account)
     double seed_bytes_pair = 0; // bytes per pair the seed chain of the batch in flight moved (0: no seed; folded in by account)
 
     Tvl1LoopCfg loop{};
@@ -101,32 +102,14 @@ void Tvl1Engine::destroy() {
     dfx_free_dev(dI);
     dfx_free_dev(dIx);
     dfx_free_dev(dIy);
-    dfx_free_dev(d_frame_slots);
-    dfx_free_host(h_slots_pinned);
+    slots.release(mem);
     dfx_free_dev(d_planes);
-    dfx_free_dev(d_state);
-    dfx_free_dev(d_pairs);
-    dfx_free_host(h_pairs_pinned);
+    state.release(mem), pairs.release(mem), iter_tab.release(mem), check_tab.release(mem), work_tab.release(mem);
     dfx_free_dev(d_partials);
-    dfx_free_dev(d_iters_out);
-    dfx_free_dev(d_checks_out);
-    dfx_free_dev(d_work_out);
-    dfx_free_host(h_work);
-    dfx_free_host(h_iters);
-    dfx_free_host(h_checks);
     dfx_free_dev(d_level_done);
     dfx_free_host(h_done_flag);
-    for (auto &e : ev_group)
-        if (e) {
-            (void)hipEventDestroy(e);
-            e = nullptr;
-        }
-    for (auto &e : ev_lvl)
-        for (auto &x : e)
-            if (x) {
-                (void)hipEventDestroy(x);
-                x = nullptr;
-            }
+    dfx_destroy_events(ev_group, 2);
+    dfx_destroy_events(&ev_lvl[0][0], DFX_LVL_MAX * 2);
 }
 
 int Tvl1Engine::create() {
@@ -197,7 +180,7 @@ int Tvl1Engine::create() {
 size_t Tvl1Engine::device_bytes() const {
     const size_t per_pair = sizeof(Tvl1State) + sizeof(PairDesc) + sizeof(int) * DFX_LVL_MAX * (TVL1_MAX_WARPS + 2) +
                             sizeof(long long) * DFX_LVL_MAX * 2;
-    return planes_cap + partials_cap + pyr_cap[0] + pyr_cap[1] + pyr_cap[2] + sizeof(int) * (size_t)slot_ids + per_pair * (size_t)pair_cap +
+    return planes_cap + partials_cap + pyr_cap[0] + pyr_cap[1] + pyr_cap[2] + sizeof(int) * (size_t)slots.cap + per_pair * (size_t)pairs.cap +
            (d_level_done ? sizeof(unsigned int) : 0);
 }
 
@@ -218,54 +201,24 @@ int Tvl1Engine::set_size(int W, int H) {
         return rc;
     // batch: enough pairs that the coarse levels fill 256 CUs, bounded by memory — by what is free now plus what this
     // engine holds and would give back for a larger allocation
-    size_t free_b = 0, total_b = 0;
-    HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
-    int nB = dfx_plan_fit_batch(pl.batch, pl.per_pair, free_b + device_bytes());
     const size_t slot_bytes = (size_t)pl.slot_stride * sizeof(float);
-    if (dfx_grow_buf(c, d_planes, planes_cap, slot_bytes * nB) != DFX_OK) {
-        if (planes_cap == 0)
-            B = 0; // not even the array it had came back: no FlowBuffer runs until a dfx_set_size succeeds
-        if (planes_cap < slot_bytes)
-            return DFX_ERR_HIP;
-        nB = (int)std::min<size_t>(planes_cap / slot_bytes, (size_t)nB); // what the allocation it had holds
-    }
-    if (nB > pair_cap) {
-        // small arrays: the new set first, the old one is freed only when every allocation has succeeded
-        Tvl1State *n_state = nullptr;
-        PairDesc *n_pairs = nullptr, *n_hpairs = nullptr;
-        int *n_iters = nullptr, *n_checks = nullptr, *n_hiters = nullptr, *n_hchecks = nullptr;
-        long long *n_work = nullptr, *n_hwork = nullptr;
-        const size_t it = sizeof(int) * nB * DFX_LVL_MAX * TVL1_MAX_WARPS, ck = sizeof(int) * nB * DFX_LVL_MAX * 2,
-                     wk = sizeof(long long) * nB * DFX_LVL_MAX * 2;
-        const bool ok = hipMalloc(&n_state, sizeof(Tvl1State) * nB) == hipSuccess &&
-                        hipMalloc(&n_pairs, sizeof(PairDesc) * nB) == hipSuccess &&
-                        hipHostMalloc(&n_hpairs, sizeof(PairDesc) * nB, hipHostMallocDefault) == hipSuccess &&
-                        hipMalloc(&n_iters, it) == hipSuccess && hipMalloc(&n_checks, ck) == hipSuccess &&
-                        hipMalloc(&n_work, wk) == hipSuccess && hipHostMalloc(&n_hwork, wk, hipHostMallocDefault) == hipSuccess &&
-                        hipHostMalloc(&n_hiters, it, hipHostMallocDefault) == hipSuccess &&
-                        hipHostMalloc(&n_hchecks, ck, hipHostMallocDefault) == hipSuccess;
-        if (!ok) {
-            (void)hipGetLastError();
-            dfx_free_dev(n_state), dfx_free_dev(n_pairs), dfx_free_host(n_hpairs), dfx_free_dev(n_iters);
-            dfx_free_dev(n_checks), dfx_free_dev(n_work), dfx_free_host(n_hwork), dfx_free_host(n_hiters);
-            dfx_free_host(n_hchecks);
-            return dfx_fail(c, DFX_ERR_HIP, "tvl1: allocating the per-pair tables failed");
-        }
-        dfx_free_dev(d_state), dfx_free_dev(d_pairs), dfx_free_host(h_pairs_pinned), dfx_free_dev(d_iters_out);
-        dfx_free_dev(d_checks_out), dfx_free_dev(d_work_out), dfx_free_host(h_work), dfx_free_host(h_iters);
-        dfx_free_host(h_checks);
-        d_state = n_state, d_pairs = n_pairs, h_pairs_pinned = n_hpairs, d_iters_out = n_iters, d_checks_out = n_checks;
-        d_work_out = n_work, h_work = n_hwork, h_iters = n_hiters, h_checks = n_hchecks;
-        pair_cap = nB;
-        // as create leaves them: should a later allocation of this call fail, the engine goes on at its old size on these
-        HIPCHK(c, hipMemset(d_state, 0, sizeof(Tvl1State) * pair_cap));
-        HIPCHK(c, hipMemset(d_work_out, 0, sizeof(long long) * pair_cap * DFX_LVL_MAX * 2));
-    }
-    int rc = dfx_grow_buf(c, d_partials, partials_cap, sizeof(double) * (size_t)pl.partials_stride * nB);
-    if (rc == DFX_OK)
-        rc = grow_frame_slots(nB + 1, pl.frame_elems);
-    if (rc != DFX_OK)
+    int nB = 0;
+    if (const int rc = dfx_fit_pair_slots(mem, pl.batch, pl.per_pair, slot_bytes, device_bytes(), d_planes, planes_cap, B, nB))
         return rc;
+    if (nB > pairs.cap) {
+        if (!dfx_grow_tables(mem, nB, state, pairs, iter_tab, check_tab, work_tab))
+            return dfx_fail(c, DFX_ERR_HIP, "tvl1: allocating the per-pair tables failed");
+        // as create leaves them: should a later allocation of this call fail, the engine goes on at its old size on these
+        HIPCHK(c, hipMemset(state.dev, 0, state.bytes(pairs.cap)));
+        HIPCHK(c, hipMemset(work_tab.dev, 0, work_tab.bytes(pairs.cap)));
+    }
+    if (const int rc = dfx_grow(mem, d_partials, partials_cap, sizeof(double) * (size_t)pl.partials_stride * nB))
+        return rc;
+    const int rc = grow_frame_slots(nB + 1, pl.frame_elems);
+    if (rc != DFX_OK) { // the engine goes on at its old size, on the frame slots the pyramids still hold
+        dfx_settle_frame_slots(n_frame_slots, rc, slots_held());
+        return rc;
+    }
     // commit: the geometry every launch derives its Tvl1LevelCtx from, and the control state as it is after create
     nlevels = pl.nlevels;
     for (int s = 0; s < DFX_LVL_MAX; ++s)
@@ -276,9 +229,9 @@ int Tvl1Engine::set_size(int W, int H) {
     n_planes = pl.n_planes;
     partials_stride = pl.partials_stride;
     B = nB;
-    n_frame_slots = frame_slots_held(frame_elems);
-    HIPCHK(c, hipMemset(d_state, 0, sizeof(Tvl1State) * pair_cap));
-    HIPCHK(c, hipMemset(d_work_out, 0, sizeof(long long) * pair_cap * DFX_LVL_MAX * 2));
+    dfx_settle_frame_slots(n_frame_slots, DFX_OK, slots_held());
+    HIPCHK(c, hipMemset(state.dev, 0, state.bytes(pairs.cap)));
+    HIPCHK(c, hipMemset(work_tab.dev, 0, work_tab.bytes(pairs.cap)));
     HIPCHK(c, hipMemset(d_level_done, 0, sizeof(unsigned int)));
     *h_done_flag = 0;
     done_token = 0;
@@ -290,27 +243,10 @@ int Tvl1Engine::set_size(int W, int H) {
 
 // `need` frame slots of `elems` floats per pyramid
 int Tvl1Engine::grow_frame_slots(int need, long long elems) {
-    const size_t bytes = (size_t)need * elems * sizeof(float);
-    // each pyramid by what it holds: after a failure every one of them is at least as large as it was (or gone, and then
-    // frame_slots_held() counts none)
-    if (dfx_grow_buf(c, dI, pyr_cap[0], bytes) != DFX_OK || dfx_grow_buf(c, dIx, pyr_cap[1], bytes) != DFX_OK ||
-        dfx_grow_buf(c, dIy, pyr_cap[2], bytes) != DFX_OK) {
-        n_frame_slots = std::min(n_frame_slots, frame_slots_held(frame_elems));
-        return DFX_ERR_HIP;
-    }
-    if (need > slot_ids) {
-        int *nd = nullptr, *nh = nullptr;
-        if (hipMalloc(&nd, sizeof(int) * need) != hipSuccess ||
-            hipHostMalloc(&nh, sizeof(int) * need, hipHostMallocDefault) != hipSuccess) {
-            (void)hipGetLastError();
-            dfx_free_dev(nd);
-            return dfx_fail(c, DFX_ERR_HIP, "tvl1: allocating the frame-slot tables failed");
-        }
-        dfx_free_dev(d_frame_slots);
-        dfx_free_host(h_slots_pinned);
-        d_frame_slots = nd, h_slots_pinned = nh;
-        slot_ids = need;
-    }
+    if (const int rc = dfx_grow_slot_bufs(mem, slot_bufs(elems), need))
+        return rc;
+    if (!dfx_grow_tables(mem, need, slots))
+        return dfx_fail(c, DFX_ERR_HIP, "tvl1: allocating the frame-slot tables failed");
     return DFX_OK;
 }
 
@@ -319,8 +255,7 @@ int Tvl1Engine::ensure_frame_slots(int need) {
         return DFX_OK;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     const int rc = grow_frame_slots(need, frame_elems);
-    if (rc == DFX_OK)
-        n_frame_slots = frame_slots_held(frame_elems);
+    dfx_settle_frame_slots(n_frame_slots, rc, slots_held());
     return rc;
 }
 
@@ -329,8 +264,9 @@ int Tvl1Engine::build_frames(const unsigned char *d_src, long long src_frame_str
                              const int *h_slots) {
     if (n <= 0)
         return DFX_OK;
-    std::memcpy(h_slots_pinned, h_slots, sizeof(int) * n);
-    HIPCHK(c, hipMemcpyAsync(d_frame_slots, h_slots_pinned, sizeof(int) * n, hipMemcpyHostToDevice, c->stream));
+    int *const d_frame_slots = slots.dev;
+    slots.stage(h_slots, n);
+    HIPCHK(c, hipMemcpyAsync(d_frame_slots, slots.host, slots.bytes(n), hipMemcpyHostToDevice, c->stream));
     const Level &L0 = lv[0];
     tvl1_launch_u8_to_f32(c->stream, d_src, src_frame_stride, src_pitch, d_frame_slots, n, dI, frame_elems, L0.w, L0.h,
                           L0.pitch);
@@ -363,8 +299,8 @@ Tvl1LevelCtx Tvl1Engine::level_ctx(int s, int n_pairs) const {
     x.planes = d_planes;
     x.plane_stride = plane_stride;
     x.slot_stride = slot_stride;
-    x.state = d_state;
-    x.pairs = d_pairs;
+    x.state = state.dev;
+    x.pairs = pairs.dev;
     x.partials = d_partials;
     x.partials_stride = partials_stride;
     x.n_pairs = n_pairs;
@@ -372,9 +308,9 @@ Tvl1LevelCtx Tvl1Engine::level_ctx(int s, int n_pairs) const {
     x.k = kc;
     x.thr = c->prm.tvl1_epsilon * c->prm.tvl1_epsilon * (double)(L.w * L.h);
     x.level = s;
-    x.iters_out = d_iters_out;
-    x.checks_out = d_checks_out;
-    x.work_out = d_work_out;
+    x.iters_out = iter_tab.dev;
+    x.checks_out = check_tab.dev;
+    x.work_out = work_tab.dev;
     x.level_done_count = d_level_done;
     x.host_done_flag = d_done_flag;
     x.done_token = 0;
@@ -403,8 +339,8 @@ int Tvl1Engine::run_pairs(int nb, const PairDesc *h_pairs, float *d_out, long lo
                           const DfxSeedIn *seed) {
     last_nb = 0; // the read-backs below overwrite the last batch's tables
     seed_bytes_pair = 0;
-    std::memcpy(h_pairs_pinned, h_pairs, sizeof(PairDesc) * nb);
-    HIPCHK(c, hipMemcpyAsync(d_pairs, h_pairs_pinned, sizeof(PairDesc) * nb, hipMemcpyHostToDevice, c->stream));
+    pairs.stage(h_pairs, nb);
+    HIPCHK(c, hipMemcpyAsync(pairs.dev, pairs.host, pairs.bytes(nb), hipMemcpyHostToDevice, c->stream));
     const int impl = c->prm.impl, math = c->prm.tvl1_math;
     const bool nbr_lds = (c->prm.variant & DFX_VAR_TVL1_STEP_NBR_LDS) != 0;
     const bool head_regs = (c->prm.variant & DFX_VAR_TVL1_HEAD_NBR_LDS) != 0;
@@ -498,18 +434,17 @@ int Tvl1Engine::run_pairs(int nb, const PairDesc *h_pairs, float *d_out, long lo
         }
         c->stats.kernel_launches += 1;
     }
-    HIPCHK(c, hipMemcpyAsync(h_iters, d_iters_out, sizeof(int) * nb * DFX_LVL_MAX * TVL1_MAX_WARPS,
-                             hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(h_checks, d_checks_out, sizeof(int) * nb * DFX_LVL_MAX * 2, hipMemcpyDeviceToHost,
-                             c->stream));
-    HIPCHK(c, hipMemcpyAsync(h_work, d_work_out, sizeof(long long) * nb * DFX_LVL_MAX * 2, hipMemcpyDeviceToHost,
-                             c->stream));
+    HIPCHK(c, hipMemcpyAsync(iter_tab.host, iter_tab.dev, iter_tab.bytes(nb), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(check_tab.host, check_tab.dev, check_tab.bytes(nb), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(work_tab.host, work_tab.dev, work_tab.bytes(nb), hipMemcpyDeviceToHost, c->stream));
     return DFX_OK;
 }
 
 // Fold the read-back iteration counts of a finished batch into the statistics (SURVEY.md §8d byte model).
 int Tvl1Engine::account(int nb) {
     dfx_stats &st = c->stats;
+    const int *const h_iters = iter_tab.host, *const h_checks = check_tab.host;
+    const long long *const h_work = work_tab.host;
     for (int s = 0; s < nlevels && loop.warps > 0; ++s) {
         float ms = 0.f;
         HIPCHK(c, hipEventElapsedTime(&ms, ev_lvl[s][0], ev_lvl[s][1]));
@@ -550,11 +485,9 @@ int Tvl1Engine::account(int nb) {
     }
     last_nb = nb;
     const int b = nb - 1;
-    st.levels = nlevels;
+    dfx_stats_levels(st, nlevels, [&](int s) { return std::make_pair(lv[s].w, lv[s].h); });
     st.tvl1_checks = 0;
     for (int s = 0; s < nlevels; ++s) {
-        st.level_w[s] = lv[s].w;
-        st.level_h[s] = lv[s].h;
         for (int w = 0; w < DFX_MAX_WARPS; ++w)
             st.tvl1_iters[s][w] = (w < TVL1_MAX_WARPS) ? h_iters[(b * DFX_LVL_MAX + s) * TVL1_MAX_WARPS + w] : 0;
         st.tvl1_checks += h_checks[(b * DFX_LVL_MAX + s) * 2];
@@ -570,6 +503,7 @@ int Tvl1Engine::batch_tables(int max_pairs, int *iters, int *checks) const {
     if (max_pairs < last_nb || !iters || !checks)
         return -DFX_ERR_INVALID;
     static_assert(DFX_LVL_MAX <= DFX_MAX_LEVELS && TVL1_MAX_WARPS <= DFX_MAX_WARPS, "tables do not fit dfx.h's");
+    const int *const h_iters = iter_tab.host, *const h_checks = check_tab.host;
     std::memset(iters, 0, sizeof(int) * (size_t)last_nb * DFX_MAX_LEVELS * DFX_MAX_WARPS);
     std::memset(checks, 0, sizeof(int) * (size_t)last_nb * DFX_MAX_LEVELS);
     for (int b = 0; b < last_nb; ++b)
