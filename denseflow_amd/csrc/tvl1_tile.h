@@ -6,6 +6,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "dfx_device.h"
 #include "tvl1_device_common.h"
 #include "tvl1_math.h"
@@ -78,8 +80,9 @@ __device__ __forceinline__ void sub_from_left(f2 a, f2 b, f2 &da, f2 &db) {
 // puts a canonicalising v_max_f32 per half after inline assembly (it cannot know that a difference is never a signalling
 // NaN): pk_dual<HYP, true> therefore forms max / min in assembly as well (pk_abs_max_min).
 //
-// What the loop costs now (profiles/tvl1_loop_diet/, static, interior tile, a role without skips, per iteration = 4 float2s of
-// two rows each): 550 vector instructions in k_tvl1_step_fused<true, 0> (581 before), 539 in k_tvl1_warp_head<0> (570), of
+// What the loop cost after these (profiles/tvl1_loop_diet/, static, interior tile, a role without skips, per iteration = 4
+// float2s of two rows each; since then the convergence check left the iterations that have none: TVL1_CHECK_PEEL below, 482):
+// 550 vector instructions in k_tvl1_step_fused<true, 0> (581 before), 539 in k_tvl1_warp_head<0> (570), of
 // them 332 packed and 32 with a DPP source; 17 / 16 ds_*; 108 / 121 s_nop (87 / 103).  Three reductions made the difference,
 // each bit-identical and measured alone against the parent on one MI355X (bench.py --steps 20 --warmup 5, three alternations,
 // parent 540.6 - 541.2 pairs/s): the square root inside pk_dual_denominator without its NaN guard 543.5 - 545.5 (+0.7 %), that
@@ -104,6 +107,27 @@ __device__ __forceinline__ void sub_right_minus_self(f2 a, f2 b, f2 &da, f2 &db)
     da = pk_set(r0, r1);
     db = pk_set(r2, r3);
 }
+
+// The convergence check out of the iterations that have none (profiles/tvl1_check_peel/).  Only the last iteration of a step
+// that ends a segment evaluates the error, a few of the ~120 coarsest-level steps of a headline batch; written as
+// `if (chk) { e = u - u_new; e1s = e1 * e1 + e2 * e2; }` the compiler if-converts the block and every iteration pays for it:
+// the differences, squares and sum (20 packed operations), a select per half on the wave-uniform `chk` to keep the old e1s,
+// and the float -> double conversions, additions and ownership selects of the sum itself.  With this switch the lean form's
+// loop takes one wave-uniform branch per iteration into one of two copies of the primal half: without the check (nothing of
+// the above, u updated in place) or with it; the dual half is common.  Interior loop of k_tvl1_step_fused<true, 0>, a role
+// without skips, static: 550 -> 482 vector instructions in an iteration without a check (534 with one), of them 332 -> 312
+// packed, 32 with a DPP source as before; s_nop 108 -> 127.  Against the parent on one MI355X (bench.py --steps 20 --warmup 5,
+// three alternations): 557.0 - 558.9 vs 546.6 - 549.2 pairs/s (+1.9 %), the step kernel 926 -> 904 us per launch, the same bits.
+// The register forms (LK = false) keep the one body: they have no register to spare.  Peeling whole iterations off the loop
+// (a second copy of both halves behind it) gave the step kernel 8 - 36 bytes of scratch and 55 KB of code; this form stays at
+// 128 VGPRs without scratch and at 45 KB.  0: one body, the check decided in every iteration (A/B switch for measurements).
+// Rejected with it: the four vertical-neighbour differences of a float2 as one v_sub_f32 per half in assembly instead of the
+// compiler's two v_mov_b32 + v_pk_add_f32 (16 vector instructions fewer per iteration) — alone 551.9 - 553.7, whose lowest run
+// is not above the parent's highest by the parent's spread (by 0.01 pairs/s), and alone it left the warp-and-head kernel with 68
+// bytes of nominal scratch; on top of the peel it gave 560.9 - 561.2 (+0.5 %).  Not kept.
+#ifndef TVL1_CHECK_PEEL
+#define TVL1_CHECK_PEEL 1
+#endif
 
 // The packed tile function in four phases: issue the HBM loads of a tile (raw, into registers) / turn them into the
 // tile state (mask, pack, 1/grad, LDS neighbour planes) / iterate / store the owned region.
@@ -226,8 +250,12 @@ __device__ __forceinline__ void tile_consume(const Tvl1LevelCtx &c, int x0, int 
 // n_iters inner iterations on the tile state; ends with a barrier.  Returns this thread's share of sum(diff) of the
 // last iteration when do_check.
 //   * vertical neighbours: the upper half of float2 j looks up to float2 j-1 and down to j+1, the mirrored lower
-//     half the other way round, so (p12 - p12_up) and (u_down - u) are formed per half (two scalar subtractions
-//     instead of one packed one — 4 extra instructions per float2 and iteration);
+//     half the other way round, so the subtrahend of (p12 - p12_up) and the minuend of (u_down - u) take their halves
+//     from two different float2s.  The source writes them per half; the compiler packs each back into one v_pk_add_f32
+//     with negated operands behind two v_mov_b32 that assemble the register pair (32 of the loop's 33 v_mov_b32: three
+//     instructions per difference where two v_sub_f32 would do — tried and not kept, see TVL1_CHECK_PEEL above);
+//   * the convergence check belongs to the last iteration alone: the lean form branches, once per iteration and
+//     wave-uniformly, between a primal half without it and one with it (TVL1_CHECK_PEEL);
 //   * iteration m of n only has to produce rows that the owned region [K, TH-K) can still depend on: with
 //     d = n - m iterations to go, u is needed on [K-d, TH-K+d] and p on [K-d, TH-K+d).  For the float2 whose rows are
 //     a from the edges that means: primal update iff a >= K-d-1, dual update iff a >= K-d.  Role 0 (a = 0 .. HP-1)
@@ -258,17 +286,22 @@ __device__ __forceinline__ double tile_iterate_trap(const Tvl1LevelCtx &c, TileS
     const int row_xd = a0 + HP;                // row below the upper half
     const int row_yd = min(TH - a0, TH - 1);   // row below the lower half (role 0: clamped, halo)
     double dsum = 0.0;
+    constexpr bool PEEL = LK && TVL1_CHECK_PEEL;
 #if DFX_TVL1_DEBUG == 1
     n_iters = 0;
 #endif
-    for (int it = 0; it < n_iters; ++it) {
-        const bool chk = do_check && (it == n_iters - 1);
+    // The primal half of iteration `it`.  CM says what it knows about the convergence check: 0 = this iteration has none (no
+    // difference, no square, no select; u is updated in place), 1 = it has one, 2 = decided at run time (do_check and the
+    // last iteration; the compiler if-converts that into selects on a wave-uniform condition in every iteration).
+    f2 e1s[HP]; // (declared out here, not inside the lambda: there it costs k_tvl1_step_fused_nbr_lds<1> two registers)
+    auto primal = [&](const int it, auto cm) __attribute__((always_inline)) {
+        constexpr int CM = decltype(cm)::value;
+        const bool chk = CM == 2 ? do_check && (it == n_iters - 1) : CM == 1;
         const int need = K - (n_iters - 1 - it); // rows closer than this to the edge need no dual update any more
         // ---- primal update (A.6)
         const float p12ux = bnd[0][xu][lx], p22ux = bnd[1][xu][lx];
         const float p12uy = innermost ? T.p12[HP - 1].x : bnd[0][yu][lx];
         const float p22uy = innermost ? T.p22[HP - 1].x : bnd[1][yu][lx];
-        f2 e1s[HP];
 #pragma unroll
         for (int j = 0; j < HP; ++j) {
             if (SKIPS && a0 + j < need - 1) {
@@ -345,6 +378,9 @@ __device__ __forceinline__ double tile_iterate_trap(const Tvl1LevelCtx &c, TileS
                 }
         }
         __syncthreads();
+    };
+    auto dual = [&](const int it) __attribute__((always_inline)) {
+        const int need = K - (n_iters - 1 - it);
         // ---- dual update (A.7)
         float u1dx, u2dx, u1dy, u2dy;
         if (LK) { // row a0 + HP: role + 1's first upper-half row (innermost: its own lower half); row TH - a0: role - 1's
@@ -417,6 +453,15 @@ __device__ __forceinline__ double tile_iterate_trap(const Tvl1LevelCtx &c, TileS
         bnd[0][NW + role][lx] = T.p12[0].y;
         bnd[1][NW + role][lx] = T.p22[0].y;
         __syncthreads();
+    };
+    for (int it = 0; it < n_iters; ++it) {
+        if (!PEEL)
+            primal(it, std::integral_constant<int, 2>());
+        else if (do_check && it == n_iters - 1) // one wave-uniform branch per iteration; the dual half is common
+            primal(it, std::integral_constant<int, 1>());
+        else
+            primal(it, std::integral_constant<int, 0>());
+        dual(it);
     }
     return dsum;
 }
