@@ -12,6 +12,7 @@
 #include <cstdlib>
 
 #include "brox_kernels.h"
+#include "flow_quad.h"   // dfx_planar_merge_tile
 #include "tvl1_math_pk.h" // f2, pk_fma, the exact Newton division (shared with the TVL1 kernels)
 
 #define BROX_EPS2 1e-6f

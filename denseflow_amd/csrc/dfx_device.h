@@ -272,21 +272,7 @@ __device__ __forceinline__ void dfx_planar_store2(const DfxPlanarOut &o, int i, 
     if (n == 2)
         du[1] = a1, dv[1] = c1;
 }
-// The merge kernels' planar form: a workgroup of 256 lanes covers 256 x 4 pixels, a lane four neighbouring pixels of
-// one row — 16-byte loads from the engine's u and v planes (their pitch is a multiple of 64 floats, so the four floats
-// at a multiple of 4 below w exist), and a wave writes 1 KB of one row per plane.  su / sv: the planes' first pixel.
-__device__ __forceinline__ void dfx_planar_merge_tile(const DfxPlanarOut &o, int i, const float *su, const float *sv, int w,
-                                                      int h, int pitch) {
-    const int x = ((int)blockIdx.x * 64 + ((int)threadIdx.x & 63)) * 4;
-    const int y = (int)blockIdx.y * 4 + ((int)threadIdx.x >> 6);
-    if (x >= w || y >= h)
-        return;
-    const long long s = (long long)y * pitch + x;
-    const float4 a = *reinterpret_cast<const float4 *>(su + s), c = *reinterpret_cast<const float4 *>(sv + s);
-    const float u[4] = {a.x, a.y, a.z, a.w}, v[4] = {c.x, c.y, c.z, c.w};
-    dfx_planar_store4(o, i, x, y, min(4, w - x), u, v);
-}
-static inline dim3 dfx_planar_merge_grid(int w, int h, int n) { return dim3((w + 255) / 256, (h + 3) / 4, n); }
+// (the merge kernels' planar form, dfx_planar_merge_tile / dfx_planar_merge_grid, is in flow_quad.h with the lane quad it uses)
 #ifndef DFX_XCD_REMAP
 #define DFX_XCD_REMAP 1 // 0: plain blockIdx (A/B builds, scripts/build_variant.sh)
 #endif

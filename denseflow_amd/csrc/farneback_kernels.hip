@@ -21,6 +21,7 @@
 #include <cstdlib>
 
 #include "dfx_device.h"
+#include "flow_quad.h" // dfx_planar_merge_tile
 #include "farneback_kernels.h"
 #include "farneback_plan.h"
 

@@ -19,15 +19,13 @@
 // No link is shortcut: 0 * (inf - x) is NaN and the lerp says so, at link 0 (ax = ay = 0) as anywhere.
 // tests/flow_chain_ref.py is the same text in NumPy; the two agree bit for bit (NaN for NaN).
 //
-// The shape of k_warp: 4 neighbouring pixels of a row per lane, 256 threads (4 rows of 256 pixels), grid.z the anchors.  A lane
-// keeps A and valid of its 4 pixels in registers through all L links of its chain (the loop is in the kernel, not unrolled):
-// one launch per call however long the chain, and nothing goes through HBM between links unless every link is emitted.  Link 0
+// The lane quad and the tap of flow_quad.h, grid.z the anchors.  A lane keeps A and valid of its 4 pixels in registers
+// through all L links of its chain (the loop is in the kernel, not unrolled): one launch per call however long the chain,
+// and nothing goes through HBM between links unless every link is emitted.  Link 0
 // samples the pixel itself: the lane's own 4 elements of rows y and y1 of each plane, and its 4 mask bytes, are one access
 // each (plus the one element to the right of them); every later link gathers its 4 taps per plane from global memory (the
 // displacement is unbounded: no tile to stage), the two taps of a row as one 8-byte load (FC_PAIR_TAPS; 4-byte aligned, which
-// global loads of gfx950 accept) taken at min(x0, W-2) so that it never leaves the row.  Emitted planes are one 16-byte
-// store, valid one 4-byte store, where the base and every stride of that buffer keep the alignment (fc_launch decides once per
-// launch), single elements otherwise and at the ragged right edge.  No LDS, no barrier, no scratch.
+// global loads of gfx950 accept) taken at min(x0, W-2) so that it never leaves the row.  No LDS, no barrier, no scratch.
 // Bytes per pixel and link: 8 of flow gathered where neighbouring lanes land on neighbouring taps (up to 4 sectors per plane
 // where they do not), 1 .. 4 of mask, + 8 of out + 1 of valid per emitted flow.
 #include "flow_chain_kernels.h"
@@ -35,6 +33,9 @@
 #include <algorithm>
 
 #include "dfx_device.h"
+#include "flow_quad.h"
+
+static_assert(FC_BORDER_ZERO == FQ_BORDER_ZERO && FC_BORDER_CLAMP == FQ_BORDER_CLAMP, "flow_quad.h");
 
 #ifndef FC_PAIR_TAPS
 #define FC_PAIR_TAPS 1 // 0: every tap a 4-byte load of its own (kept for profiles/flow_chain's A/B)
@@ -48,13 +49,8 @@ struct FcWide {
     int flow, occ, out, valid, pair;
 };
 
-__device__ __forceinline__ float fc_lerp(float p00, float p01, float p10, float p11, float ax, float ay) {
-    const float t = p00 + ax * (p01 - p00);
-    const float b = p10 + ax * (p11 - p10);
-    return t + ay * (b - t);
-}
-
-// r[0 .. n-1] = row[x .. x+n-1] (one access where wide and n == 4), r[4] = row[min(x+4, w-1)] where n == 4
+// r[0 .. n-1] = row[x .. x+n-1] (one access where wide and n == 4), r[4] = row[min(x+4, w-1)] where n == 4.  The quad load of
+// flow_quad.h with a fifth element and a compiler barrier that only this kernel needs: kept here, not in the shared loader.
 __device__ __forceinline__ void fc_row5(const float *row, int x, int n, int w, bool wide, float (&r)[5]) {
     if (wide && n == 4) {
         const float4 q = *reinterpret_cast<const float4 *>(row + x);
@@ -92,36 +88,26 @@ __device__ __forceinline__ void fc_taps(const float *row, int x0, int x1, int xb
 // one link of one pixel: fu the u plane of the link's flow, oc its mask
 template <bool OCC>
 __device__ __forceinline__ void fc_step(const FcArgs &a, bool pair, const float *fu, const unsigned char *oc, int xe, int y,
-                                        float wmax, float hmax, float &au, float &av, unsigned &ok) {
-    float px = (float)xe + au, py = (float)y + av;
-    // the range test comes before any conversion to int: false for NaN and for either infinity
-    const bool inside = px >= 0.0f && py >= 0.0f && px <= wmax && py <= hmax;
-    bool take = inside, good = inside;
-    if (a.border == FC_BORDER_CLAMP) {
-        take = px == px && py == py;
-        px = __builtin_fminf(__builtin_fmaxf(px, 0.0f), wmax);
-        py = __builtin_fminf(__builtin_fmaxf(py, 0.0f), hmax);
-    }
-    if (take) {
-        const float fx = floorf(px), fy = floorf(py);
-        const int x0 = (int)fx, y0 = (int)fy;
-        const float ax = px - fx, ay = py - fy;
-        const int x1 = min(x0 + 1, a.w - 1), y1 = min(y0 + 1, a.h - 1);
-        const int xb = min(x0, a.w - 2);
-        const float *r0 = fu + (long long)y0 * a.row_pitch, *r1 = fu + (long long)y1 * a.row_pitch;
+                                        float &au, float &av, unsigned &ok) {
+    const FqTap t = fq_tap((float)xe + au, (float)y + av, a.w, a.h, a.border);
+    bool good = t.inside;
+    if (t.take) {
+        const int xb = min(t.x0, a.w - 2);
+        const float *r0 = fu + (long long)t.y0 * a.row_pitch, *r1 = fu + (long long)t.y1 * a.row_pitch;
         float p00, p01, p10, p11;
-        fc_taps(r0, x0, x1, xb, pair, p00, p01);
-        fc_taps(r1, x0, x1, xb, pair, p10, p11);
-        const float su = fc_lerp(p00, p01, p10, p11, ax, ay);
-        fc_taps(r0 + a.plane_stride, x0, x1, xb, pair, p00, p01);
-        fc_taps(r1 + a.plane_stride, x0, x1, xb, pair, p10, p11);
-        const float sv = fc_lerp(p00, p01, p10, p11, ax, ay);
+        fc_taps(r0, t.x0, t.x1, xb, pair, p00, p01);
+        fc_taps(r1, t.x0, t.x1, xb, pair, p10, p11);
+        const float su = fq_lerp(p00, p01, p10, p11, t.ax, t.ay);
+        fc_taps(r0 + a.plane_stride, t.x0, t.x1, xb, pair, p00, p01);
+        fc_taps(r1 + a.plane_stride, t.x0, t.x1, xb, pair, p10, p11);
+        const float sv = fq_lerp(p00, p01, p10, p11, t.ax, t.ay);
         au = au + su;
         av = av + sv;
         if (OCC) {
-            const unsigned char *o0 = oc + (long long)y0 * a.occ_pitch, *o1 = oc + (long long)y1 * a.occ_pitch;
-            const unsigned m00 = o0[x0], m01 = o0[x1], m10 = o1[x0], m11 = o1[x1];
-            const unsigned m = m00 | (ax > 0.0f ? m01 : 0u) | (ay > 0.0f ? m10 : 0u) | (ax > 0.0f && ay > 0.0f ? m11 : 0u);
+            const unsigned char *o0 = oc + (long long)t.y0 * a.occ_pitch, *o1 = oc + (long long)t.y1 * a.occ_pitch;
+            const unsigned m00 = o0[t.x0], m01 = o0[t.x1], m10 = o1[t.x0], m11 = o1[t.x1];
+            const unsigned m =
+                m00 | (t.ax > 0.0f ? m01 : 0u) | (t.ay > 0.0f ? m10 : 0u) | (t.ax > 0.0f && t.ay > 0.0f ? m11 : 0u);
             good = good && m == 0u;
         }
     }
@@ -131,41 +117,20 @@ __device__ __forceinline__ void fc_step(const FcArgs &a, bool pair, const float 
 // the lane's n pixels of output flow o and of its valid plane
 __device__ __forceinline__ void fc_emit(const FcArgs &a, const FcWide &wide, long long o, int x, int y, int n, const float (&au)[4],
                                         const float (&av)[4], const unsigned (&ok)[4]) {
-    float *pu = a.out + o * a.out_stride + (long long)y * a.out_pitch + x;
-    float *pv = pu + a.out_plane;
-    if (wide.out && n == 4) {
-        *reinterpret_cast<float4 *>(pu) = make_float4(au[0], au[1], au[2], au[3]);
-        *reinterpret_cast<float4 *>(pv) = make_float4(av[0], av[1], av[2], av[3]);
-    } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-            if (e < n)
-                pu[e] = au[e], pv[e] = av[e];
-    }
-    if (a.valid) {
-        unsigned char *d = a.valid + o * a.valid_stride + (long long)y * a.valid_pitch + x;
-        if (wide.valid && n == 4) {
-            *reinterpret_cast<unsigned *>(d) = ok[0] | (ok[1] << 8) | (ok[2] << 16) | (ok[3] << 24);
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                if (e < n)
-                    d[e] = (unsigned char)ok[e];
-        }
-    }
+    fq_store_flow(a.out + o * a.out_stride + (long long)y * a.out_pitch + x, a.out_plane, wide.out != 0, n, au, av);
+    if (a.valid)
+        fq_store_u8(a.valid + o * a.valid_stride + (long long)y * a.valid_pitch + x, wide.valid != 0, n, ok);
 }
 
 // OCC: with occlusion masks; ALL: every link's A is emitted (FC_ALL), not only the last.  grid: (ceil(w / 256), ceil(h / 4),
 // anchors).  Eight waves per SIMD (64 registers) in every form.
 template <bool OCC, bool ALL>
 __global__ __launch_bounds__(256, 8) void k_flow_chain(FcArgs a, FcWide wide) {
-    const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
-    const int x = ((int)blockIdx.x * 64 + lane) * 4, y = (int)blockIdx.y * 4 + wave;
+    const int x = fq_x(), y = fq_y();
     if (x >= a.w || y >= a.h)
         return;
     const long long j = (long long)blockIdx.z;
-    const int n = min(4, a.w - x);
-    const float wmax = (float)(a.w - 1), hmax = (float)(a.h - 1);
+    const int n = fq_count(a.w, x);
     long long link = (long long)a.first + j * a.anchor_step; // the flow this link reads
     const long long o0 = ALL ? j * a.length : j;            // the chain's first output flow
     float au[4], av[4];
@@ -180,29 +145,16 @@ __global__ __launch_bounds__(256, 8) void k_flow_chain(FcArgs a, FcWide wide) {
         fc_row5(r1, x, n, a.w, wide.flow != 0, t1);
 #pragma unroll
         for (int e = 0; e < 4; ++e)
-            au[e] = e < n ? 0.0f + fc_lerp(t0[e], fc_right(t0, e, n), t1[e], fc_right(t1, e, n), 0.0f, 0.0f) : 0.0f;
+            au[e] = e < n ? 0.0f + fq_lerp(t0[e], fc_right(t0, e, n), t1[e], fc_right(t1, e, n), 0.0f, 0.0f) : 0.0f;
         fc_row5(r0 + a.plane_stride, x, n, a.w, wide.flow != 0, t0);
         fc_row5(r1 + a.plane_stride, x, n, a.w, wide.flow != 0, t1);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            av[e] = e < n ? 0.0f + fc_lerp(t0[e], fc_right(t0, e, n), t1[e], fc_right(t1, e, n), 0.0f, 0.0f) : 0.0f;
+            av[e] = e < n ? 0.0f + fq_lerp(t0[e], fc_right(t0, e, n), t1[e], fc_right(t1, e, n), 0.0f, 0.0f) : 0.0f;
             ok[e] = e < n ? 1u : 0u;
         }
-        if (OCC) {
-            const unsigned char *o = a.occ + link * a.occ_stride + (long long)y * a.occ_pitch + x;
-            if (wide.occ && n == 4) {
-                const unsigned m = *reinterpret_cast<const unsigned *>(o);
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    if ((m >> (8 * e)) & 0xffu)
-                        ok[e] = 0u;
-            } else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    if (e < n && o[e] != 0)
-                        ok[e] = 0u;
-            }
-        }
+        if (OCC)
+            fq_mask_clear(a.occ + link * a.occ_stride + (long long)y * a.occ_pitch + x, wide.occ != 0, n, ok);
     }
     if (ALL)
         fc_emit(a, wide, o0, x, y, n, au, av, ok);
@@ -214,7 +166,7 @@ __global__ __launch_bounds__(256, 8) void k_flow_chain(FcArgs a, FcWide wide) {
 #pragma unroll
         for (int e = 0; e < 4; ++e)
             if (e < n)
-                fc_step<OCC>(a, wide.pair != 0, fu, oc, x + e, y, wmax, hmax, au[e], av[e], ok[e]);
+                fc_step<OCC>(a, wide.pair != 0, fu, oc, x + e, y, au[e], av[e], ok[e]);
         if (ALL)
             fc_emit(a, wide, o0 + k, x, y, n, au, av, ok);
     }
@@ -224,8 +176,7 @@ __global__ __launch_bounds__(256, 8) void k_flow_chain(FcArgs a, FcWide wide) {
 
 template <bool OCC, bool ALL>
 void fc_launch_as(hipStream_t s, const FcArgs &a, const FcWide &wide) {
-    hipLaunchKernelGGL((k_flow_chain<OCC, ALL>), dim3((unsigned)((a.w + 255) / 256), (unsigned)((a.h + 3) / 4), (unsigned)a.anchors),
-                       dim3(256), 0, s, a, wide);
+    hipLaunchKernelGGL((k_flow_chain<OCC, ALL>), fq_grid(a.w, a.h, a.anchors), dim3(256), 0, s, a, wide);
 }
 
 } // namespace

@@ -3,9 +3,7 @@
 // operation rounded on its own (the build's -ffp-contract=off), / and sqrtf IEEE; tests/flow_colour_ref.py is the same text in
 // NumPy and the two agree byte for byte, and bit for bit in the squared radii.
 //
-// Two streaming passes with no host synchronisation between them, 4 neighbouring pixels of a row per lane (one 16-byte load
-// per flow plane, one 4-byte load of the mask and of each 4 frame bytes, one 4-byte store per 4 output bytes where bases and
-// strides keep that alignment; single elements otherwise and at the ragged right edge):
+// Two streaming passes with no host synchronisation between them, on the lane quad and the segments of flow_quad.h:
 //   k_flowvis_max    : the squared radius of the known pixels, reduced with integer max on the bit patterns (a known r2 is
 //                      never negative and never NaN, so the order does not matter) across the wave, the workgroup's four
 //                      waves (LDS) and then with one atomic max per workgroup into word i and one into word n.
@@ -17,6 +15,7 @@
 #include <algorithm>
 
 #include "dfx_device.h"
+#include "flow_quad.h"
 
 namespace {
 
@@ -31,36 +30,12 @@ struct FlowvisWide { // a lane's 4 elements in one access: wave-uniform
 template <bool MASKED>
 __device__ __forceinline__ void fv_fetch(const FlowvisArgs &a, const FlowvisWide &wide, long long i, int x, int y, int n,
                                          float (&u)[4], float (&v)[4], unsigned (&m)[4]) {
-    const float *fu = a.flow + i * a.flow_stride + (long long)y * a.row_pitch + x;
-    const float *fv = fu + a.plane_stride;
-    if (wide.flow && n == 4) {
-        const float4 q = *reinterpret_cast<const float4 *>(fu);
-        const float4 s = *reinterpret_cast<const float4 *>(fv);
-        u[0] = q.x, u[1] = q.y, u[2] = q.z, u[3] = q.w;
-        v[0] = s.x, v[1] = s.y, v[2] = s.z, v[3] = s.w;
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            u[k] = k < n ? fu[k] : 0.0f;
-            v[k] = k < n ? fv[k] : 0.0f;
-        }
-    }
+    fq_load_flow(a.flow + i * a.flow_stride + (long long)y * a.row_pitch + x, a.plane_stride, wide.flow != 0, n, u, v);
 #pragma unroll
     for (int k = 0; k < 4; ++k)
         m[k] = 0u;
-    if (MASKED) {
-        const unsigned char *p = a.mask + i * a.mask_stride + (long long)y * a.mask_pitch + x;
-        if (wide.mask && n == 4) {
-            const unsigned q = *reinterpret_cast<const unsigned *>(p);
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                m[k] = (q >> (8 * k)) & 0xffu;
-        } else {
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                m[k] = k < n ? p[k] : 0u;
-        }
-    }
+    if (MASKED)
+        fq_load_u8(a.mask + i * a.mask_stride + (long long)y * a.mask_pitch + x, wide.mask != 0, n, m);
 }
 
 // which of the n fetched pixels are known; unknown pixels and those beyond the row's end become (0, 0), not known — nothing
@@ -80,7 +55,7 @@ __device__ __forceinline__ void fv_classify(int n, float (&u)[4], float (&v)[4],
 template <bool MASKED>
 __global__ __launch_bounds__(256) void k_flowvis_max(FlowvisArgs a, FlowvisWide wide) {
     const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
-    const int x = ((int)blockIdx.x * 64 + lane) * 4;
+    const int x = fq_x();
     const long long i = (long long)a.i0 + (long long)blockIdx.z;
     constexpr int G = FV_MAX_ROWS / 4;
     const int n = min(4, a.w - x); // <= 0 in lanes right of the image
@@ -89,7 +64,7 @@ __global__ __launch_bounds__(256) void k_flowvis_max(FlowvisArgs a, FlowvisWide 
     // first every row's loads, then the arithmetic: the loads of all four rows are in flight at once
 #pragma unroll
     for (int g = 0; g < G; ++g) {
-        const int y = ((int)blockIdx.y * G + g) * 4 + wave;
+        const int y = fq_y(FV_MAX_ROWS, g);
 #pragma unroll
         for (int k = 0; k < 4; ++k)
             u[g][k] = v[g][k] = 0.0f, mk[g][k] = 0u;
@@ -187,30 +162,6 @@ __device__ __forceinline__ void fv_colour(float u, float v, float D, bool measur
     }
 }
 
-// m = 1 .. 4 bytes at p, one 4-byte access where wide and m == 4
-__device__ __forceinline__ void fv_get4(const unsigned char *p, bool wide, int m, unsigned (&e)[4]) {
-    if (wide && m == 4) {
-        const unsigned q = *reinterpret_cast<const unsigned *>(p);
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            e[k] = (q >> (8 * k)) & 0xffu;
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            e[k] = k < m ? p[k] : 0u;
-    }
-}
-__device__ __forceinline__ void fv_put4(unsigned char *p, bool wide, int m, const unsigned (&e)[4]) {
-    if (wide && m == 4) {
-        *reinterpret_cast<unsigned *>(p) = e[0] | (e[1] << 8) | (e[2] << 16) | (e[3] << 24);
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (k < m)
-                p[k] = (unsigned char)e[k];
-    }
-}
-
 // MASKED: with mask planes; IL: interleaved output (three planes otherwise); BLEND: over a frame.
 // grid: (ceil(w / 256), ceil(h / 4), flows).
 template <bool MASKED, bool IL, bool BLEND>
@@ -219,12 +170,11 @@ __global__ __launch_bounds__(256) void k_flowvis_colour(FlowvisArgs a, FlowvisWi
     if (threadIdx.x < 56)
         wheel[threadIdx.x] = fv_wheel_entry(threadIdx.x == 55 ? 0 : (int)threadIdx.x);
     __syncthreads();
-    const int x = ((int)blockIdx.x * 64 + ((int)threadIdx.x & 63)) * 4;
-    const int y = (int)blockIdx.y * 4 + ((int)threadIdx.x >> 6);
+    const int x = fq_x(), y = fq_y();
     if (x >= a.w || y >= a.h)
         return;
     const long long i = (long long)a.i0 + (long long)blockIdx.z;
-    const int n = min(4, a.w - x);
+    const int n = fq_count(a.w, x);
     const bool measured = a.norm != FLOWVIS_NORM_FIXED; // wave-uniform, as R is
     const float R = measured ? sqrtf(a.max2[a.norm == FLOWVIS_NORM_FLOW ? i : (long long)a.n]) : a.max_rad;
     const float D = R + 0x1p-23f;
@@ -249,7 +199,7 @@ __global__ __launch_bounds__(256) void k_flowvis_colour(FlowvisArgs a, FlowvisWi
         const unsigned char *f = a.frame + i * a.frame_image + (long long)y * a.frame_pitch;
         if (a.frame_channels == 1) {
             unsigned e[4];
-            fv_get4(f + x, wide.frame != 0, n, e);
+            fq_load_u8(f + x, wide.frame != 0, n, e);
 #pragma unroll
             for (int k = 0; k < 4; ++k)
                 fr[k][0] = fr[k][1] = fr[k][2] = e[k];
@@ -257,19 +207,19 @@ __global__ __launch_bounds__(256) void k_flowvis_colour(FlowvisArgs a, FlowvisWi
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
                 unsigned e[4];
-                fv_get4(f + c * a.frame_plane + x, wide.frame != 0, n, e);
+                fq_load_u8(f + c * a.frame_plane + x, wide.frame != 0, n, e);
 #pragma unroll
                 for (int k = 0; k < 4; ++k)
                     fr[k][c] = e[k];
             }
         } else {
 #pragma unroll
-            for (int g = 0; g < 3; ++g) { // elements 4 g .. 4 g + 3 of the lane's 12 interleaved ones
+            for (int g = 0; g < 3; ++g) { // the interleaved segments of flow_quad.h
                 unsigned e[4];
-                fv_get4(f + 3 * x + 4 * g, wide.frame != 0, min(max(3 * n - 4 * g, 0), 4), e);
+                fq_load_u8(f + fq_seg_offset<3, true>(x, g, 0), wide.frame != 0, fq_seg_count<3, true>(g, n), e);
 #pragma unroll
                 for (int k = 0; k < 4; ++k)
-                    fr[(4 * g + k) / 3][(4 * g + k) % 3] = e[k];
+                    fr[fq_seg_pixel<3, true>(g, k)][fq_seg_channel<3, true>(g, k)] = e[k];
             }
         }
         const unsigned al = (unsigned)a.alpha256;
@@ -281,14 +231,12 @@ __global__ __launch_bounds__(256) void k_flowvis_colour(FlowvisArgs a, FlowvisWi
     }
     unsigned char *d = a.out + i * a.out_image + (long long)y * a.out_pitch;
 #pragma unroll
-    for (int g = 0; g < 3; ++g) { // plane g, or elements 4 g .. 4 g + 3 of the lane's 12 interleaved ones
+    for (int g = 0; g < 3; ++g) { // the segments of flow_quad.h
         unsigned e[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            e[k] = IL ? o[(4 * g + k) / 3][(4 * g + k) % 3] : o[k][g];
-        const int m = IL ? min(max(3 * n - 4 * g, 0), 4) : n;
+        fq_segment<3, IL>(o, g, e);
+        const int m = fq_seg_count<3, IL>(g, n);
         if (m > 0)
-            fv_put4(IL ? d + 3 * x + 4 * g : d + g * a.out_plane + x, wide.out != 0, m, e);
+            fq_store_u8(d + fq_seg_offset<3, IL>(x, g, a.out_plane), wide.out != 0, m, e);
     }
 }
 
@@ -316,21 +264,20 @@ void flowvis_launch(hipStream_t s, const FlowvisArgs &args) {
         (void)hipMemsetAsync(args.max2, 0, ((size_t)args.n + 1) * sizeof(float), s);
     // grid.z holds at most 65535 flows: more than that go in several launches, every measuring launch before the first colour launch
     const int chunk = 65535;
-    const unsigned gx = (unsigned)((args.w + 255) / 256);
     for (int pass = args.max2 ? 0 : 1; pass < 2; ++pass) {
         for (int i0 = 0; i0 < args.n; i0 += chunk) {
             FlowvisArgs a = args;
             a.i0 = i0;
             const unsigned gz = (unsigned)std::min(chunk, args.n - i0);
             if (pass == 0) {
-                const dim3 grid(gx, (unsigned)((a.h + FV_MAX_ROWS - 1) / FV_MAX_ROWS), gz);
+                const dim3 grid = fq_grid(a.w, a.h, (int)gz, FV_MAX_ROWS);
                 if (a.mask)
                     hipLaunchKernelGGL((k_flowvis_max<true>), grid, dim3(256), 0, s, a, wide);
                 else
                     hipLaunchKernelGGL((k_flowvis_max<false>), grid, dim3(256), 0, s, a, wide);
                 continue;
             }
-            const dim3 grid(gx, (unsigned)((a.h + 3) / 4), gz);
+            const dim3 grid = fq_grid(a.w, a.h, (int)gz);
             if (a.mask && !a.planar)
                 flowvis_colour_as<true, true>(s, grid, a, wide);
             else if (a.mask)

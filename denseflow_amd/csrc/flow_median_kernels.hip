@@ -28,6 +28,7 @@
 #include <algorithm>
 
 #include "dfx_device.h"
+#include "flow_quad.h"
 #include "flow_median_networks.h"
 
 namespace {
@@ -188,7 +189,7 @@ __global__ __launch_bounds__(256, K == 3 ? 8 : (MASKED ? 5 : 6)) void k_flow_med
     const int x = x0 + 4 * tx, y = y0 + ty;
     if (x >= a.w || y >= a.h)
         return;
-    const int n = min(4, a.w - x);
+    const int n = fq_count(a.w, x);
 
     // per pixel: the rank to take, whether the pixel keeps its input, and its mask_out
     int rank[4];
@@ -251,29 +252,14 @@ __global__ __launch_bounds__(256, K == 3 ? 8 : (MASKED ? 5 : 6)) void k_flow_med
         }
     }
 
-    unsigned *ou = reinterpret_cast<unsigned *>(a.out) + i * a.out_stride + (long long)y * a.out_pitch + x;
-    unsigned *ov = ou + a.out_plane;
-    if (wide.out && n == 4) {
-        *reinterpret_cast<uint4 *>(ou) = make_uint4(res[0][0], res[0][1], res[0][2], res[0][3]);
-        *reinterpret_cast<uint4 *>(ov) = make_uint4(res[1][0], res[1][1], res[1][2], res[1][3]);
-    } else {
+    float ru[4], rv[4]; // the bit patterns travel as they are: no float instruction touches them
 #pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (k < n)
-                ou[k] = res[0][k], ov[k] = res[1][k];
-    }
+    for (int k = 0; k < 4; ++k)
+        ru[k] = __uint_as_float(res[0][k]), rv[k] = __uint_as_float(res[1][k]);
+    fq_store_flow(a.out + i * a.out_stride + (long long)y * a.out_pitch + x, a.out_plane, wide.out, n, ru, rv);
     if constexpr (MASKED) {
-        if (a.mask_out) {
-            unsigned char *d = a.mask_out + i * a.mask_out_stride + (long long)y * a.mask_out_pitch + x;
-            if (wide.mask_out && n == 4) {
-                *reinterpret_cast<unsigned *>(d) = mo[0] | (mo[1] << 8) | (mo[2] << 16) | (mo[3] << 24);
-            } else {
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    if (k < n)
-                        d[k] = (unsigned char)mo[k];
-            }
-        }
+        if (a.mask_out)
+            fq_store_u8(a.mask_out + i * a.mask_out_stride + (long long)y * a.mask_out_pitch + x, wide.mask_out, n, mo);
     }
 }
 

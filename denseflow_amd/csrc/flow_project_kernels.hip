@@ -31,15 +31,15 @@
 //                   tile's centre pixel lands (24 pixels to its left, 8 rows above it); a tap outside the window goes to
 //                   a global atomic as before; after a barrier the window's non-zero words are added to the workspace, lane
 //                   after lane along the window's rows (1152 contiguous bytes per row).
-//   k_fp_normalise  4 neighbouring pixels of a row per lane: their 12 words as six 16-byte loads where the workspace base is
-//                   16-byte aligned and W is even (8-byte loads otherwise), the planes as one 16-byte store each (hole: one
-//                   4-byte store) where the base and every stride of that buffer keep the alignment, single elements otherwise.
+//   k_fp_normalise  the lane quad of flow_quad.h: a lane's 12 words as six 16-byte loads where the workspace base is 16-byte
+//                   aligned and W is even (8-byte loads otherwise), the planes and the hole mask through its quad stores.
 // No float atomics anywhere.
 #include "flow_project_kernels.h"
 
 #include <algorithm>
 
 #include "dfx_device.h"
+#include "flow_quad.h"
 
 #ifndef FP_LDS_WINDOW
 #define FP_LDS_WINDOW 1 // 0: the plain global-atomic scatter (kept for profiles/flow_project's A/B)
@@ -175,14 +175,13 @@ __global__ __launch_bounds__(FP_THREADS) void k_fp_scatter(FpArgs a) {
     }
 }
 
-// grid: (ceil(w / 256), ceil(h / 4), flows of the wave)
+// grid: fq_grid(w, h, flows of the wave)
 __global__ __launch_bounds__(256) void k_fp_normalise(FpArgs a, FpWide wide) {
-    const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
-    const int x = ((int)blockIdx.x * 64 + lane) * 4, y = (int)blockIdx.y * 4 + wave;
+    const int x = fq_x(), y = fq_y();
     if (x >= a.w || y >= a.h)
         return;
     const long long f = (long long)blockIdx.z;
-    const int n = min(4, a.w - x);
+    const int n = fq_count(a.w, x);
     const u64 *p = a.work + ((f * a.h + y) * a.w + x) * FP_WORDS;
     u64 q[4 * FP_WORDS];
     if (wide.work && n == 4) {
@@ -210,41 +209,12 @@ __global__ __launch_bounds__(256) void k_fp_normalise(FpArgs a, FpWide wide) {
         oh[e] = hole ? 1u : 0u;
         oc[e] = (float)(d * 5.9604644775390625e-08); // 2^-24: the same bits as the division by 16777216.0
     }
-    if (a.out) {
-        float *pu = a.out + f * a.out_stride + (long long)y * a.out_pitch + x;
-        float *pv = pu + a.out_plane;
-        if (wide.out && n == 4) {
-            *reinterpret_cast<float4 *>(pu) = make_float4(ou[0], ou[1], ou[2], ou[3]);
-            *reinterpret_cast<float4 *>(pv) = make_float4(ov[0], ov[1], ov[2], ov[3]);
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                if (e < n)
-                    pu[e] = ou[e], pv[e] = ov[e];
-        }
-    }
-    if (a.hole) {
-        unsigned char *d = a.hole + f * a.hole_stride + (long long)y * a.hole_pitch + x;
-        if (wide.hole && n == 4) {
-            *reinterpret_cast<unsigned *>(d) = oh[0] | (oh[1] << 8) | (oh[2] << 16) | (oh[3] << 24);
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                if (e < n)
-                    d[e] = (unsigned char)oh[e];
-        }
-    }
-    if (a.cov) {
-        float *d = a.cov + f * a.cov_stride + (long long)y * a.cov_pitch + x;
-        if (wide.cov && n == 4) {
-            *reinterpret_cast<float4 *>(d) = make_float4(oc[0], oc[1], oc[2], oc[3]);
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                if (e < n)
-                    d[e] = oc[e];
-        }
-    }
+    if (a.out)
+        fq_store_flow(a.out + f * a.out_stride + (long long)y * a.out_pitch + x, a.out_plane, wide.out != 0, n, ou, ov);
+    if (a.hole)
+        fq_store_u8(a.hole + f * a.hole_stride + (long long)y * a.hole_pitch + x, wide.hole != 0, n, oh);
+    if (a.cov)
+        fq_store_f32(a.cov + f * a.cov_stride + (long long)y * a.cov_pitch + x, wide.cov != 0, n, oc);
 }
 
 template <bool IMP, bool OCC>
@@ -265,8 +235,7 @@ FpWide fp_wide(const FpArgs &args) {
 }
 
 void fp_normalise(hipStream_t s, const FpArgs &a, const FpWide &wide) {
-    hipLaunchKernelGGL(k_fp_normalise, dim3((unsigned)((a.w + 255) / 256), (unsigned)((a.h + 3) / 4), (unsigned)a.n), dim3(256), 0, s, a,
-                       wide);
+    hipLaunchKernelGGL(k_fp_normalise, fq_grid(a.w, a.h, a.n), dim3(256), 0, s, a, wide);
 }
 
 } // namespace

@@ -11,9 +11,7 @@
 // The sums are integers so that they do not depend on the order in which 272 workgroups (1080p) add them: a float
 // reduction by atomics would give another model on every run, and the inlier set of the next round with it.
 //
-// k_gm_accumulate<model, first_round> is one round.  The shape of k_warp's statistics forms: 256 threads, 4 neighbouring
-// pixels of a row per lane, 16-byte loads of u and v and a 4-byte load of the mask where the base and every stride keep that
-// alignment (gm_launch decides once per call), single elements otherwise and at the ragged right edge.  A workgroup walks a
+// k_gm_accumulate<model, first_round> is one round, on the lane quad of flow_quad.h.  A workgroup walks a
 // band of GM_BAND_ROWS rows at fixed columns, wave w the rows w, w + 4, ..: a lane's four columns never change, so it keeps
 // per column only the 32-bit count, sum of yc, sum of qu and sum of qv of its at most 8 rows (|q| <= 2^20: below 2^23), and
 // over its columns together the sums of yc^2 (32-bit: 32 terms below 2^26), yc*qu and yc*qv (64-bit, one 32 x 32 -> 64
@@ -34,6 +32,7 @@
 #include <algorithm>
 
 #include "dfx_device.h"
+#include "flow_quad.h"
 
 namespace {
 
@@ -51,39 +50,13 @@ struct GmQuad {
 
 // the 4 pixels (x .. x + 3, y) of flow i: the values and the ok test
 __device__ __forceinline__ void gm_load(const GmArgs &a, const GmWide &wide, int x, int y, long long i, GmQuad &q) {
-    const int n = min(4, a.w - x);
-    const float *fu = a.flow + i * a.flow_stride + (long long)y * a.row_pitch + x;
-    const float *fv = fu + a.plane_stride;
-    if (wide.flow && n == 4) {
-        const float4 s = *reinterpret_cast<const float4 *>(fu);
-        const float4 t = *reinterpret_cast<const float4 *>(fv);
-        q.u[0] = s.x, q.u[1] = s.y, q.u[2] = s.z, q.u[3] = s.w;
-        q.v[0] = t.x, q.v[1] = t.y, q.v[2] = t.z, q.v[3] = t.w;
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            q.u[k] = k < n ? fu[k] : 0.0f;
-            q.v[k] = k < n ? fv[k] : 0.0f;
-        }
-    }
+    const int n = fq_count(a.w, x);
+    fq_load_flow(a.flow + i * a.flow_stride + (long long)y * a.row_pitch + x, a.plane_stride, wide.flow != 0, n, q.u, q.v);
 #pragma unroll
     for (int k = 0; k < 4; ++k) // false for NaN and for either infinity
         q.ok[k] = (k < n && __builtin_fabsf(q.u[k]) < 4096.0f && __builtin_fabsf(q.v[k]) < 4096.0f) ? 1u : 0u;
-    if (a.mask) {
-        const unsigned char *m = a.mask + i * a.mask_stride + (long long)y * a.mask_pitch + x;
-        if (wide.mask && n == 4) {
-            const unsigned w4 = *reinterpret_cast<const unsigned *>(m);
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if ((w4 >> (8 * k)) & 0xffu)
-                    q.ok[k] = 0u;
-        } else {
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (k < n && m[k] != 0)
-                    q.ok[k] = 0u;
-        }
-    }
+    if (a.mask)
+        fq_mask_clear(a.mask + i * a.mask_stride + (long long)y * a.mask_pitch + x, wide.mask != 0, n, q.ok);
 }
 
 struct GmModel {
@@ -159,7 +132,7 @@ __device__ __forceinline__ void gm_close_round(dfx_gm_result *r, const long long
 template <int MODEL, bool FIRST>
 __global__ __launch_bounds__(256, 6) void k_gm_accumulate(GmArgs a, GmWide wide, int round, float tt) {
     const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
-    const int x = ((int)blockIdx.x * 64 + lane) * 4;
+    const int x = fq_x();
     const long long i = (long long)blockIdx.z;
     dfx_gm_result *res = a.result + i;
     GmModel m;
@@ -175,7 +148,7 @@ __global__ __launch_bounds__(256, 6) void k_gm_accumulate(GmArgs a, GmWide wide,
         xf[k] = (float)(2 * (x + k) - (a.w - 1));
 #pragma unroll 1
     for (int g = 0; g < GM_BAND_ROWS / 4; ++g) {
-        const int y = ((int)blockIdx.y * (GM_BAND_ROWS / 4) + g) * 4 + wave;
+        const int y = fq_y(GM_BAND_ROWS, g);
         if (x < a.w && y < a.h) {
             GmQuad q;
             gm_load(a, wide, x, y, i, q);
@@ -254,8 +227,7 @@ __global__ __launch_bounds__(256, 6) void k_gm_accumulate(GmArgs a, GmWide wide,
 
 // The flow minus the final model, and the pixels that do not follow it.  grid: (ceil(w / 256), ceil(h / 4), flows).
 __global__ __launch_bounds__(256, 8) void k_gm_apply(GmArgs a, GmWide wide, float tt) {
-    const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
-    const int x = ((int)blockIdx.x * 64 + lane) * 4, y = (int)blockIdx.y * 4 + wave;
+    const int x = fq_x(), y = fq_y();
     const long long i = (long long)blockIdx.z;
     if (x >= a.w || y >= a.h)
         return;
@@ -265,7 +237,7 @@ __global__ __launch_bounds__(256, 8) void k_gm_apply(GmArgs a, GmWide wide, floa
         m.p[j] = a.result[i].p[j];
     GmQuad q;
     gm_load(a, wide, x, y, i, q);
-    const int n = min(4, a.w - x);
+    const int n = fq_count(a.w, x);
     const float yf = (float)(2 * y - (a.h - 1));
     float ru[4], rv[4];
     unsigned mv[4];
@@ -274,30 +246,10 @@ __global__ __launch_bounds__(256, 8) void k_gm_apply(GmArgs a, GmWide wide, floa
         gm_residual(m, q.u[k], q.v[k], (float)(2 * (x + k) - (a.w - 1)), yf, ru[k], rv[k]);
         mv[k] = (q.ok[k] != 0u && ru[k] * ru[k] + rv[k] * rv[k] <= tt) ? 0u : 1u;
     }
-    if (a.out) {
-        float *ou = a.out + i * a.out_stride + (long long)y * a.out_pitch + x;
-        float *ov = ou + a.out_plane;
-        if (wide.out && n == 4) {
-            *reinterpret_cast<float4 *>(ou) = make_float4(ru[0], ru[1], ru[2], ru[3]);
-            *reinterpret_cast<float4 *>(ov) = make_float4(rv[0], rv[1], rv[2], rv[3]);
-        } else {
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (k < n)
-                    ou[k] = ru[k], ov[k] = rv[k];
-        }
-    }
-    if (a.moving) {
-        unsigned char *d = a.moving + i * a.moving_stride + (long long)y * a.moving_pitch + x;
-        if (wide.moving && n == 4) {
-            *reinterpret_cast<unsigned *>(d) = mv[0] | (mv[1] << 8) | (mv[2] << 16) | (mv[3] << 24);
-        } else {
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (k < n)
-                    d[k] = (unsigned char)mv[k];
-        }
-    }
+    if (a.out)
+        fq_store_flow(a.out + i * a.out_stride + (long long)y * a.out_pitch + x, a.out_plane, wide.out != 0, n, ru, rv);
+    if (a.moving)
+        fq_store_u8(a.moving + i * a.moving_stride + (long long)y * a.moving_pitch + x, wide.moving != 0, n, mv);
 }
 
 template <int MODEL>
@@ -327,7 +279,6 @@ void gm_launch(hipStream_t s, const GmArgs &args) {
             t = t * args.growth;
         tt[k] = t * t;
     }
-    const unsigned gx = (unsigned)((args.w + 255) / 256);
     // grid.z holds at most 65535 flows: more than that go in several launches
     const int chunk = 65535;
     for (int i0 = 0; i0 < args.n; i0 += chunk) {
@@ -341,7 +292,7 @@ void gm_launch(hipStream_t s, const GmArgs &args) {
             a.out += (long long)i0 * args.out_stride;
         if (a.moving)
             a.moving += (long long)i0 * args.moving_stride;
-        const dim3 grid(gx, (unsigned)((a.h + GM_BAND_ROWS - 1) / GM_BAND_ROWS), (unsigned)a.n);
+        const dim3 grid = fq_grid(a.w, a.h, a.n, GM_BAND_ROWS);
         for (int k = 0; k < a.rounds; ++k) {
             if (a.model == GM_TRANSLATION)
                 gm_round<GM_TRANSLATION>(s, a, wide, grid, k, tt[k]);
@@ -349,7 +300,6 @@ void gm_launch(hipStream_t s, const GmArgs &args) {
                 gm_round<GM_AFFINE>(s, a, wide, grid, k, tt[k]);
         }
         if (a.out || a.moving)
-            hipLaunchKernelGGL(k_gm_apply, dim3(gx, (unsigned)((a.h + 3) / 4), (unsigned)a.n), dim3(256), 0, s, a, wide,
-                               args.thr * args.thr);
+            hipLaunchKernelGGL(k_gm_apply, fq_grid(a.w, a.h, a.n), dim3(256), 0, s, a, wide, args.thr * args.thr);
     }
 }

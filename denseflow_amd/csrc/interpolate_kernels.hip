@@ -26,21 +26,24 @@
 // so every fill pass is one launch over 2k flows, and the synthesis reads Gf from GA or GB and Hf from H, MA or MB,
 // whichever the last pass wrote.
 //
-// k_interp_synth: the shape of k_warp — 4 neighbouring pixels of a row per lane, 256 threads over 256 x 4 pixels, grid.z
-// the pairs of the wave.  Per lane: four 16-byte loads (Gf_0, Gf_1: u and v), two 4-byte loads of H and, in the FILLED form
-// only, two of Hf; up to 8 byte taps per channel (the displacement is unbounded: no tile to stage); the pixel's own bytes
-// only where neither frame is usable; one store per output access (4 bytes of u8, 16 of float32 per segment where the base
-// and every stride of out keep that alignment, single elements otherwise and at the ragged right edge) and one of source.
+// k_interp_synth: the lane quad, the tap and the segments of flow_quad.h, grid.z the pairs of the wave.  Per lane: four
+// 16-byte loads (Gf_0, Gf_1: u and v), two 4-byte loads of H and, in the FILLED form only, two of Hf; up to 8 byte taps per
+// channel (the displacement is unbounded: no tile to stage); the pixel's own bytes only where neither frame is usable; one
+// store per output segment and one of source.
 // No LDS, no barrier, no scratch.  Bytes per pixel: 16 of flow, 2 or 4 of masks, 2 .. 8 C of taps, C x elem of out, 1 of source.
 #include "interpolate_kernels.h"
 
 #include <algorithm>
 
 #include "dfx_device.h"
+#include "flow_quad.h"
 #include "flow_median_kernels.h"
 #include "flow_project_kernels.h"
 
 namespace {
+
+static_assert(INTERP_OUT_U8 == FQ_ELEM_U8 && INTERP_OUT_F32 == DFX_ELEM_F32 && INTERP_TILE_W == 256 && INTERP_TILE_H == 4,
+              "flow_quad.h");
 
 struct IsArgs {
     const unsigned char *img0, *img1;
@@ -56,16 +59,13 @@ struct IsArgs {
     long long source_pitch, source_stride;
 };
 
-// the bilinear samples of the 4 pixels (x .. x + 3, y) of one side at p + g(p), and bit k of the result: inside
+// the bilinear samples of the 4 pixels (x .. x + 3, y) of one side at p + g(p), and bit k of the result: inside.  gu: the
+// lane's 4 elements of Gf's u plane in the workspace, where rows are padded so that they are always one access.
 template <int C, bool IL>
 __device__ __forceinline__ unsigned is_sample(const IsArgs &a, const unsigned char *img, const float *gu, int x, int y, int n,
                                               float (&s)[4][C]) {
-    constexpr int XS = IL ? C : 1;
-    const float4 q = *reinterpret_cast<const float4 *>(gu);
-    const float4 r = *reinterpret_cast<const float4 *>(gu + (long long)a.wp * a.h);
-    const float u[4] = {q.x, q.y, q.z, q.w}, v[4] = {r.x, r.y, r.z, r.w};
-    const long long cs = IL ? 1 : a.img_plane;
-    const float wmax = (float)(a.w - 1), hmax = (float)(a.h - 1);
+    float u[4], v[4];
+    fq_load_flow(gu, (long long)a.wp * a.h, true, 4, u, v);
     unsigned in = 0u;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -73,26 +73,10 @@ __device__ __forceinline__ unsigned is_sample(const IsArgs &a, const unsigned ch
         for (int c = 0; c < C; ++c)
             s[k][c] = 0.0f;
         if (k < n) {
-            const float px = (float)(x + k) + u[k], py = (float)y + v[k];
-            // the range test comes before any conversion to int: false for NaN and for either infinity
-            const bool inside = px >= 0.0f && py >= 0.0f && px <= wmax && py <= hmax;
-            if (inside) {
+            const FqTap t = fq_tap((float)(x + k) + u[k], (float)y + v[k], a.w, a.h, FQ_BORDER_ZERO);
+            if (t.inside) {
                 in |= 1u << k;
-                const float fx = floorf(px), fy = floorf(py);
-                const int x0 = (int)fx, y0 = (int)fy;
-                const float ax = px - fx, ay = py - fy;
-                const int x1 = min(x0 + 1, a.w - 1), y1 = min(y0 + 1, a.h - 1);
-                const unsigned char *r0 = img + (long long)y0 * a.img_pitch, *r1 = img + (long long)y1 * a.img_pitch;
-                const int o0 = x0 * XS, o1 = x1 * XS;
-#pragma unroll
-                for (int c = 0; c < C; ++c) {
-                    const long long co = C == 1 ? 0 : c * cs;
-                    const float p00 = (float)r0[o0 + co], p01 = (float)r0[o1 + co];
-                    const float p10 = (float)r1[o0 + co], p11 = (float)r1[o1 + co];
-                    const float tp = p00 + ax * (p01 - p00);
-                    const float bt = p10 + ax * (p11 - p10);
-                    s[k][c] = tp + ay * (bt - tp);
-                }
+                fq_sample_u8<C, IL>(img, a.img_pitch, a.img_plane, t, s[k]);
             }
         }
     }
@@ -100,27 +84,27 @@ __device__ __forceinline__ unsigned is_sample(const IsArgs &a, const unsigned ch
 }
 
 // C: channels; IL: interleaved (C == 3 only); FILLED: fill_passes > 0, the second tier exists.
-// grid: (ceil(w / 256), ceil(h / 4), pairs of the wave)
+// grid: fq_grid(w, h, pairs of the wave, INTERP_TILE_H)
 template <int C, bool IL, bool FILLED>
 __global__ __launch_bounds__(256, 4) void k_interp_synth(IsArgs a) {
     constexpr int XS = IL ? C : 1;
-    const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
-    const int x = ((int)blockIdx.x * 64 + lane) * 4, y = (int)blockIdx.y * INTERP_TILE_H + wave;
+    const int x = fq_x(), y = fq_y(INTERP_TILE_H);
     if (x >= a.w || y >= a.h)
         return;
     const long long i = (long long)blockIdx.z;
-    const int n = min(4, a.w - x);
+    const int n = fq_count(a.w, x);
     const long long pp = (long long)a.wp * a.h, at = (long long)y * a.wp + x;
     const unsigned char *i0 = a.img0 + i * a.img_image, *i1 = a.img1 + i * a.img_image;
     float s0[4][C], s1[4][C];
     const unsigned in0 = is_sample<C, IL>(a, i0, a.g + (2 * i) * 2 * pp + at, x, y, n, s0);
     const unsigned in1 = is_sample<C, IL>(a, i1, a.g + (2 * i + 1) * 2 * pp + at, x, y, n, s1);
-    const unsigned h0 = *reinterpret_cast<const unsigned *>(a.hole + (2 * i) * pp + at);
-    const unsigned h1 = *reinterpret_cast<const unsigned *>(a.hole + (2 * i + 1) * pp + at);
-    unsigned f0 = 0u, f1 = 0u;
+    // the workspace's mask planes: always one access
+    unsigned h0[4], h1[4], f0[4] = {0u, 0u, 0u, 0u}, f1[4] = {0u, 0u, 0u, 0u};
+    fq_load_u8(a.hole + (2 * i) * pp + at, true, 4, h0);
+    fq_load_u8(a.hole + (2 * i + 1) * pp + at, true, 4, h1);
     if constexpr (FILLED) {
-        f0 = *reinterpret_cast<const unsigned *>(a.fill + (2 * i) * pp + at);
-        f1 = *reinterpret_cast<const unsigned *>(a.fill + (2 * i + 1) * pp + at);
+        fq_load_u8(a.fill + (2 * i) * pp + at, true, 4, f0);
+        fq_load_u8(a.fill + (2 * i + 1) * pp + at, true, 4, f1);
     }
     const long long cs = IL ? 1 : a.img_plane;
     float o[4][C];
@@ -128,12 +112,12 @@ __global__ __launch_bounds__(256, 4) void k_interp_synth(IsArgs a) {
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         const bool ins0 = (in0 >> k) & 1u, ins1 = (in1 >> k) & 1u;
-        const bool prim0 = ((h0 >> (8 * k)) & 0xffu) == 0u && ins0, prim1 = ((h1 >> (8 * k)) & 0xffu) == 0u && ins1;
+        const bool prim0 = h0[k] == 0u && ins0, prim1 = h1[k] == 0u && ins1;
         const bool first = prim0 || prim1;
         bool w0 = prim0, w1 = prim1;
         if (FILLED && !first) {
-            w0 = ((f0 >> (8 * k)) & 0xffu) == 0u && ins0;
-            w1 = ((f1 >> (8 * k)) & 0xffu) == 0u && ins1;
+            w0 = f0[k] == 0u && ins0;
+            w1 = f1[k] == 0u && ins1;
         }
         code[k] = w0 ? (w1 ? 0u : 1u) : (w1 ? 2u : 3u);
         if (FILLED && !first && (w0 || w1))
@@ -156,64 +140,25 @@ __global__ __launch_bounds__(256, 4) void k_interp_synth(IsArgs a) {
         for (int c = 0; c < C; ++c)
             o[k][c] = __builtin_fminf(__builtin_fmaxf(o[k][c], 0.0f), 255.0f);
     }
-    if (a.source) {
-        unsigned char *d = a.source + i * a.source_stride + (long long)y * a.source_pitch + x;
-        if (a.wide_source && n == 4) {
-            *reinterpret_cast<unsigned *>(d) = code[0] | (code[1] << 8) | (code[2] << 16) | (code[3] << 24);
-        } else {
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (k < n)
-                    d[k] = (unsigned char)code[k];
-        }
-    }
+    if (a.source)
+        fq_store_u8(a.source + i * a.source_stride + (long long)y * a.source_pitch + x, a.wide_source != 0, n, code);
     if (!a.out)
         return;
-    // segment g: the lane's 4 elements of plane g (gray, planar), or elements 4 g .. 4 g + 3 of its 12 interleaved ones
 #pragma unroll
-    for (int g = 0; g < C; ++g) {
+    for (int g = 0; g < C; ++g) { // the segments of flow_quad.h
         float sv[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int k = IL ? (4 * g + e) / C : e, c = IL ? (4 * g + e) % C : g;
-            sv[e] = o[k][c];
-        }
-        const int m = IL ? min(max(C * n - 4 * g, 0), 4) : n; // elements of the segment inside the row
+        fq_segment<C, IL>(o, g, sv);
+        const int m = fq_seg_count<C, IL>(g, n);
         if (m <= 0)
             continue;
-        const long long to = i * a.out_image + (IL ? 0 : g * a.out_plane) + (long long)y * a.out_pitch + x * XS + (IL ? 4 * g : 0);
-        if (a.out_dtype == INTERP_OUT_U8) {
-            unsigned char *p = static_cast<unsigned char *>(a.out) + to;
-            unsigned q[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                q[e] = (unsigned)rintf(sv[e]);
-            if (a.wide_out && m == 4) {
-                *reinterpret_cast<unsigned *>(p) = q[0] | (q[1] << 8) | (q[2] << 16) | (q[3] << 24);
-            } else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    if (e < m)
-                        p[e] = (unsigned char)q[e];
-            }
-        } else {
-            float *p = static_cast<float *>(a.out) + to;
-            if (a.wide_out && m == 4) {
-                *reinterpret_cast<float4 *>(p) = make_float4(sv[0], sv[1], sv[2], sv[3]);
-            } else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    if (e < m)
-                        p[e] = sv[e];
-            }
-        }
+        const long long to = i * a.out_image + (long long)y * a.out_pitch + fq_seg_offset<C, IL>(x, g, a.out_plane);
+        fq_store_image(a.out, to, a.out_dtype, a.wide_out != 0, m, sv);
     }
 }
 
 template <int C, bool IL>
 void is_launch_as(hipStream_t s, const IsArgs &a, bool filled) {
-    const dim3 grid((unsigned)((a.w + INTERP_TILE_W - 1) / INTERP_TILE_W), (unsigned)((a.h + INTERP_TILE_H - 1) / INTERP_TILE_H),
-                    (unsigned)a.n);
+    const dim3 grid = fq_grid(a.w, a.h, a.n, INTERP_TILE_H);
     if (filled)
         hipLaunchKernelGGL((k_interp_synth<C, IL, true>), grid, dim3(256), 0, s, a);
     else

@@ -14,6 +14,7 @@
 #include <cstdlib>
 
 #include "dfx_device.h"
+#include "flow_quad.h" // dfx_planar_merge_tile
 #include "tvl1_kernels.h"
 #include "tvl1_math.h"
 #include "tvl1_math_pk.h"
