@@ -8,6 +8,7 @@ inside libdfx.so.  There is no CPU fallback: a missing library or GPU raises.
 Tensor consumers: FlowEngine.calc_optflows_planar (numpy) and FlowEngine.flow_tensor (torch tensors in, an
 (M, 2, H, W) float32 torch tensor out, optionally bounded to [-1, 1]); torch is imported only inside flow_tensor.
 FlowEngine.flow_colour / flow_colour_tensor draw flows as colour images on the Middlebury wheel (colour_wheel()).
+FlowEngine.flow_hist / flow_hist_tensor give the HOF / MBHx / MBHy cell histograms of flows (flow_hist_slots()).
 """
 from .engine import (  # noqa: F401
     DfxError,
@@ -20,6 +21,7 @@ from .engine import (  # noqa: F401
     build_library,
     colour_wheel,
     device_count,
+    flow_hist_slots,
     library_path,
     load_library,
 )
@@ -35,6 +37,7 @@ __all__ = [
     "build_library",
     "colour_wheel",
     "device_count",
+    "flow_hist_slots",
     "library_path",
     "load_library",
 ]

@@ -10,6 +10,7 @@
 #include "fb_check_kernels.h"
 #include "flow_chain_kernels.h"
 #include "flow_colour_kernels.h"
+#include "flow_hist_kernels.h"
 #include "flow_project_kernels.h"
 #include "flow_median_kernels.h"
 #include "global_motion_kernels.h"
@@ -1034,6 +1035,49 @@ int dfx_flow_colour_device(dfx_handle h, const dfx_colour_desc *d) {
         a.frame_image = (long long)d->frame_image_stride;
     }
     flowvis_launch(h->stream, a);
+    return post_finish(h);
+}
+
+// ---- motion descriptors of flows: HOF and MBH cell histograms (flow_hist_kernels.hip) ----
+int dfx_flow_hist_device(dfx_handle h, const dfx_hist_desc *d) {
+    int st;
+    if (!post_begin(h, d, &st))
+        return st;
+    if (!d->d_flow)
+        return dfx_fail(h, DFX_ERR_INVALID, "NULL device flows");
+    if (!d->d_sums && !d->d_out)
+        return dfx_fail(h, DFX_ERR_INVALID, "nothing asked for: d_sums and d_out are both NULL");
+    if (d->kinds < 1 || d->kinds > 7)
+        return dfx_fail(h, DFX_ERR_INVALID, "kinds must be a bit set of DFX_HIST_HOF, DFX_HIST_MBHX and DFX_HIST_MBHY: 1 .. 7");
+    if (d->bins < 2 || d->bins > FH_MAX_BINS)
+        return dfx_fail(h, DFX_ERR_INVALID, "bins must be 2 .. 16");
+    if (d->cell != 4 && d->cell != 8 && d->cell != 16 && d->cell != 32)
+        return dfx_fail(h, DFX_ERR_INVALID, "cell must be 4, 8, 16 or 32");
+    if (d->norm < DFX_HIST_NORM_NONE || d->norm > DFX_HIST_NORM_L2)
+        return dfx_fail(h, DFX_ERR_INVALID, "norm must be DFX_HIST_NORM_NONE, _L1, _L1_SQRT or _L2");
+    if (!std::isfinite(d->still_thr))
+        return dfx_fail(h, DFX_ERR_INVALID, "still_thr must be finite");
+    if (planar_strides_bad(h, d->row_pitch_floats, d->plane_stride_floats, d->flow_stride_floats))
+        return dfx_fail(h, DFX_ERR_INVALID, kPlanarStrides);
+    if (int e = plane_check(h, d->d_mask != nullptr, d->mask_pitch, d->mask_stride, "mask", "mask"))
+        return e;
+    if ((size_t)d->d_sums % 8 != 0)
+        return dfx_fail(h, DFX_ERR_INVALID, "d_sums must be 8-byte aligned");
+    const size_t cw = ((size_t)h->W + d->cell - 1) / d->cell, ch = ((size_t)h->H + d->cell - 1) / d->cell;
+    if (d->d_sums && d->sums_stride < ch * cw * (size_t)fh_slots(d->kinds, d->bins))
+        return dfx_fail(h, DFX_ERR_INVALID, "sums_stride must be at least CH * CW * D");
+    HIPCHK(h, hipSetDevice(h->device));
+    FhArgs a{};
+    a.flow = d->d_flow, a.mask = d->d_mask, a.sums = reinterpret_cast<long long *>(d->d_sums), a.out = d->d_out;
+    a.n = d->n, a.w = h->W, a.h = h->H;
+    a.row_pitch = (long long)d->row_pitch_floats, a.plane_stride = (long long)d->plane_stride_floats;
+    a.flow_stride = (long long)d->flow_stride_floats;
+    a.mask_pitch = (long long)d->mask_pitch, a.mask_stride = (long long)d->mask_stride;
+    a.sums_stride = (long long)d->sums_stride;
+    a.out_slot = (long long)d->out_slot_stride_floats, a.out_col = (long long)d->out_col_stride_floats;
+    a.out_row = (long long)d->out_row_stride_floats, a.out_flow = (long long)d->out_flow_stride_floats;
+    a.kinds = d->kinds, a.bins = d->bins, a.cell = d->cell, a.norm = d->norm, a.still_thr = d->still_thr;
+    fh_launch(h->stream, a);
     return post_finish(h);
 }
 

@@ -15,6 +15,7 @@
 #include <algorithm>
 
 #include "dfx_device.h"
+#include "flow_angle.h"
 #include "flow_quad.h"
 
 namespace {
@@ -116,28 +117,6 @@ __device__ __forceinline__ float4 fv_wheel_entry(int k) {
         r = 255, g = 0, b = 255 - 255 * (k - 49) / 6;
     }
     return make_float4((float)r / 255.0f, (float)g / 255.0f, (float)b / 255.0f, 0.0f);
-}
-
-// atan2(y, x) / pi in half-turns: the polynomial of the text, signs from the sign bits so that +-0 behave as in IEEE atan2
-__device__ __forceinline__ float fv_atan2_turns(float y, float x) {
-    const float ax = __builtin_fabsf(x), ay = __builtin_fabsf(y);
-    const float mx = __builtin_fmaxf(ax, ay), mn = __builtin_fminf(ax, ay);
-    const float t = mx > 0.0f ? mn / mx : 0.0f;
-    const float s = t * t;
-    float p = -0x1.81b21cp-7f;
-    p = p * s + 0x1.b0bae2p-5f;
-    p = p * s + -0x1.ddcd90p-4f;
-    p = p * s + 0x1.8ca306p-3f;
-    p = p * s + -0x1.54a3a4p-2f;
-    p = p * s + 0x1.fffd5cp-1f;
-    float r = t * p;
-    if (ay > ax)
-        r = 1.5707964f - r;
-    if (__float_as_uint(x) >> 31)
-        r = 3.1415927f - r;
-    if (__float_as_uint(y) >> 31)
-        r = -r;
-    return r * 0.31830987f;
 }
 
 // the RGB bytes of a known flow vector under D = R + 2^-23

@@ -340,6 +340,32 @@ class DfxColourDesc(C.Structure):
     ]
 
 
+class DfxHistDesc(C.Structure):
+    """dfx_hist_desc of include/dfx.h, field for field."""
+    _fields_ = [
+        ("d_flow", C.c_void_p),
+        ("row_pitch_floats", C.c_size_t),
+        ("plane_stride_floats", C.c_size_t),
+        ("flow_stride_floats", C.c_size_t),
+        ("n", C.c_int),
+        ("d_mask", C.c_void_p),
+        ("mask_pitch", C.c_size_t),
+        ("mask_stride", C.c_size_t),
+        ("kinds", C.c_int),
+        ("cell", C.c_int),
+        ("bins", C.c_int),
+        ("still_thr", C.c_float),
+        ("norm", C.c_int),
+        ("d_sums", C.c_void_p),
+        ("sums_stride", C.c_size_t),
+        ("d_out", C.c_void_p),
+        ("out_slot_stride_floats", C.c_size_t),
+        ("out_col_stride_floats", C.c_size_t),
+        ("out_row_stride_floats", C.c_size_t),
+        ("out_flow_stride_floats", C.c_size_t),
+    ]
+
+
 # ------------------------------------------------------------------------------------------ build
 
 def library_path() -> str:
@@ -456,6 +482,9 @@ def load_library():
     if hasattr(L, "dfx_flow_colour_device"):  # a library built before the colour coding (DFX_LIBRARY A/B) still loads
         L.dfx_flow_colour_device.argtypes = [vp, C.POINTER(DfxColourDesc)]
         L.dfx_flow_colour_device.restype = i
+    if hasattr(L, "dfx_flow_hist_device"):  # a library built before the motion descriptors (DFX_LIBRARY A/B) still loads
+        L.dfx_flow_hist_device.argtypes = [vp, C.POINTER(DfxHistDesc)]
+        L.dfx_flow_hist_device.restype = i
     if hasattr(L, "dfxi_probe_planar_value_as"):  # test hook (selftest.hip)
         L.dfxi_probe_planar_value_as.argtypes = [i, i, vp, C.c_float, vp, sz]
         L.dfxi_probe_planar_value_as.restype = i
@@ -786,6 +815,59 @@ def _colour_settings(norm, max_rad, order, layout, unknown, alpha):
     if isinstance(alpha, (bool, str)) or not isinstance(alpha, (int, float, np.integer, np.floating)) or not 0 <= alpha <= 1:
         raise ValueError("alpha must be a number in [0, 1]")
     return code, rad, SRC_ORDERS[order], lay, unk, int(round(float(alpha) * 256))
+
+
+HIST_KINDS = {"hof": 1, "mbhx": 2, "mbhy": 4}  # DFX_HIST_HOF / _MBHX / _MBHY
+HIST_NORMS = {"none": 0, "l1": 1, "l1_sqrt": 2, "l2": 3}  # DFX_HIST_NORM_*
+HIST_CELLS = (4, 8, 16, 32)
+
+
+def _hist_kinds(kinds):
+    """The bit set of a kind name or a sequence of distinct kind names."""
+    names = (kinds,) if isinstance(kinds, str) else kinds
+    try:
+        names = tuple(names)
+        ok = len(names) > 0 and all(isinstance(k, str) and k in HIST_KINDS for k in names) and len(set(names)) == len(names)
+    except TypeError:
+        ok = False
+    if not ok:
+        raise ValueError('kinds must be one or more of "hof", "mbhx", "mbhy", each once')
+    return sum(HIST_KINDS[k] for k in names)
+
+
+def _hist_bins(bins):
+    if isinstance(bins, bool) or not isinstance(bins, (int, np.integer)) or not 2 <= bins <= 16:
+        raise ValueError("bins must be an integer 2 .. 16")
+    return int(bins)
+
+
+def flow_hist_slots(kinds=("hof", "mbhx", "mbhy"), bins: int = 8):
+    """The names of the D slots of a cell in their order (dfx_flow_hist_device): "hof0" .. "hof<bins-1>", "hof_still",
+    "mbhx0" .., "mbhy0" ..; the channels lie in that order whatever the order of `kinds`."""
+    code, bins = _hist_kinds(kinds), _hist_bins(bins)
+    names = []
+    for k, bit in HIST_KINDS.items():
+        if code & bit:
+            names += [f"{k}{b}" for b in range(bins)] + (["hof_still"] if bit == 1 else [])
+    return names
+
+
+def _hist_settings(kinds, cell, bins, still_thr, norm):
+    """(kinds code, cell, bins, still_thr, norm code, D), checked as dfx_flow_hist_device checks them, before the library is
+    reached."""
+    code, bins = _hist_kinds(kinds), _hist_bins(bins)
+    if isinstance(cell, bool) or not isinstance(cell, (int, np.integer)) or cell not in HIST_CELLS:
+        raise ValueError("cell must be 4, 8, 16 or 32")
+    if isinstance(still_thr, (bool, str)) or not isinstance(still_thr, (int, float, np.integer, np.floating)):
+        raise ValueError("still_thr must be a finite number")
+    with np.errstate(over="ignore"):
+        thr = np.float32(still_thr)
+    if not np.isfinite(thr):
+        raise ValueError("still_thr must be a finite number")
+    if not isinstance(norm, str) or norm not in HIST_NORMS:
+        raise ValueError('norm must be "none", "l1", "l1_sqrt" or "l2"')
+    D = ((bins + 1) if code & 1 else 0) + (bins if code & 2 else 0) + (bins if code & 4 else 0)
+    return code, int(cell), bins, float(thr), HIST_NORMS[norm], D
 
 
 def _warp_border(border):
@@ -2244,6 +2326,90 @@ class FlowEngine:
         for k, t in enumerate(ts):
             res[:, k] = self.interpolate(clip[:m], clip[step:], fwd, bwd, t, occ_f, occ_b, fill_passes, ksize, min_weight)
         return res
+
+    # -- motion descriptors of flows: HOF and MBH cell histograms (dfx_flow_hist_device) ----
+    def flow_hist_device(self, d_flow_ptr: int, row_pitch_floats: int, plane_stride_floats: int, flow_stride_floats: int,
+                         n: int, kinds: int, cell: int, bins: int, still_thr: float, norm: int = 0,
+                         d_sums_ptr: int | None = None, sums_stride: int = 0, d_out_ptr: int | None = None,
+                         out_slot_stride_floats: int = 0, out_col_stride_floats: int = 0, out_row_stride_floats: int = 0,
+                         out_flow_stride_floats: int = 0, d_mask_ptr: int | None = None, mask_pitch: int = 0,
+                         mask_stride: int = 0):
+        """n planar float32 flows that are already in device memory, as cell histograms: the fields of dfx_hist_desc
+        (include/dfx.h) as arguments, codes and raw pointers as the header gives them."""
+        d = DfxHistDesc(d_flow_ptr, row_pitch_floats, plane_stride_floats, flow_stride_floats, int(n), d_mask_ptr, mask_pitch,
+                        mask_stride, int(kinds), int(cell), int(bins), float(still_thr), int(norm), d_sums_ptr, sums_stride,
+                        d_out_ptr, out_slot_stride_floats, out_col_stride_floats, out_row_stride_floats,
+                        out_flow_stride_floats)
+        self._check(self._L.dfx_flow_hist_device(self._h, C.byref(d)))
+
+    def flow_hist(self, flows, kinds=("hof", "mbhx", "mbhy"), cell: int = 8, bins: int = 8, still_thr: float = 0.4,
+                  norm: str = "none", mask=None, want_sums: bool = False):
+        """Motion descriptors of flows (dfx_flow_hist_device): per cell x cell pixels the orientation histogram of the flow
+        (HOF, with a slot for still pixels) and of the spatial derivatives of u and v (MBHx, MBHy), Dalal et al. 2006 and the
+        descriptors of dense trajectories.
+
+        flows: (n, 2, H, W) float32.  kinds: a name or names of "hof", "mbhx", "mbhy"; the channels lie in that order.  bins
+        2 .. 16 orientation slots per channel, bin 0 centred on +x, counter-clockwise with y down; cell 4, 8, 16 or 32.
+        still_thr: a HOF magnitude at or below it counts into the still slot (iDT's 0.4 by default; negative: never).  norm
+        "none": weights in pixels times magnitude; "l1", "l1_sqrt", "l2": per cell and channel.  mask: optional (n, H, W)
+        uint8, nonzero = not here; masked, NaN, infinite and huge (> 1e9) pixels add nothing, and neither does an MBH pixel
+        with such a neighbour.  Returns (n, D, CH, CW) float32 with CH = ceil(H / cell), CW = ceil(W / cell), the slots named
+        by flow_hist_slots(kinds, bins); with want_sums also the integer sums (n, CH, CW, D) int64 (weights times 256)."""
+        code, cell, bins, thr, ncode, D = _hist_settings(kinds, cell, bins, still_thr, norm)
+        H, W = self.height, self.width
+        fl = _np_flows(flows, H, W, lead="n")
+        n = fl.shape[0]
+        mask = _np_planes(mask, n, H, W, np.uint8, "mask", "n")
+        CH, CW = -(-H // cell), -(-W // cell)
+        out = np.zeros((n, D, CH, CW), np.float32)
+        sums = np.zeros((n, CH, CW, D), np.int64) if want_sums else None
+        if n:
+            with self._staged((fl, mask), (out, sums)) as (d_fl, d_mask, d_out, d_sums):
+                self.flow_hist_device(d_fl, W, H * W, 2 * H * W, n, code, cell, bins, thr, ncode, d_sums, CH * CW * D, d_out,
+                                      CH * CW, 1, CW, D * CH * CW, d_mask, W, H * W)
+        return (out, sums) if want_sums else out
+
+    def flow_hist_tensor(self, flows, kinds=("hof", "mbhx", "mbhy"), cell: int = 8, bins: int = 8, still_thr: float = 0.4,
+                         norm: str = "none", mask=None, want_sums: bool = False, layout: str = "chw", out=None):
+        """flow_hist for torch tensors on this handle's device, read and written where they lie.
+
+        flows: (n, 2, H, W) torch.float32 with a contiguous innermost dimension, e.g. what flow_tensor returns; every stride is
+        taken from the tensor, so a slice of a larger tensor is read without a copy.  mask: optional (n, H, W) torch.uint8.
+        layout "chw": the result is (n, D, CH, CW); "hwc": (n, CH, CW, D).  out: optional torch.float32 tensor of that shape
+        with any strides (a slice of a larger tensor is written in place); otherwise the result is allocated contiguous.
+        want_sums: also return the integer sums as an (n, CH, CW, D) torch.int64 tensor.
+
+        Torch's current stream on that device is synchronised before the call; the call returns with its device work
+        complete.  Raises ValueError before the library is reached for a wrong setting, dtype, device, shape or stride."""
+        import torch
+
+        code, cell, bins, thr, ncode, D = _hist_settings(kinds, cell, bins, still_thr, norm)
+        lay = _warp_layout(layout)
+        H, W = self.height, self.width
+        row_pitch, flow_plane, flow_stride = _flow_geometry(flows, H, W, "flows", "n")
+        n, dev = flows.shape[0], flows.device
+        mask_pitch = mask_stride = 0
+        if mask is not None:
+            mask_pitch, mask_stride = _plane_geometry(mask, n, H, W, torch.uint8, "mask", "n")
+        CH, CW = -(-H // cell), -(-W // cell)
+        shape = (n, D, CH, CW) if lay else (n, CH, CW, D)
+        if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or tuple(out.shape) != shape):
+            raise ValueError(f"out must be a torch.float32 tensor of shape {shape}")
+        self._check_devices(flows, "flows must be on this handle's device", (mask, out),
+                            "mask and out must be on the flows' device")
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=dev)
+        so = out.stride()
+        s_flow, (s_slot, s_row, s_col) = so[0], ((so[1], so[2], so[3]) if lay else (so[3], so[1], so[2]))
+        if min(so) < 0:
+            raise ValueError("out: strides must not be negative")
+        sums = torch.empty((n, CH, CW, D), dtype=torch.int64, device=dev) if want_sums else None
+        torch.cuda.current_stream(dev).synchronize()
+        if n:
+            self.flow_hist_device(flows.data_ptr(), row_pitch, flow_plane, flow_stride, n, code, cell, bins, thr, ncode,
+                                  sums.data_ptr() if want_sums else None, CH * CW * D, out.data_ptr(), s_slot, s_col, s_row,
+                                  s_flow, mask.data_ptr() if mask is not None else None, mask_pitch, mask_stride)
+        return (out, sums) if want_sums else out
 
     # -- flows as colour images: the Middlebury wheel, unknown pixels marked (dfx_flow_colour_device) ----
     def flow_colour_device(self, d_flow_ptr: int, row_pitch_floats: int, plane_stride_floats: int, flow_stride_floats: int,
