@@ -9,6 +9,7 @@ Tensor consumers: FlowEngine.calc_optflows_planar (numpy) and FlowEngine.flow_te
 (M, 2, H, W) float32 torch tensor out, optionally bounded to [-1, 1]); torch is imported only inside flow_tensor.
 FlowEngine.flow_colour / flow_colour_tensor draw flows as colour images on the Middlebury wheel (colour_wheel()).
 FlowEngine.flow_hist / flow_hist_tensor give the HOF / MBHx / MBHy cell histograms of flows (flow_hist_slots()).
+FlowEngine.splat / splat_tensor carry images and float payloads forward along a flow (the forward warp; holes marked).
 """
 from .engine import (  # noqa: F401
     DfxError,

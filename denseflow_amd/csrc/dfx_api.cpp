@@ -18,6 +18,7 @@
 #include "jpeg_kernels.h"
 #include "prepare_kernels.h"
 #include "quantize_kernels.h"
+#include "splat_kernels.h"
 #include "warp_kernels.h"
 
 namespace {
@@ -1078,6 +1079,105 @@ int dfx_flow_hist_device(dfx_handle h, const dfx_hist_desc *d) {
     a.out_row = (long long)d->out_row_stride_floats, a.out_flow = (long long)d->out_flow_stride_floats;
     a.kinds = d->kinds, a.bins = d->bins, a.cell = d->cell, a.norm = d->norm, a.still_thr = d->still_thr;
     fh_launch(h->stream, a);
+    return post_finish(h);
+}
+
+// ---- forward warp (splat) of images and float payloads along a flow (splat_kernels.hip) ----
+namespace {
+// float32 payload planes: rows of W floats, `channels` planes (more than one only), images
+bool splat_f32_strides_bad(dfx_handle h, int channels, size_t pitch, size_t plane, size_t image) {
+    if (pitch < (size_t)h->W || pitch > ((size_t)1 << 40))
+        return true;
+    if (channels > 1)
+        return plane < (size_t)h->H * pitch || plane > ((size_t)1 << 58) || image < (size_t)channels * plane;
+    return image < (size_t)h->H * pitch;
+}
+inline bool splat_channels_ok(int src_dtype, int channels) {
+    return src_dtype == DFX_WARP_U8 ? (channels == 1 || channels == 3) : (channels >= 1 && channels <= SPLAT_MAX_CHANNELS);
+}
+} // namespace
+
+size_t dfx_splat_work_bytes(dfx_handle h, int channels) {
+    if (!h || channels < 1 || channels > SPLAT_MAX_CHANNELS)
+        return 0;
+    return (size_t)h->W * (size_t)h->H * (size_t)splat_words(channels) * sizeof(unsigned long long);
+}
+
+int dfx_splat_device(dfx_handle h, const dfx_splat_desc *d) {
+    int st;
+    if (!post_begin(h, d, &st))
+        return st;
+    if (!d->d_src || !d->d_flow || !d->d_work)
+        return dfx_fail(h, DFX_ERR_INVALID, "NULL device sources, flows or workspace");
+    if (!d->d_out && !d->d_hole && !d->d_coverage)
+        return dfx_fail(h, DFX_ERR_INVALID, "one of d_out, d_hole and d_coverage is required");
+    if (!std::isfinite(d->t) || d->t == 0.0f)
+        return dfx_fail(h, DFX_ERR_INVALID, "t must be finite and nonzero");
+    if (!std::isfinite(d->min_weight) || !(d->min_weight >= 0.0f))
+        return dfx_fail(h, DFX_ERR_INVALID, "min_weight must be finite and >= 0");
+    if (d->src_dtype != DFX_WARP_U8 && d->src_dtype != DFX_PLANAR_F32)
+        return dfx_fail(h, DFX_ERR_INVALID, "src_dtype must be DFX_WARP_U8 or DFX_PLANAR_F32");
+    const bool f32 = d->src_dtype == DFX_PLANAR_F32;
+    if (!splat_channels_ok(d->src_dtype, d->channels))
+        return dfx_fail(h, DFX_ERR_INVALID, "channels must be 1 or 3 for an 8-bit source and 1 .. 4 for a float32 one");
+    if (d->channels > 1 && (f32 ? d->layout != DFX_SRC_PLANAR : (d->layout != DFX_SRC_INTERLEAVED && d->layout != DFX_SRC_PLANAR)))
+        return dfx_fail(h, DFX_ERR_INVALID, "layout must be DFX_SRC_INTERLEAVED or DFX_SRC_PLANAR; a float32 source is planar");
+    if (d->mode != DFX_SPLAT_MEAN && d->mode != DFX_SPLAT_SUM)
+        return dfx_fail(h, DFX_ERR_INVALID, "mode must be DFX_SPLAT_MEAN or DFX_SPLAT_SUM");
+    if (d->hole_mode != DFX_SPLAT_HOLE_ZERO && d->hole_mode != DFX_SPLAT_HOLE_KEEP)
+        return dfx_fail(h, DFX_ERR_INVALID, "hole_mode must be DFX_SPLAT_HOLE_ZERO or DFX_SPLAT_HOLE_KEEP");
+    if (d->out_dtype != DFX_WARP_U8 && d->out_dtype != DFX_PLANAR_F32)
+        return dfx_fail(h, DFX_ERR_INVALID, "out_dtype must be DFX_WARP_U8 or DFX_PLANAR_F32");
+    if (d->out_dtype == DFX_WARP_U8 && (f32 || d->mode != DFX_SPLAT_MEAN))
+        return dfx_fail(h, DFX_ERR_INVALID, "out_dtype DFX_WARP_U8 needs an 8-bit source and DFX_SPLAT_MEAN");
+    if (d->d_out == d->d_src)
+        return dfx_fail(h, DFX_ERR_INVALID, "a splat cannot run in place: d_out != d_src is required");
+    if ((size_t)d->d_work % 8 != 0)
+        return dfx_fail(h, DFX_ERR_INVALID, "d_work must be 8-byte aligned");
+    const size_t per_image = dfx_splat_work_bytes(h, d->channels);
+    if (d->work_bytes < per_image)
+        return dfx_fail(h, DFX_ERR_INVALID, "work_bytes must be at least dfx_splat_work_bytes");
+    const bool planes = d->channels > 1 && d->layout == DFX_SRC_PLANAR, il3 = d->channels == 3 && !planes;
+    if (f32 ? splat_f32_strides_bad(h, d->channels, d->src_pitch, d->src_plane_stride, d->src_image_stride)
+            : warp_image_strides_bad(h, il3, planes, d->src_pitch, d->src_plane_stride, d->src_image_stride))
+        return dfx_fail(h, DFX_ERR_INVALID, "sources: a pitch or stride smaller than what it spans");
+    if (planar_strides_bad(h, d->row_pitch_floats, d->plane_stride_floats, d->flow_stride_floats))
+        return dfx_fail(h, DFX_ERR_INVALID, kPlanarStrides);
+    if (int e = plane_check(h, d->d_importance != nullptr, d->importance_pitch_floats, d->importance_stride_floats, "importance",
+                            "importance", "_floats"))
+        return e;
+    if (int e = plane_check(h, d->d_occ != nullptr, d->occ_pitch, d->occ_stride, "mask", "occ"))
+        return e;
+    if (d->d_out && (f32 ? splat_f32_strides_bad(h, d->channels, d->out_pitch, d->out_plane_stride, d->out_image_stride)
+                         : warp_image_strides_bad(h, il3, planes, d->out_pitch, d->out_plane_stride, d->out_image_stride)))
+        return dfx_fail(h, DFX_ERR_INVALID, "splatted images: a pitch or stride smaller than what it spans");
+    if (int e = plane_check(h, d->d_hole != nullptr, d->hole_pitch, d->hole_stride, "hole", "hole"))
+        return e;
+    if (int e = plane_check(h, d->d_coverage != nullptr, d->coverage_pitch_floats, d->coverage_stride_floats, "coverage", "coverage",
+                            "_floats"))
+        return e;
+    HIPCHK(h, hipSetDevice(h->device));
+    SplatArgs a{};
+    a.src = d->d_src, a.flow = d->d_flow, a.imp = d->d_importance, a.occ = d->d_occ;
+    a.out = d->d_out, a.hole = d->d_hole, a.cov = d->d_coverage;
+    a.work = static_cast<unsigned long long *>(d->d_work);
+    a.n = d->n, a.w = h->W, a.h = h->H;
+    a.channels = d->channels, a.src_f32 = f32 ? 1 : 0, a.interleaved = il3 ? 1 : 0;
+    a.out_u8 = d->out_dtype == DFX_WARP_U8 ? 1 : 0, a.sum = d->mode == DFX_SPLAT_SUM ? 1 : 0;
+    a.keep = d->hole_mode == DFX_SPLAT_HOLE_KEEP ? 1 : 0;
+    a.t = d->t;
+    a.wmin = fp_wmin(d->min_weight);
+    a.src_pitch = (long long)d->src_pitch, a.src_plane = (long long)d->src_plane_stride;
+    a.src_image = (long long)d->src_image_stride;
+    a.row_pitch = (long long)d->row_pitch_floats, a.plane_stride = (long long)d->plane_stride_floats;
+    a.flow_stride = (long long)d->flow_stride_floats;
+    a.imp_pitch = (long long)d->importance_pitch_floats, a.imp_stride = (long long)d->importance_stride_floats;
+    a.occ_pitch = (long long)d->occ_pitch, a.occ_stride = (long long)d->occ_stride;
+    a.out_pitch = (long long)d->out_pitch, a.out_plane = (long long)d->out_plane_stride;
+    a.out_image = (long long)d->out_image_stride;
+    a.hole_pitch = (long long)d->hole_pitch, a.hole_stride = (long long)d->hole_stride;
+    a.cov_pitch = (long long)d->coverage_pitch_floats, a.cov_stride = (long long)d->coverage_stride_floats;
+    splat_launch(h->stream, a, (long long)(d->work_bytes / per_image));
     return post_finish(h);
 }
 

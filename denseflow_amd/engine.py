@@ -272,6 +272,47 @@ class DfxProjectDesc(C.Structure):
     ]
 
 
+class DfxSplatDesc(C.Structure):
+    """dfx_splat_desc of include/dfx.h, field for field."""
+    _fields_ = [
+        ("d_src", C.c_void_p),
+        ("src_dtype", C.c_int),
+        ("channels", C.c_int),
+        ("layout", C.c_int),
+        ("src_pitch", C.c_size_t),
+        ("src_plane_stride", C.c_size_t),
+        ("src_image_stride", C.c_size_t),
+        ("d_flow", C.c_void_p),
+        ("row_pitch_floats", C.c_size_t),
+        ("plane_stride_floats", C.c_size_t),
+        ("flow_stride_floats", C.c_size_t),
+        ("n", C.c_int),
+        ("t", C.c_float),
+        ("min_weight", C.c_float),
+        ("mode", C.c_int),
+        ("hole_mode", C.c_int),
+        ("out_dtype", C.c_int),
+        ("d_importance", C.c_void_p),
+        ("importance_pitch_floats", C.c_size_t),
+        ("importance_stride_floats", C.c_size_t),
+        ("d_occ", C.c_void_p),
+        ("occ_pitch", C.c_size_t),
+        ("occ_stride", C.c_size_t),
+        ("d_out", C.c_void_p),
+        ("out_pitch", C.c_size_t),
+        ("out_plane_stride", C.c_size_t),
+        ("out_image_stride", C.c_size_t),
+        ("d_hole", C.c_void_p),
+        ("hole_pitch", C.c_size_t),
+        ("hole_stride", C.c_size_t),
+        ("d_coverage", C.c_void_p),
+        ("coverage_pitch_floats", C.c_size_t),
+        ("coverage_stride_floats", C.c_size_t),
+        ("d_work", C.c_void_p),
+        ("work_bytes", C.c_size_t),
+    ]
+
+
 class DfxInterpDesc(C.Structure):
     """dfx_interp_desc of include/dfx.h, field for field."""
     _fields_ = [
@@ -485,6 +526,11 @@ def load_library():
     if hasattr(L, "dfx_flow_hist_device"):  # a library built before the motion descriptors (DFX_LIBRARY A/B) still loads
         L.dfx_flow_hist_device.argtypes = [vp, C.POINTER(DfxHistDesc)]
         L.dfx_flow_hist_device.restype = i
+    if hasattr(L, "dfx_splat_device"):  # a library built before the forward warp (DFX_LIBRARY A/B) still loads
+        L.dfx_splat_device.argtypes = [vp, C.POINTER(DfxSplatDesc)]
+        L.dfx_splat_device.restype = i
+        L.dfx_splat_work_bytes.argtypes = [vp, i]
+        L.dfx_splat_work_bytes.restype = sz
     if hasattr(L, "dfxi_probe_planar_value_as"):  # test hook (selftest.hip)
         L.dfxi_probe_planar_value_as.argtypes = [i, i, vp, C.c_float, vp, sz]
         L.dfxi_probe_planar_value_as.restype = i
@@ -732,6 +778,26 @@ def _project_settings(t, scale, min_weight):
     if not mw32 >= 0:
         raise ValueError("min_weight must be >= 0")
     return float(t32), float(scale32), float(mw32)
+
+
+SPLAT_MODES = {"mean": 0, "sum": 1}  # DFX_SPLAT_MEAN / DFX_SPLAT_SUM
+SPLAT_HOLES = {"zero": 0, "keep": 1}  # DFX_SPLAT_HOLE_ZERO / DFX_SPLAT_HOLE_KEEP
+SPLAT_MAX_CHANNELS = 4
+
+
+def _splat_settings(t, min_weight, mode, holes, src_u8, out_u8):
+    """(t, min_weight, mode code, hole-mode code), t and min_weight as float32 values, checked as dfx_splat_device checks
+    them, before the library is reached.  src_u8 / out_u8: whether the source and the output are 8-bit."""
+    t, _, min_weight = _project_settings(t, None, min_weight)
+    if not isinstance(mode, str) or mode not in SPLAT_MODES:
+        raise ValueError('mode must be "mean" or "sum"')
+    if not isinstance(holes, str) or holes not in SPLAT_HOLES:
+        raise ValueError('holes must be "zero" or "keep"')
+    if out_u8 and not src_u8:
+        raise ValueError("dtype uint8 needs uint8 images: a float32 payload gives float32")
+    if out_u8 and mode != "mean":
+        raise ValueError('mode "sum" needs dtype float32')
+    return t, min_weight, SPLAT_MODES[mode], SPLAT_HOLES[holes]
 
 
 INTERP_MAX_PASSES = 16
@@ -2142,6 +2208,212 @@ class FlowEngine:
                                      importance.data_ptr() if importance is not None else None, *igeom,
                                      occ.data_ptr() if occ is not None else None, *cgeom)
         return (out, hole, cov) if coverage else (out, hole)
+
+    # -- forward warp (splat) of images and float payloads along a flow (dfx_splat_device) ----
+    def splat_work_bytes(self, channels: int) -> int:
+        """The bytes of workspace one image of `channels` channels of this handle's size needs (dfx_splat_work_bytes)."""
+        return int(self._L.dfx_splat_work_bytes(self._h, int(channels)))
+
+    def splat_device(self, d_src_ptr: int, src_dtype: int, channels: int, layout: int, src_pitch: int, src_plane_stride: int,
+                     src_image_stride: int, d_flow_ptr: int, row_pitch_floats: int, plane_stride_floats: int,
+                     flow_stride_floats: int, n: int, d_work_ptr: int, work_bytes: int, t: float = 1.0,
+                     min_weight: float = 0.25, mode: int = 0, hole_mode: int = 0, out_dtype: int = PLANAR_F32,
+                     d_out_ptr: int | None = None, out_pitch: int = 0, out_plane_stride: int = 0, out_image_stride: int = 0,
+                     d_hole_ptr: int | None = None, hole_pitch: int = 0, hole_stride: int = 0,
+                     d_coverage_ptr: int | None = None, coverage_pitch_floats: int = 0, coverage_stride_floats: int = 0,
+                     d_importance_ptr: int | None = None, importance_pitch_floats: int = 0,
+                     importance_stride_floats: int = 0, d_occ_ptr: int | None = None, occ_pitch: int = 0,
+                     occ_stride: int = 0):
+        """n sources and n planar float32 flows that are already in device memory: the fields of dfx_splat_desc
+        (include/dfx.h) as arguments, codes and raw pointers as the header gives them."""
+        d = DfxSplatDesc(d_src_ptr, int(src_dtype), int(channels), int(layout), src_pitch, src_plane_stride, src_image_stride,
+                         d_flow_ptr, row_pitch_floats, plane_stride_floats, flow_stride_floats, int(n), t, min_weight,
+                         int(mode), int(hole_mode), int(out_dtype), d_importance_ptr, importance_pitch_floats,
+                         importance_stride_floats, d_occ_ptr, occ_pitch, occ_stride, d_out_ptr, out_pitch, out_plane_stride,
+                         out_image_stride, d_hole_ptr, hole_pitch, hole_stride, d_coverage_ptr, coverage_pitch_floats,
+                         coverage_stride_floats, d_work_ptr, work_bytes)
+        self._check(self._L.dfx_splat_device(self._h, C.byref(d)))
+
+    def _splat_images(self, images, layout_code):
+        """A numpy array of sources as the splat takes it: (array, channels, whether it is 8-bit).  uint8 as the warp takes
+        images; float32 (n, C, H, W) with C = 1 .. 4."""
+        a = np.asarray(images)
+        H, W = self.height, self.width
+        if a.dtype == np.float32:
+            if a.ndim != 4 or a.shape[2:] != (H, W) or not 1 <= a.shape[1] <= SPLAT_MAX_CHANNELS:
+                raise ValueError("float32 images must be (n, C, H, W) with C = 1 .. 4")
+            return np.ascontiguousarray(a), a.shape[1], False
+        if a.dtype != np.uint8:
+            raise ValueError("images must be uint8 or float32")
+        return self._warp_images(a, layout_code) + (True,)
+
+    def splat(self, images, flows, t: float = 1.0, importance=None, occ=None, mode: str = "mean", holes: str = "zero",
+              min_weight: float = 0.25, dtype=None, layout: str = "hwc", return_hole: bool = False,
+              return_coverage: bool = False, out=None):
+        """Image i carried forward along flows[i] to time t and written where it lands (dfx_splat_device): the forward warp.
+        Frame 0 with F_{0->1} gives frame 0 as seen at time t; a float32 payload (labels, depth, features) travels the same
+        way.
+
+        images: uint8, (n, H, W), (n, H, W, 3) or, with layout="chw", (n, 3, H, W); or float32 (n, C, H, W), C = 1 .. 4
+        (|v| <= 32768; a pixel with a larger or non-finite value is skipped).  flows: (n, 2, H, W) float32.  importance:
+        optional (n, H, W) float32, > 0 counts, how much a source weighs against the others landing on the same pixel (the
+        exp(alpha * z) of softmax splatting is the caller's).  occ: optional (n, H, W) uint8, nonzero = the source pixel is
+        skipped.  mode "mean": the weighted mean of what lands; "sum": the weighted sum in full-weight sources (float32
+        only; the caller normalises).  min_weight: the share of one full-weight source below which a target is a hole
+        (0.25: a choice, see include/dfx.h).  holes "zero": holes are 0; "keep": the hole pixels of `out` — required then,
+        an array of the result's shape and dtype — stay as they are (a background, or an earlier splat).  dtype: np.uint8
+        (the default for uint8 images in "mean") or np.float32.  Returns out, or (out[, hole][, coverage]): hole (n, H, W)
+        uint8 with 1 in the holes, coverage (n, H, W) float32, the summed weight in full-weight sources."""
+        l = _warp_layout(layout)
+        img, ch, src_u8 = self._splat_images(images, l)
+        if dtype is None:
+            dtype = np.uint8 if src_u8 and mode == "mean" else np.float32
+        code, np_dt = _warp_dtype(dtype)
+        if code not in (WARP_U8, PLANAR_F32):
+            raise ValueError("dtype must be np.uint8 or np.float32")
+        t, min_weight, m, hm = _splat_settings(t, min_weight, mode, holes, src_u8, code == WARP_U8)
+        n = img.shape[0]
+        H, W = self.height, self.width
+        fl = self._warp_flows(flows, n)
+        importance = _np_planes(importance, n, H, W, np.float32, "importance", "n")
+        occ = _np_planes(occ, n, H, W, np.uint8, "occ", "n")
+        if out is not None:
+            if not isinstance(out, np.ndarray) or out.dtype != np_dt or out.shape != img.shape or not out.flags.c_contiguous:
+                raise ValueError(f"out must be a contiguous {np_dt.name} array of the images' shape")
+        elif hm:
+            raise ValueError('holes="keep" needs out: the array whose hole pixels are kept')
+        else:
+            out = np.empty(img.shape, np_dt)
+        hole = np.empty((n, H, W), np.uint8) if return_hole else None
+        cov = np.empty((n, H, W), np.float32) if return_coverage else None
+        if n:
+            planes = ch > 1 and (l == 1 or not src_u8)
+            pitch = W * (1 if ch == 1 or planes else 3)
+            plane = H * W if planes else 0
+            image = ch * H * W
+            wb = self.splat_work_bytes(ch) * min(n, 8)
+            keep_in, fresh = (out, None) if hm else (None, out)  # a kept output goes up first and comes back by hand
+            with self._staged((img, fl, importance, occ, keep_in), (fresh, hole, cov), [wb]) as \
+                    (d_img, d_fl, d_imp, d_occ, d_keep, d_fresh, d_hole, d_cov, work):
+                d_out = d_keep if hm else d_fresh
+                self.splat_device(d_img, WARP_U8 if src_u8 else PLANAR_F32, ch, 1 if planes else 0, pitch, plane, image,
+                                  d_fl, W, H * W, 2 * H * W, n, work, wb, t, min_weight, m, hm, code, d_out, pitch, plane,
+                                  image, d_hole, W, H * W, d_cov, W, H * W, d_imp, W, H * W, d_occ, W, H * W)
+                if hm:
+                    self._check(self._L.dfx_memcpy_d2h(self._h, out.ctypes.data, d_out, out.nbytes))
+        res = (out,) + ((hole,) if return_hole else ()) + ((cov,) if return_coverage else ())
+        return res if len(res) > 1 else out
+
+    def _splat_tensor_payload(self, t, what):
+        """(channels, row pitch, plane stride, image stride), in floats, of a torch.float32 tensor of payload planes
+        (n, C, H, W), C = 1 .. 4, read from its strides."""
+        H, W = self.height, self.width
+        if t.dim() != 4 or tuple(t.shape[2:]) != (H, W) or not 1 <= t.shape[1] <= SPLAT_MAX_CHANNELS:
+            raise ValueError(f"{what}: float32 must be (n, C, H, W) with C = 1 .. 4")
+        n, ch = t.shape[0], t.shape[1]
+        if ch == 2:
+            return (2,) + _flow_geometry(t, H, W, what, "n")
+        st = t.stride()
+        pitch = st[2] if H > 1 else W
+        plane = st[1] if ch > 1 else H * pitch
+        image = st[0] if n > 1 else ch * plane
+        if (st[3] != 1 and W > 1) or pitch < W or plane < H * pitch or image < ch * plane:
+            raise ValueError(f"{what}: the innermost dimension must be contiguous and rows, planes and images must not overlap")
+        return ch, pitch, (plane if ch > 1 else 0), image
+
+    def splat_tensor(self, images, flows, t: float = 1.0, importance=None, occ=None, mode: str = "mean", holes: str = "zero",
+                     min_weight: float = 0.25, dtype=None, layout: str | None = None, return_hole: bool = False,
+                     return_coverage: bool = False, out=None, work=None):
+        """splat for torch tensors on this handle's device, read and written where they lie.
+
+        images: torch.uint8, (n, H, W), (n, 3, H, W) or (n, H, W, 3) — the memory layout, interleaved or three planes, and
+        every stride are taken from the tensor, so the NCHW view of an NHWC batch or a slice of a larger tensor is read
+        without a copy (layout is needed only for H = W = 3) — or torch.float32 (n, C, H, W), C = 1 .. 4, with a contiguous
+        innermost dimension.  flows: (n, 2, H, W) torch.float32.  importance: optional (n, H, W) torch.float32; occ: optional
+        (n, H, W) torch.uint8.  dtype: torch.uint8 (the default for uint8 images in "mean") or torch.float32.  out: optional
+        tensor of that dtype and the images' shape that lies in memory as the images do, not `images` itself; required for
+        holes="keep", whose hole pixels it keeps.  work: optional contiguous tensor of any dtype to use as the workspace,
+        8-byte aligned and at least splat_work_bytes(C) large (more takes more images per wave of launches); without it one
+        for min(n, 8) images is allocated through torch.  Returns out, or (out[, hole][, coverage]).
+
+        Torch's current stream on that device is synchronised before the call; the call returns with its device work
+        complete.  Raises ValueError before the library is reached for a wrong setting, dtype, device, shape or stride."""
+        import torch
+
+        if layout is not None:
+            _warp_layout(layout)
+        if not isinstance(images, torch.Tensor) or images.dtype not in (torch.uint8, torch.float32):
+            raise ValueError("images must be a torch.uint8 or torch.float32 tensor")
+        src_u8 = images.dtype == torch.uint8
+        tdt = (torch.uint8 if src_u8 and mode == "mean" else torch.float32) if dtype is None else dtype
+        if tdt not in (torch.uint8, torch.float32):
+            raise ValueError("dtype must be torch.uint8 or torch.float32")
+        t, min_weight, m, hm = _splat_settings(t, min_weight, mode, holes, src_u8, tdt == torch.uint8)
+        H, W = self.height, self.width
+
+        def geometry(x, what):
+            if src_u8:
+                return self._warp_tensor_images(x, layout, what)
+            ch, pitch, plane, image = self._splat_tensor_payload(x, what)
+            return ch, (1 if ch > 1 else 0), pitch, plane, image, True
+
+        ch, mem, pitch, plane, image, chw = geometry(images, "images")
+        n, dev = images.shape[0], images.device
+        fgeom = _flow_geometry(flows, H, W, "flows", "n", n, ", one flow per image")
+        igeom = cgeom = (0, 0)
+        if importance is not None:
+            igeom = _plane_geometry(importance, n, H, W, torch.float32, "importance", "n", "planes")
+        if occ is not None:
+            cgeom = _plane_geometry(occ, n, H, W, torch.uint8, "occ", "n", "planes")
+        if out is not None:
+            if not isinstance(out, torch.Tensor) or out.dtype != tdt or out.shape != images.shape:
+                raise ValueError(f"out must be a {tdt} tensor of the images' shape")
+            och, omem, out_pitch, out_plane, out_image, _ = geometry(out, "out")
+            if (och, omem) != (ch, mem):
+                raise ValueError("out must lie in memory as the images do (interleaved or planar)")
+            if out.data_ptr() == images.data_ptr() and n:
+                raise ValueError("out must not be images: a splat cannot run in place")
+        elif hm:
+            raise ValueError('holes="keep" needs out: the tensor whose hole pixels are kept')
+        per = (1 + ch) * 8 * H * W
+        if work is not None:
+            if not isinstance(work, torch.Tensor) or not work.is_contiguous():
+                raise ValueError("work must be a contiguous torch tensor")
+            work_bytes = work.numel() * work.element_size()
+            if work_bytes < per:
+                raise ValueError(f"work must hold at least {per} bytes (splat_work_bytes)")
+        self._check_devices(images, "images must be on this handle's device", (flows, importance, occ, out, work),
+                            "flows, importance, occ, out and work must be on the images' device")
+        if work is not None and work.data_ptr() % 8 != 0:
+            raise ValueError("work must be 8-byte aligned")
+        if out is None:
+            if ch == 3 and mem == 0:  # interleaved memory, whatever the shape's order
+                base = torch.empty((n, H, W, 3), dtype=tdt, device=dev)
+                out = base.permute(0, 3, 1, 2) if chw else base
+                out_pitch, out_plane, out_image = 3 * W, 0, 3 * H * W
+            elif src_u8 and ch == 3:
+                base = torch.empty((n, 3, H, W), dtype=tdt, device=dev)
+                out = base if chw else base.permute(0, 2, 3, 1)
+                out_pitch, out_plane, out_image = W, H * W, 3 * H * W
+            else:
+                out = torch.empty(tuple(images.shape), dtype=tdt, device=dev)
+                out_pitch, out_plane, out_image = W, (H * W if ch > 1 else 0), ch * H * W
+        hole = torch.empty((n, H, W), dtype=torch.uint8, device=dev) if return_hole else None
+        cov = torch.empty((n, H, W), dtype=torch.float32, device=dev) if return_coverage else None
+        if n:
+            if work is None:
+                work = torch.empty((per * min(n, 8) // 8,), dtype=torch.int64, device=dev)
+                work_bytes = work.numel() * 8
+            torch.cuda.current_stream(dev).synchronize()
+            self.splat_device(images.data_ptr(), WARP_U8 if src_u8 else PLANAR_F32, ch, mem, pitch, plane, image,
+                              flows.data_ptr(), *fgeom, n, work.data_ptr(), work_bytes, t, min_weight, m, hm,
+                              WARP_U8 if tdt == torch.uint8 else PLANAR_F32, out.data_ptr(), out_pitch, out_plane, out_image,
+                              hole.data_ptr() if return_hole else None, W, H * W,
+                              cov.data_ptr() if return_coverage else None, W, H * W,
+                              importance.data_ptr() if importance is not None else None, *igeom,
+                              occ.data_ptr() if occ is not None else None, *cgeom)
+        res = (out,) + ((hole,) if return_hole else ()) + ((cov,) if return_coverage else ())
+        return res if len(res) > 1 else out
 
     # -- frame interpolation at time t from two frames and their flows (dfx_interpolate_device) ----
     def interpolate_work_bytes(self, fill_passes: int = 3) -> int:
