@@ -1348,7 +1348,8 @@ int dfx_encode_jpeg(dfx_handle h, const uint8_t *const *planes, size_t pitch, in
         return rc;
     const size_t plane = (size_t)h->W * h->H;
     // a staging set holds 2 * img_slots planes back to back (after dfx_set_size possibly more than the encoder is sized for)
-    const int chunk_max = 2 * std::min(h->img_slots, h->jpeg.slots);
+    // and a launch takes at most DFX_GRID_YZ_MAX planes in grid.y
+    const int chunk_max = (int)std::min<long long>(2ll * std::min(h->img_slots, h->jpeg.slots), DFX_GRID_YZ_MAX);
     for (int i0 = 0; i0 < n; i0 += chunk_max) {
         const int nc = std::min(chunk_max, n - i0);
         for (int j = 0; j < nc; ++j)

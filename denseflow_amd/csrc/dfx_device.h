@@ -16,6 +16,10 @@
 
 #define DFX_LVL_MAX 16
 
+// The most workgroups a launch takes along grid.y or grid.z.  A launcher that puts a caller's count of items (flows, frames,
+// planes) there walks the batch in launches of at most this many and offsets every per-item pointer by the launch's first item.
+constexpr int DFX_GRID_YZ_MAX = 65535;
+
 enum : int {
     PL_U1_0 = 0, PL_U2_0, PL_U1_1, PL_U2_1,                // u sets 0/1
     PL_P11_0, PL_P12_0, PL_P21_0, PL_P22_0,                // p set 0

@@ -143,7 +143,7 @@ int ensure_colour(dfx_context *c, int frames, int quality, int sw, int sh) {
 int extract_body(dfx_context *c, const uint8_t *const *frames, size_t pitch, int sw, int sh, int n, int quality,
                  uint8_t *const *jpg, size_t cap, uint32_t *sizes, uint64_t *ticket) {
     auto &j = c->colour;
-    const int B = std::min(frames_batch(c), std::max(n, 1));
+    const int B = std::min({frames_batch(c), std::max(n, 1), DFX_GRID_YZ_MAX}); // a batch's frames lie in grid.z
     int rc = ensure_colour(c, std::max(B, j.slots), quality, sw, sh);
     if (rc != DFX_OK)
         return rc;

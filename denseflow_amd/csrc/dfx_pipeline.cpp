@@ -767,6 +767,8 @@ int dfx_ensure_jpeg(dfx_context *c, int pairs, int quality) {
 
 int dfx_launch_jpeg(dfx_context *c, int q, int n_planes, int n_x, int y_first) {
     const auto &j = c->jpeg;
+    if (n_planes > DFX_GRID_YZ_MAX) // they lie in grid.y
+        return dfx_fail(c, DFX_ERR_INVALID, "JPEG: more than 65535 planes in one batch");
     JpegCtx jc;
     jc.planes = c->d_img[q];
     jc.plane_stride = (long long)c->W * c->H;

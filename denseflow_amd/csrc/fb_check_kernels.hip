@@ -85,8 +85,8 @@ void fb_check_launch(hipStream_t s, const FbCheckArgs &args) {
         occ_bits |= (unsigned long long)(size_t)args.dir[d].occ;
     }
     const int vec_occ = (occ_bits & 3) == 0 ? 4 : 1;
-    // grid.z holds at most 65535 planes: more flows than that go in several launches
-    const int chunk = 65535 / dirs;
+    // grid.z holds at most FQ_ITEMS_MAX = 65535 planes: more flows than that go in several launches
+    const int chunk = FQ_ITEMS_MAX / dirs;
     for (int i0 = 0; i0 < args.n; i0 += chunk) {
         FbCheckArgs a = args;
         a.dirs = dirs;

@@ -192,8 +192,8 @@ void fc_launch(hipStream_t s, const FcArgs &args) {
     wide.out = dfx_planar_vec(args.out, args.out_stride, args.out_plane, args.out_pitch) == 4;
     wide.valid = dfx_bytes4(args.valid, args.valid_pitch, args.valid_stride);
     wide.pair = FC_PAIR_TAPS && args.w >= 2;
-    // grid.z holds at most 65535 anchors: more than that go in several launches
-    const int chunk = 65535;
+    // grid.z holds at most FQ_ITEMS_MAX = 65535 anchors: more than that go in several launches
+    const int chunk = FQ_ITEMS_MAX;
     const long long per = all ? args.length : 1; // output flows per anchor
     for (int j0 = 0; j0 < args.anchors; j0 += chunk) {
         FcArgs a = args;

@@ -241,8 +241,8 @@ void flowvis_launch(hipStream_t s, const FlowvisArgs &args) {
                             args.frame_channels == 3 && args.frame_planar ? args.frame_plane : 0);
     if (args.max2)
         (void)hipMemsetAsync(args.max2, 0, ((size_t)args.n + 1) * sizeof(float), s);
-    // grid.z holds at most 65535 flows: more than that go in several launches, every measuring launch before the first colour launch
-    const int chunk = 65535;
+    // grid.z holds at most FQ_ITEMS_MAX = 65535 flows: more than that go in several launches, every measuring launch before the first colour launch
+    const int chunk = FQ_ITEMS_MAX;
     for (int pass = args.max2 ? 0 : 1; pass < 2; ++pass) {
         for (int i0 = 0; i0 < args.n; i0 += chunk) {
             FlowvisArgs a = args;

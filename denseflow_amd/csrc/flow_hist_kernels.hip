@@ -307,8 +307,8 @@ void fh_launch(hipStream_t s, const FhArgs &args) {
     a.wide_flow = dfx_planar_vec(a.flow, a.flow_stride, a.plane_stride, a.row_pitch) == 4;
     a.wide_mask = dfx_bytes4(a.mask, a.mask_pitch, a.mask_stride, 0);
     const dim3 grid0((unsigned)((a.w + 255) / 256), (unsigned)((a.ch + a.bands - 1) / a.bands), 1);
-    // grid.z holds at most 65535 flows: more than that go in several launches
-    const int chunk = 65535;
+    // grid.z holds at most FQ_ITEMS_MAX = 65535 flows: more than that go in several launches
+    const int chunk = FQ_ITEMS_MAX;
     for (int i0 = 0; i0 < args.n; i0 += chunk) {
         a.i0 = i0;
         const dim3 grid(grid0.x, grid0.y, (unsigned)std::min(chunk, args.n - i0));

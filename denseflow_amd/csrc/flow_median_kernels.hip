@@ -283,8 +283,8 @@ void fm_launch(hipStream_t s, const FmArgs &args) {
     wide.mask = dfx_bytes4(args.mask, args.mask_pitch, args.mask_stride);
     wide.out = dfx_planar_vec(args.out, args.out_stride, args.out_plane, args.out_pitch) == 4;
     wide.mask_out = dfx_bytes4(args.mask_out, args.mask_out_pitch, args.mask_out_stride);
-    // grid.z holds at most 65535 flows: more than that go in several launches
-    const int chunk = 65535;
+    // grid.z holds at most FQ_ITEMS_MAX = 65535 flows: more than that go in several launches
+    const int chunk = FQ_ITEMS_MAX;
     for (int i0 = 0; i0 < args.n; i0 += chunk) {
         FmArgs a = args;
         a.n = std::min(chunk, args.n - i0);

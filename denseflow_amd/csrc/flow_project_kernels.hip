@@ -241,7 +241,7 @@ void fp_normalise(hipStream_t s, const FpArgs &a, const FpWide &wide) {
 } // namespace
 
 void fp_renormalise(hipStream_t s, const FpArgs &args) {
-    if (args.n <= 0 || args.n > 65535 || args.w <= 0 || args.h <= 0)
+    if (args.n <= 0 || args.n > FQ_ITEMS_MAX || args.w <= 0 || args.h <= 0)
         return;
     fp_normalise(s, args, fp_wide(args));
 }
@@ -251,7 +251,7 @@ void fp_launch(hipStream_t s, const FpArgs &args, long long flows_per_wave) {
         return;
     const FpWide wide = fp_wide(args);
     const long long per_flow = (long long)args.w * args.h * FP_WORDS; // words
-    const int chunk = (int)std::min<long long>(flows_per_wave, 65535);  // grid.z holds at most 65535 flows
+    const int chunk = (int)std::min<long long>(flows_per_wave, FQ_ITEMS_MAX);  // grid.z holds at most FQ_ITEMS_MAX = 65535 flows
     for (int i0 = 0; i0 < args.n; i0 += chunk) {
         FpArgs a = args;
         a.n = std::min(chunk, args.n - i0);

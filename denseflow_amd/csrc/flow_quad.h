@@ -119,6 +119,9 @@ DFX_HD void fq_segment(const T (&s)[4][C], int g, T (&seg)[4]) {
 __device__ __forceinline__ int fq_x() { return ((int)blockIdx.x * 64 + ((int)threadIdx.x & 63)) * 4; }
 __device__ __forceinline__ int fq_y(int rows = 4, int g = 0) { return (int)blockIdx.y * rows + 4 * g + ((int)threadIdx.x >> 6); }
 __device__ __forceinline__ int fq_count(int w, int x) { return min(4, w - x); }
+// grid.z holds the items of one launch, at most FQ_ITEMS_MAX (dfx_device.h's DFX_GRID_YZ_MAX): a launcher walks a larger
+// batch in several launches.
+constexpr int FQ_ITEMS_MAX = DFX_GRID_YZ_MAX;
 static inline dim3 fq_grid(int w, int h, int n, int rows = 4) {
     return dim3((unsigned)((w + 255) / 256), (unsigned)((h + rows - 1) / rows), (unsigned)n);
 }

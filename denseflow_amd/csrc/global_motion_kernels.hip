@@ -279,8 +279,8 @@ void gm_launch(hipStream_t s, const GmArgs &args) {
             t = t * args.growth;
         tt[k] = t * t;
     }
-    // grid.z holds at most 65535 flows: more than that go in several launches
-    const int chunk = 65535;
+    // grid.z holds at most FQ_ITEMS_MAX = 65535 flows: more than that go in several launches
+    const int chunk = FQ_ITEMS_MAX;
     for (int i0 = 0; i0 < args.n; i0 += chunk) {
         GmArgs a = args;
         a.n = std::min(chunk, args.n - i0);

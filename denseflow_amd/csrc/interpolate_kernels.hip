@@ -197,8 +197,8 @@ void interp_launch(hipStream_t s, const InterpArgs &args) {
     const size_t per_pair = interp_work_bytes(args.w, args.h, args.fill_passes);
     if (args.n <= 0 || per_pair == 0 || args.work_bytes < per_pair)
         return;
-    // grid.z holds at most 65535 flows: a wave's 2k flows go in one launch of every pass
-    const int k = (int)std::min<size_t>(std::min<size_t>((size_t)args.n, args.work_bytes / per_pair), 32767);
+    // grid.z holds at most FQ_ITEMS_MAX = 65535 flows: a wave's 2k flows go in one launch of every pass
+    const int k = (int)std::min<size_t>(std::min<size_t>((size_t)args.n, args.work_bytes / per_pair), FQ_ITEMS_MAX / 2);
     const int w = args.w, h = args.h;
     const long long wp = (w + 3) & ~3, pp = wp * h;
     const InterpLayout l = interp_layout(w, h, args.fill_passes, (size_t)k);

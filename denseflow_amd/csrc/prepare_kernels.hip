@@ -16,6 +16,10 @@
 // read once per destination pixel, 1-3 B/px of source + 1 B/px written: HBM-bound, tiny next to the flow).
 #include "prepare_kernels.h"
 
+#include <algorithm>
+
+#include "dfx_device.h"
+
 namespace {
 
 // gray value of pixel x of a row.  The source format is a template parameter, so that the B, G, R interleaved form stays the
@@ -186,14 +190,18 @@ void prepare_launch(hipStream_t s, const unsigned char *d_src, long long src_pit
         return;
     // cv::resize: inv_scale = dsize / ssize (double), scale = 1 / inv_scale
     const double scale_x = 1.0 / ((double)dw / (double)sw), scale_y = 1.0 / ((double)dh / (double)sh);
-    const dim3 grid((dw + 63) / 64, (dh + 3) / 4, n);
     const int mode = prepare_mode(sw, sh, dw, dh);
     const bool swap = channels == 3 && rgb, pl = channels == 3 && planar;
     const long long ch = pl ? (plane_stride ? plane_stride : src_pitch * sh) : 1;
     auto k = pl ? (swap ? k_prepare_frames<true, true> : k_prepare_frames<false, true>)
                 : (swap ? k_prepare_frames<true, false> : k_prepare_frames<false, false>);
-    hipLaunchKernelGGL(k, grid, dim3(256), 0, s, d_src, src_pitch, src_frame_stride, sw, sh, channels, ch, d_dst, dst_pitch,
-                       dst_frame_stride, dw, dh, scale_x, scale_y, mode);
+    // grid.z holds at most DFX_GRID_YZ_MAX frames: more than that go in several launches
+    const int chunk = DFX_GRID_YZ_MAX;
+    for (int i0 = 0; i0 < n; i0 += chunk) {
+        const dim3 grid((dw + 63) / 64, (dh + 3) / 4, std::min(chunk, n - i0));
+        hipLaunchKernelGGL(k, grid, dim3(256), 0, s, d_src + i0 * src_frame_stride, src_pitch, src_frame_stride, sw, sh, channels,
+                           ch, d_dst + i0 * dst_frame_stride, dst_pitch, dst_frame_stride, dw, dh, scale_x, scale_y, mode);
+    }
 }
 
 void prepare_bgr_launch(hipStream_t s, const unsigned char *d_src, long long src_pitch, long long src_frame_stride, int sw,
@@ -202,7 +210,11 @@ void prepare_bgr_launch(hipStream_t s, const unsigned char *d_src, long long src
     if (n <= 0)
         return;
     const double scale_x = 1.0 / ((double)dw / (double)sw), scale_y = 1.0 / ((double)dh / (double)sh);
-    const dim3 grid(((dw + 3) / 4 + 63) / 64, (dh + 3) / 4, n);
-    hipLaunchKernelGGL(k_prepare_bgr, grid, dim3(256), 0, s, d_src, src_pitch, src_frame_stride, sw, sh, d_dst, dst_pitch,
-                       dst_frame_stride, dw, dh, scale_x, scale_y, prepare_mode(sw, sh, dw, dh));
+    const int chunk = DFX_GRID_YZ_MAX; // as in prepare_launch
+    for (int i0 = 0; i0 < n; i0 += chunk) {
+        const dim3 grid(((dw + 3) / 4 + 63) / 64, (dh + 3) / 4, std::min(chunk, n - i0));
+        hipLaunchKernelGGL(k_prepare_bgr, grid, dim3(256), 0, s, d_src + i0 * src_frame_stride, src_pitch, src_frame_stride, sw, sh,
+                           d_dst + i0 * dst_frame_stride, dst_pitch, dst_frame_stride, dw, dh, scale_x, scale_y,
+                           prepare_mode(sw, sh, dw, dh));
+    }
 }

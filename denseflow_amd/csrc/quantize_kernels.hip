@@ -11,6 +11,8 @@
 // two 4-byte stores per lane -> full 64-lane coalescing).
 #include "quantize_kernels.h"
 
+#include "dfx_device.h"
+
 #include <algorithm>
 
 namespace {
@@ -205,22 +207,32 @@ void quant_launch_flow_to_png_planes(hipStream_t s, const float *d_flows, long l
     unsigned *mm = reinterpret_cast<unsigned *>(d_scratch);
     PngScale *scale = reinterpret_cast<PngScale *>(mm + 4 * (size_t)n);
     const long long n_px = (long long)w * h;
-    hipLaunchKernelGGL(k_png_minmax_init, dim3((4 * n + 255) / 256), dim3(256), 0, s, mm, n);
+    // the keys, bounds and scales of all n flows lie in grid.x; grid.z holds at most DFX_GRID_YZ_MAX flows: more than that
+    // go in several launches, each on its own flows, keys, scales and planes
+    const int chunk = DFX_GRID_YZ_MAX;
+    hipLaunchKernelGGL(k_png_minmax_init, dim3((unsigned)((4 * (long long)n + 255) / 256)), dim3(256), 0, s, mm, n);
     // enough workgroups per flow to fill the device at small batches, few enough that the atomics do not matter
     const int per_flow = (int)std::max<long long>(1, std::min<long long>(256, n_px / (256 * 16)));
-    hipLaunchKernelGGL(k_png_minmax, dim3(per_flow, 1, n), dim3(256), 0, s, d_flows, flow_stride, n_px, mm);
+    for (int i0 = 0; i0 < n; i0 += chunk)
+        hipLaunchKernelGGL(k_png_minmax, dim3(per_flow, 1, std::min(chunk, n - i0)), dim3(256), 0, s,
+                           d_flows + (size_t)i0 * flow_stride, flow_stride, n_px, mm + 4 * (size_t)i0);
     hipLaunchKernelGGL(k_png_bounds, dim3((n + 63) / 64), dim3(64), 0, s, mm, n, w, h, d_bounds, scale);
-    const dim3 grid((w + 255) / 256, (h + 3) / 4, n);
-    hipLaunchKernelGGL(k_flow_to_png_planes, grid, dim3(256), 0, s, d_flows, flow_stride, w, h, scale, d_img_x, d_img_y,
-                       img_pitch, img_stride);
+    for (int i0 = 0; i0 < n; i0 += chunk) {
+        const dim3 grid((w + 255) / 256, (h + 3) / 4, std::min(chunk, n - i0));
+        hipLaunchKernelGGL(k_flow_to_png_planes, grid, dim3(256), 0, s, d_flows + (size_t)i0 * flow_stride, flow_stride, w, h,
+                           scale + i0, d_img_x + (size_t)i0 * img_stride, d_img_y + (size_t)i0 * img_stride, img_pitch,
+                           img_stride);
+    }
 }
 
 void quant_launch_flow_to_u8(hipStream_t s, const float *d_flows, long long flow_stride, int n, int w, int h,
                              double lo, double hi, unsigned char *d_img_x, unsigned char *d_img_y,
                              long long img_pitch, long long img_stride) {
-    if (n <= 0)
-        return;
-    const dim3 grid((w + 255) / 256, (h + 3) / 4, n);
-    hipLaunchKernelGGL(k_flow_to_u8, grid, dim3(256), 0, s, d_flows, flow_stride, w, h, lo, hi, d_img_x, d_img_y,
-                       img_pitch, img_stride);
+    // grid.z holds at most DFX_GRID_YZ_MAX flows: more than that go in several launches
+    const int chunk = DFX_GRID_YZ_MAX;
+    for (int i0 = 0; i0 < n; i0 += chunk) {
+        const dim3 grid((w + 255) / 256, (h + 3) / 4, std::min(chunk, n - i0));
+        hipLaunchKernelGGL(k_flow_to_u8, grid, dim3(256), 0, s, d_flows + (size_t)i0 * flow_stride, flow_stride, w, h, lo, hi,
+                           d_img_x + (size_t)i0 * img_stride, d_img_y + (size_t)i0 * img_stride, img_pitch, img_stride);
+    }
 }

@@ -333,7 +333,7 @@ void splat_launch(hipStream_t s, const SplatArgs &args, long long images_per_wav
         return;
     const SplatWide wide = sp_wide(args);
     const long long per_image = (long long)args.w * args.h * splat_words(args.channels); // words
-    const int chunk = (int)std::min<long long>(images_per_wave, 65535);                   // grid.z holds at most 65535 images
+    const int chunk = (int)std::min<long long>(images_per_wave, FQ_ITEMS_MAX);                   // grid.z holds at most FQ_ITEMS_MAX = 65535 images
     const long long src_bytes = args.src_f32 ? 4 : 1, out_bytes = args.out_u8 ? 1 : 4;
     for (int i0 = 0; i0 < args.n; i0 += chunk) {
         SplatArgs a = args;

@@ -186,8 +186,8 @@ void warp_launch(hipStream_t s, const WarpArgs &args) {
     wide.valid = dfx_bytes4(args.valid, args.valid_pitch, args.valid_stride, 0);
     if (args.stats)
         (void)hipMemsetAsync(args.stats, 0, (size_t)args.n * 2 * sizeof(unsigned long long), s);
-    // grid.z holds at most 65535 images: more than that go in several launches
-    const int chunk = 65535;
+    // grid.z holds at most FQ_ITEMS_MAX = 65535 images: more than that go in several launches
+    const int chunk = FQ_ITEMS_MAX;
     for (int i0 = 0; i0 < args.n; i0 += chunk) {
         WarpArgs a = args;
         a.n = std::min(chunk, args.n - i0);
