@@ -10,6 +10,7 @@ Tensor consumers: FlowEngine.calc_optflows_planar (numpy) and FlowEngine.flow_te
 FlowEngine.flow_colour / flow_colour_tensor draw flows as colour images on the Middlebury wheel (colour_wheel()).
 FlowEngine.flow_hist / flow_hist_tensor give the HOF / MBHx / MBHy cell histograms of flows (flow_hist_slots()).
 FlowEngine.splat / splat_tensor carry images and float payloads forward along a flow (the forward warp; holes marked).
+FlowEngine.warp_planes / warp_planes_tensor gather float, half and label planes backward along a flow (any channel count).
 """
 from .engine import (  # noqa: F401
     DfxError,

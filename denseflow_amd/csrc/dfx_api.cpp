@@ -16,6 +16,7 @@
 #include "global_motion_kernels.h"
 #include "interpolate_kernels.h"
 #include "jpeg_kernels.h"
+#include "plane_warp_kernels.h"
 #include "prepare_kernels.h"
 #include "quantize_kernels.h"
 #include "splat_kernels.h"
@@ -1178,6 +1179,77 @@ int dfx_splat_device(dfx_handle h, const dfx_splat_desc *d) {
     a.hole_pitch = (long long)d->hole_pitch, a.hole_stride = (long long)d->hole_stride;
     a.cov_pitch = (long long)d->coverage_pitch_floats, a.cov_stride = (long long)d->coverage_stride_floats;
     splat_launch(h->stream, a, (long long)(d->work_bytes / per_image));
+    return post_finish(h);
+}
+
+// ---- backward warp of float, half and label planes along a flow (plane_warp_kernels.hip) ----
+namespace {
+// rows of W (planar) or C W (interleaved) elements, C planes where planar with several channels, images
+bool warp_planes_strides_bad(dfx_handle h, int channels, bool interleaved, size_t pitch, size_t plane, size_t image) {
+    const size_t row = (size_t)h->W * (interleaved ? (size_t)channels : 1);
+    if (pitch < row || pitch > ((size_t)1 << 40))
+        return true;
+    if (!interleaved && channels > 1)
+        return plane < (size_t)h->H * pitch || plane > ((size_t)1 << 58) || image / (size_t)channels < plane;
+    return image < (size_t)h->H * pitch;
+}
+} // namespace
+
+int dfx_warp_planes_device(dfx_handle h, const dfx_warp_planes_desc *d) {
+    int st;
+    if (!post_begin(h, d, &st))
+        return st;
+    if (!d->d_src || !d->d_flow)
+        return dfx_fail(h, DFX_ERR_INVALID, "NULL device planes or flows");
+    if (!d->d_out && !d->d_valid)
+        return dfx_fail(h, DFX_ERR_INVALID, "nothing asked for: d_out and d_valid are both NULL");
+    if (d->channels < 1)
+        return dfx_fail(h, DFX_ERR_INVALID, "channels must be >= 1");
+    if (d->layout != DFX_SRC_INTERLEAVED && d->layout != DFX_SRC_PLANAR)
+        return dfx_fail(h, DFX_ERR_INVALID, "layout must be DFX_SRC_INTERLEAVED or DFX_SRC_PLANAR");
+    if (d->border != DFX_WARP_BORDER_ZERO && d->border != DFX_WARP_BORDER_CLAMP)
+        return dfx_fail(h, DFX_ERR_INVALID, "border must be DFX_WARP_BORDER_ZERO or DFX_WARP_BORDER_CLAMP");
+    if (d->sample != DFX_SAMPLE_BILINEAR && d->sample != DFX_SAMPLE_NEAREST)
+        return dfx_fail(h, DFX_ERR_INVALID, "sample must be DFX_SAMPLE_BILINEAR or DFX_SAMPLE_NEAREST");
+    if (d->invalid != DFX_WARP_INVALID_ZERO && d->invalid != DFX_WARP_INVALID_KEEP)
+        return dfx_fail(h, DFX_ERR_INVALID, "invalid must be DFX_WARP_INVALID_ZERO or DFX_WARP_INVALID_KEEP");
+    if (d->src_dtype < DFX_PLANAR_F32 || d->src_dtype > DFX_WARP_U8 || d->out_dtype < DFX_PLANAR_F32 || d->out_dtype > DFX_WARP_U8)
+        return dfx_fail(h, DFX_ERR_INVALID, "src_dtype and out_dtype must be DFX_PLANAR_F32, DFX_PLANAR_F16, DFX_PLANAR_BF16 or DFX_WARP_U8");
+    if (d->sample == DFX_SAMPLE_BILINEAR && (d->src_dtype == DFX_WARP_U8 || d->out_dtype == DFX_WARP_U8))
+        return dfx_fail(h, DFX_ERR_INVALID, "DFX_SAMPLE_BILINEAR takes and gives float32, float16 or bfloat16 (8-bit images: dfx_warp_device)");
+    if (d->sample == DFX_SAMPLE_NEAREST && d->out_dtype != d->src_dtype)
+        return dfx_fail(h, DFX_ERR_INVALID, "DFX_SAMPLE_NEAREST copies elements: out_dtype == src_dtype is required");
+    if (d->invalid == DFX_WARP_INVALID_KEEP && !d->d_out)
+        return dfx_fail(h, DFX_ERR_INVALID, "DFX_WARP_INVALID_KEEP needs d_out");
+    if (d->d_out == d->d_src)
+        return dfx_fail(h, DFX_ERR_INVALID, "a warp cannot run in place: d_out != d_src is required");
+    const bool il = d->layout == DFX_SRC_INTERLEAVED;
+    if (warp_planes_strides_bad(h, d->channels, il, d->src_pitch, d->src_plane_stride, d->src_image_stride))
+        return dfx_fail(h, DFX_ERR_INVALID, "source planes: a pitch or stride smaller than what it spans");
+    if (planar_strides_bad(h, d->row_pitch_floats, d->plane_stride_floats, d->flow_stride_floats))
+        return dfx_fail(h, DFX_ERR_INVALID, kPlanarStrides);
+    if (d->d_out && warp_planes_strides_bad(h, d->channels, il, d->out_pitch, d->out_plane_stride, d->out_image_stride))
+        return dfx_fail(h, DFX_ERR_INVALID, "warped planes: a pitch or stride smaller than what it spans");
+    if (int e = plane_check(h, d->d_occ != nullptr, d->occ_pitch, d->occ_stride, "mask", "occ"))
+        return e;
+    if (int e = plane_check(h, d->d_valid != nullptr, d->valid_pitch, d->valid_stride, "valid", "valid"))
+        return e;
+    HIPCHK(h, hipSetDevice(h->device));
+    PwArgs a{};
+    a.src = d->d_src, a.flow = d->d_flow, a.out = d->d_out, a.occ = d->d_occ, a.valid = d->d_valid;
+    a.n = d->n, a.w = h->W, a.h = h->H;
+    a.channels = d->channels, a.planar = il ? 0 : 1, a.border = d->border, a.sample = d->sample;
+    a.keep = d->invalid == DFX_WARP_INVALID_KEEP ? 1 : 0;
+    a.src_dtype = d->src_dtype, a.out_dtype = d->out_dtype;
+    a.src_pitch = (long long)d->src_pitch, a.src_plane = d->channels > 1 ? (long long)d->src_plane_stride : 0;
+    a.src_image = (long long)d->src_image_stride;
+    a.row_pitch = (long long)d->row_pitch_floats, a.plane_stride = (long long)d->plane_stride_floats;
+    a.flow_stride = (long long)d->flow_stride_floats;
+    a.out_pitch = (long long)d->out_pitch, a.out_plane = d->channels > 1 ? (long long)d->out_plane_stride : 0;
+    a.out_image = (long long)d->out_image_stride;
+    a.occ_pitch = (long long)d->occ_pitch, a.occ_stride = (long long)d->occ_stride;
+    a.valid_pitch = (long long)d->valid_pitch, a.valid_stride = (long long)d->valid_stride;
+    pw_launch(h->stream, a);
     return post_finish(h);
 }
 

@@ -112,6 +112,72 @@ DFX_HD void fq_segment(const T (&s)[4][C], int g, T (&seg)[4]) {
         seg[e] = s[fq_seg_pixel<C, IL>(g, e)][fq_seg_channel<C, IL>(g, e)];
 }
 
+// ------------------------------------------------------------------------------------------------
+// Typed planes (plane_warp_kernels.hip): the nearest position, the exact half -> float conversions, a typed tap load.
+// The nearest pixel of position (px, py): the range test, take and the clamp of fq_tap, word for word, then rintf (ties to
+// even) of each coordinate.  A taken position lies in [0, W-1] x [0, H-1] before it is rounded, so xn, yn are in range; one
+// that is not taken is (0, 0), as in fq_tap.
+struct FqNear {
+    bool inside, take;
+    int xn, yn;
+};
+DFX_HD FqNear fq_nearest(float px, float py, int w, int h, int border) {
+    const float wmax = (float)(w - 1), hmax = (float)(h - 1);
+    FqNear t;
+    t.inside = px >= 0.0f && py >= 0.0f && px <= wmax && py <= hmax;
+    t.take = t.inside;
+    if (border == FQ_BORDER_CLAMP) {
+        t.take = px == px && py == py;
+        px = __builtin_fminf(__builtin_fmaxf(px, 0.0f), wmax);
+        py = __builtin_fminf(__builtin_fmaxf(py, 0.0f), hmax);
+    }
+    px = t.take ? px : 0.0f;
+    py = t.take ? py : 0.0f;
+    t.xn = (int)__builtin_rintf(px), t.yn = (int)__builtin_rintf(py);
+    return t;
+}
+
+// float16 bits as float32, exactly: subnormals are kept (value = mantissa * 2^-24), infinities and NaNs keep their sign and
+// the payload in the upper mantissa bits.  On the device it is the compiler's conversion; the integer form is what a host
+// compiler without a 16-bit float type builds, and the two agree on all 65536 patterns.
+DFX_HD float fq_f16_to_f32(unsigned short b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return (float)__builtin_bit_cast(_Float16, b);
+#else
+    const unsigned sign = ((unsigned)b & 0x8000u) << 16, e = ((unsigned)b >> 10) & 0x1fu, m = (unsigned)b & 0x3ffu;
+    unsigned bits;
+    if (e == 0x1fu)
+        bits = sign | 0x7f800000u | (m << 13);
+    else if (e != 0u)
+        bits = sign | ((e + 112u) << 23) | (m << 13);
+    else { // zero or a subnormal: m * 2^-24 is exact in float32
+        const float v = (float)m * 5.9604644775390625e-08f;
+        return sign ? -v : v;
+    }
+    return __builtin_bit_cast(float, bits);
+#endif
+}
+// bfloat16 bits as float32: the upper half
+DFX_HD float fq_bf16_to_f32(unsigned short b) { return __builtin_bit_cast(float, (unsigned)b << 16); }
+
+// element `at` of a plane of dtype DFX_ELEM_F32 / _F16 / _BF16 as float32, exactly
+template <int ELEM>
+DFX_HD float fq_load_elem(const void *p, long long at) {
+    if constexpr (ELEM == DFX_ELEM_F32)
+        return static_cast<const float *>(p)[at];
+    else if constexpr (ELEM == DFX_ELEM_F16)
+        return fq_f16_to_f32(static_cast<const unsigned short *>(p)[at]);
+    else
+        return fq_bf16_to_f32(static_cast<const unsigned short *>(p)[at]);
+}
+// the bilinear sample of a typed plane at a taken tap (pitch: elements between rows)
+template <int ELEM>
+DFX_HD float fq_sample_elem(const void *p, long long pitch, const FqTap &t) {
+    const long long r0 = (long long)t.y0 * pitch, r1 = (long long)t.y1 * pitch;
+    return fq_lerp(fq_load_elem<ELEM>(p, r0 + t.x0), fq_load_elem<ELEM>(p, r0 + t.x1), fq_load_elem<ELEM>(p, r1 + t.x0),
+                   fq_load_elem<ELEM>(p, r1 + t.x1), t.ax, t.ay);
+}
+
 #if defined(__HIPCC__)
 // ------------------------------------------------------------------------------------------------
 // Geometry: 256 threads, grid fq_grid(w, h, images, rows).  A kernel whose workgroup walks more than 4 rows calls fq_y once

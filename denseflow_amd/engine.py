@@ -313,6 +313,38 @@ class DfxSplatDesc(C.Structure):
     ]
 
 
+class DfxWarpPlanesDesc(C.Structure):
+    """dfx_warp_planes_desc of include/dfx.h, field for field."""
+    _fields_ = [
+        ("d_src", C.c_void_p),
+        ("src_dtype", C.c_int),
+        ("channels", C.c_int),
+        ("layout", C.c_int),
+        ("src_pitch", C.c_size_t),
+        ("src_plane_stride", C.c_size_t),
+        ("src_image_stride", C.c_size_t),
+        ("d_flow", C.c_void_p),
+        ("row_pitch_floats", C.c_size_t),
+        ("plane_stride_floats", C.c_size_t),
+        ("flow_stride_floats", C.c_size_t),
+        ("n", C.c_int),
+        ("border", C.c_int),
+        ("sample", C.c_int),
+        ("invalid", C.c_int),
+        ("out_dtype", C.c_int),
+        ("d_out", C.c_void_p),
+        ("out_pitch", C.c_size_t),
+        ("out_plane_stride", C.c_size_t),
+        ("out_image_stride", C.c_size_t),
+        ("d_occ", C.c_void_p),
+        ("occ_pitch", C.c_size_t),
+        ("occ_stride", C.c_size_t),
+        ("d_valid", C.c_void_p),
+        ("valid_pitch", C.c_size_t),
+        ("valid_stride", C.c_size_t),
+    ]
+
+
 class DfxInterpDesc(C.Structure):
     """dfx_interp_desc of include/dfx.h, field for field."""
     _fields_ = [
@@ -526,6 +558,9 @@ def load_library():
     if hasattr(L, "dfx_flow_hist_device"):  # a library built before the motion descriptors (DFX_LIBRARY A/B) still loads
         L.dfx_flow_hist_device.argtypes = [vp, C.POINTER(DfxHistDesc)]
         L.dfx_flow_hist_device.restype = i
+    if hasattr(L, "dfx_warp_planes_device"):  # a library built before the warp of planes (DFX_LIBRARY A/B) still loads
+        L.dfx_warp_planes_device.argtypes = [vp, C.POINTER(DfxWarpPlanesDesc)]
+        L.dfx_warp_planes_device.restype = i
     if hasattr(L, "dfx_splat_device"):  # a library built before the forward warp (DFX_LIBRARY A/B) still loads
         L.dfx_splat_device.argtypes = [vp, C.POINTER(DfxSplatDesc)]
         L.dfx_splat_device.restype = i
@@ -676,6 +711,8 @@ def _planar_dtype(dtype):
 
 WARP_U8 = 3                               # DFX_WARP_U8: the fourth out_dtype of dfx_warp_device
 WARP_BORDERS = {"zero": 0, "clamp": 1}    # DFX_WARP_BORDER_ZERO / DFX_WARP_BORDER_CLAMP
+WARP_SAMPLES = {"bilinear": 0, "nearest": 1}  # DFX_SAMPLE_BILINEAR / DFX_SAMPLE_NEAREST
+WARP_INVALIDS = {"zero": 0, "keep": 1}    # DFX_WARP_INVALID_ZERO / DFX_WARP_INVALID_KEEP
 
 
 GM_MODELS = {"translation": 0, "affine": 1}  # DFX_GM_TRANSLATION / DFX_GM_AFFINE
@@ -940,6 +977,38 @@ def _warp_border(border):
     if not isinstance(border, str) or border not in WARP_BORDERS:
         raise ValueError('border must be "zero" or "clamp"')
     return WARP_BORDERS[border]
+
+
+def _warp_planes_settings(sample, border, invalid):
+    """(sample, border, invalid) codes of dfx_warp_planes_device."""
+    if not isinstance(sample, str) or sample not in WARP_SAMPLES:
+        raise ValueError('sample must be "bilinear" or "nearest"')
+    if not isinstance(invalid, str) or invalid not in WARP_INVALIDS:
+        raise ValueError('invalid must be "zero" or "keep"')
+    return WARP_SAMPLES[sample], _warp_border(border), WARP_INVALIDS[invalid]
+
+
+def _warp_planes_np_dtypes(src, sample, dtype):
+    """(src code, out code, numpy dtype of the result) for a numpy source dtype.  Bilinear: float32, float16, or uint16 holding
+    bfloat16 bit patterns; dtype (None: the source's) is np.float32, np.float16 or "bfloat16".  Nearest: any 1-, 2- or 4-byte
+    integer or float type, copied as bit patterns; dtype must be None or the source's."""
+    src = np.dtype(src)
+    if sample:
+        if src.kind not in "iuf" or src.itemsize not in (1, 2, 4):
+            raise ValueError('planes must be a 1-, 2- or 4-byte integer or float array for sample="nearest"')
+        same = dtype is None or (src == np.uint16 if isinstance(dtype, str) and dtype == "bfloat16" else np.dtype(dtype) == src)
+        if not same:
+            raise ValueError('sample="nearest" copies elements: dtype must be None or the planes\' dtype')
+        code = {1: WARP_U8, 2: PLANAR_F16, 4: PLANAR_F32}[src.itemsize]
+        return code, code, src
+    codes = {np.dtype(np.float32): PLANAR_F32, np.dtype(np.float16): PLANAR_F16, np.dtype(np.uint16): PLANAR_BF16}
+    if src not in codes:
+        raise ValueError('planes must be float32, float16 or uint16 (bfloat16 bit patterns) for sample="bilinear" '
+                         '(integers take sample="nearest")')
+    if dtype is None:
+        return codes[src], codes[src], src
+    out_code, np_dt = _planar_dtype(dtype)
+    return codes[src], out_code, np_dt
 
 
 def _warp_layout(layout):
@@ -1830,6 +1899,166 @@ class FlowEngine:
                              stats.data_ptr() if want_stats else None)
         res = (out,) + ((valid,) if want_valid else ()) + ((stats,) if want_stats else ())
         return res if len(res) > 1 else out
+
+    # -- the backward warp of float, half and label planes by a flow (dfx_warp_planes_device) ----
+    def warp_planes_device(self, d_src_ptr: int, src_dtype: int, channels: int, layout: int, src_pitch: int,
+                           src_plane_stride: int, src_image_stride: int, d_flow_ptr: int, row_pitch_floats: int,
+                           plane_stride_floats: int, flow_stride_floats: int, n: int, border: int = 0, sample: int = 0,
+                           invalid: int = 0, out_dtype: int = PLANAR_F32, d_out_ptr: int | None = None, out_pitch: int = 0,
+                           out_plane_stride: int = 0, out_image_stride: int = 0, d_occ_ptr: int | None = None,
+                           occ_pitch: int = 0, occ_stride: int = 0, d_valid_ptr: int | None = None, valid_pitch: int = 0,
+                           valid_stride: int = 0):
+        """n sources of `channels` planes that are already in device memory, sampled at the positions n planar float32 flows
+        name: the fields of dfx_warp_planes_desc (include/dfx.h) as arguments, codes and raw pointers as the header gives
+        them."""
+        d = DfxWarpPlanesDesc(d_src_ptr, int(src_dtype), int(channels), int(layout), src_pitch, src_plane_stride,
+                              src_image_stride, d_flow_ptr, row_pitch_floats, plane_stride_floats, flow_stride_floats, int(n),
+                              int(border), int(sample), int(invalid), int(out_dtype), d_out_ptr, out_pitch, out_plane_stride,
+                              out_image_stride, d_occ_ptr, occ_pitch, occ_stride, d_valid_ptr, valid_pitch, valid_stride)
+        self._check(self._L.dfx_warp_planes_device(self._h, C.byref(d)))
+
+    def warp_planes(self, planes, flows, sample: str = "bilinear", border: str = "zero", invalid: str = "zero", dtype=None,
+                    layout: str = "chw", occ=None, return_valid: bool = False, out=None):
+        """Source i sampled at p + flows[i](p) (dfx_warp_planes_device): labels, a depth plane, a soft mask or a feature map
+        of frame 1 at the pixels of frame 0.
+
+        planes: (n, C, H, W), or with layout="hwc" (n, H, W, C).  sample "bilinear": float32, float16 or uint16 holding
+        bfloat16 bit patterns; the result is np.float32, np.float16 or "bfloat16" (np.uint16 bit patterns) as dtype says
+        (None: as the source).  sample "nearest": any 1-, 2- or 4-byte integer or float dtype, the element at the rounded
+        position (ties to even) copied as a bit pattern; the result has the source's dtype.  flows: (n, 2, H, W) float32.
+        border "zero" / "clamp" as warp.  occ: optional (n, H, W) uint8 occlusion masks (0 = visible).  invalid "zero": every
+        pixel is written, zero bits where the target leaves the frame; "keep": only the pixels whose target stays in the
+        frame (and is not occluded) are written and the others of `out` — required then, a contiguous array of the result's
+        shape and dtype — stay as they are (a background, an ignore index, an earlier warp).  return_valid: also return the
+        (n, H, W) uint8 mask of those pixels.  Returns out, or (out, valid)."""
+        smp, b, inv = _warp_planes_settings(sample, border, invalid)
+        l = _warp_layout(layout)
+        a = np.asarray(planes)
+        H, W = self.height, self.width
+        if a.ndim != 4 or (a.shape[2:] != (H, W) if l else a.shape[1:3] != (H, W)) or a.shape[1 if l else 3] < 1:
+            raise ValueError('planes must be (n, C, H, W) or, with layout="hwc", (n, H, W, C)')
+        src_code, out_code, np_dt = _warp_planes_np_dtypes(a.dtype, smp, dtype)
+        a = np.ascontiguousarray(a)
+        n, ch = a.shape[0], a.shape[1 if l else 3]
+        fl = self._warp_flows(flows, n)
+        occ = _np_planes(occ, n, H, W, np.uint8, "occ", "n")
+        if out is not None:
+            if not isinstance(out, np.ndarray) or out.dtype != np_dt or out.shape != a.shape or not out.flags.c_contiguous:
+                raise ValueError(f"out must be a contiguous {np_dt.name} array of the planes' shape")
+        elif inv:
+            raise ValueError('invalid="keep" needs out: the array whose other pixels are kept')
+        else:
+            out = np.empty(a.shape, np_dt)
+        valid = np.empty((n, H, W), np.uint8) if return_valid else None
+        if n:
+            pitch = W if l else W * ch
+            plane = H * W if l and ch > 1 else 0
+            image = ch * H * W
+            keep_in, fresh = (out, None) if inv else (None, out)  # a kept output goes up first and comes back by hand
+            with self._staged((a, fl, occ, keep_in), (fresh, valid)) as (d_src, d_fl, d_occ, d_keep, d_fresh, d_valid):
+                d_out = d_keep if inv else d_fresh
+                self.warp_planes_device(d_src, src_code, ch, l, pitch, plane, image, d_fl, W, H * W, 2 * H * W, n, b, smp, inv,
+                                        out_code, d_out, pitch, plane, image, d_occ, W, H * W, d_valid, W, H * W)
+                if inv:
+                    self._check(self._L.dfx_memcpy_d2h(self._h, out.ctypes.data, d_out, out.nbytes))
+        return (out, valid) if return_valid else out
+
+    def _planes_tensor_geometry(self, t, chw, what):
+        """A torch tensor of planes as the warp takes it, read from its shape — (n, C, H, W), or (n, H, W, C) where not chw —
+        and its strides: (channels, layout code of how it lies in MEMORY, row pitch, plane stride, image stride), in
+        elements.  Memory may be channels-last or channels-first under either shape (a permuted view is read where it lies)."""
+        H, W = self.height, self.width
+        if t.dim() != 4 or tuple(t.shape[2:] if chw else t.shape[1:3]) != (H, W) or t.shape[1 if chw else 3] < 1:
+            raise ValueError(f'{what} must be (n, C, H, W) or, with layout="hwc", (n, H, W, C)')
+        n, ch = t.shape[0], t.shape[1 if chw else 3]
+        st = t.stride()
+        sc, sy, sx = (st[1], st[2], st[3]) if chw else (st[3], st[1], st[2])  # strides of channel, row, pixel
+        if (sx == 1 or W == 1) and (ch == 1 or sc != 1 or (H == 1 and W == 1)):  # channels-first memory: C planes
+            pitch = sy if H > 1 else W
+            plane = sc if ch > 1 else H * pitch
+            image = st[0] if n > 1 else ch * plane
+            if pitch < W or plane < H * pitch or image < ch * plane:
+                raise ValueError(f"{what}: rows, planes and images must not overlap")
+            return ch, 1, pitch, (plane if ch > 1 else 0), image
+        if (sc == 1 or ch == 1) and (sx == ch or W == 1):  # channels-last memory: C elements per pixel
+            pitch = sy if H > 1 else ch * W
+            image = st[0] if n > 1 else H * pitch
+            if pitch < ch * W or image < H * pitch:
+                raise ValueError(f"{what}: rows and images must not overlap")
+            return ch, 0, pitch, 0, image
+        raise ValueError(f"{what}: pixels must be channels-last (channel stride 1, pixel stride C) or channels-first (pixel stride 1)")
+
+    def warp_planes_tensor(self, planes, flows, sample: str = "bilinear", border: str = "zero", invalid: str = "zero",
+                           dtype=None, layout: str = "chw", occ=None, return_valid: bool = False, out=None):
+        """warp_planes for torch tensors on this handle's device, read and written where they lie.
+
+        planes: (n, C, H, W), or with layout="hwc" (n, H, W, C); torch.float32, torch.float16 or torch.bfloat16, and for
+        sample="nearest" also torch.uint8, torch.int16 or torch.int32 (label maps, copied as bit patterns).  The memory
+        layout — channels-first or channels-last — and every stride are taken from the tensor, so a channels_last tensor,
+        the NCHW view of an NHWC batch or a slice of a larger tensor is read without a copy.  flows: (n, 2, H, W)
+        torch.float32 with a contiguous innermost dimension, e.g. what flow_tensor returns.  dtype: the result's, for
+        bilinear any of the three float types whatever the source is (None: the source's); for nearest the source's.  out:
+        optional tensor of that dtype and the planes' shape that lies in memory as the planes do, not `planes` itself;
+        required for invalid="keep", whose other pixels it keeps; otherwise the result is allocated in the planes' memory
+        layout and returned in the planes' shape.  occ: optional (n, H, W) uint8 masks (0 = visible).  return_valid: also
+        return the (n, H, W) uint8 tensor of the pixels whose target stays in the frame (and is not occluded).
+
+        Torch's current stream on that device is synchronised before the call; the call returns with its device work
+        complete.  Raises ValueError before the library is reached for a wrong setting, dtype, device, shape or stride."""
+        import torch
+
+        smp, b, inv = _warp_planes_settings(sample, border, invalid)
+        chw = _warp_layout(layout) == 1
+        codes = {torch.float32: PLANAR_F32, torch.float16: PLANAR_F16, torch.bfloat16: PLANAR_BF16}
+        if smp:
+            codes.update({torch.uint8: WARP_U8, torch.int16: PLANAR_F16, torch.int32: PLANAR_F32})
+        if not isinstance(planes, torch.Tensor) or planes.dtype not in codes:
+            raise ValueError("planes must be a torch.float32, torch.float16 or torch.bfloat16 tensor" +
+                             (", or torch.uint8, torch.int16 or torch.int32" if smp else
+                              ' (torch.uint8, torch.int16 and torch.int32 take sample="nearest")'))
+        tdt = planes.dtype if dtype is None else dtype
+        if smp and tdt != planes.dtype:
+            raise ValueError('sample="nearest" copies elements: dtype must be None or the planes\' dtype')
+        if tdt not in codes:
+            raise ValueError("dtype must be torch.float32, torch.float16 or torch.bfloat16")
+        H, W = self.height, self.width
+        ch, mem, pitch, plane, image = self._planes_tensor_geometry(planes, chw, "planes")
+        n, dev = planes.shape[0], planes.device
+        fgeom = _flow_geometry(flows, H, W, "flows", "n", n, ", one flow per image")
+        ogeom = (0, 0)
+        if occ is not None:
+            ogeom = _plane_geometry(occ, n, H, W, torch.uint8, "occ", "n")
+        if out is not None:
+            if not isinstance(out, torch.Tensor) or out.dtype != tdt or out.shape != planes.shape:
+                raise ValueError(f"out must be a {tdt} tensor of the planes' shape")
+            och, omem, out_pitch, out_plane, out_image = self._planes_tensor_geometry(out, chw, "out")
+            if omem != mem and ch > 1:
+                raise ValueError("out must lie in memory as the planes do (channels-last or channels-first)")
+            if omem != mem:  # one channel: the two layouts name the same memory
+                out_pitch, out_plane, out_image = (out_pitch, 0, out_image)
+            if out.data_ptr() == planes.data_ptr() and n:
+                raise ValueError("out must not be planes: a warp cannot run in place")
+        elif inv:
+            raise ValueError('invalid="keep" needs out: the tensor whose other pixels are kept')
+        self._check_devices(planes, "planes must be on this handle's device", (flows, occ, out),
+                            "flows, occ and out must be on the planes' device")
+        if out is None:
+            if mem == 0:  # channels-last memory, whatever the shape's order
+                base = torch.empty((n, H, W, ch), dtype=tdt, device=dev)
+                out = base.permute(0, 3, 1, 2) if chw else base
+                out_pitch, out_plane, out_image = ch * W, 0, ch * H * W
+            else:
+                base = torch.empty((n, ch, H, W), dtype=tdt, device=dev)
+                out = base if chw else base.permute(0, 2, 3, 1)
+                out_pitch, out_plane, out_image = W, (H * W if ch > 1 else 0), ch * H * W
+        valid = torch.empty((n, H, W), dtype=torch.uint8, device=dev) if return_valid else None
+        torch.cuda.current_stream(dev).synchronize()
+        if n:
+            self.warp_planes_device(planes.data_ptr(), codes[planes.dtype], ch, mem, pitch, plane, image, flows.data_ptr(),
+                                    *fgeom, n, b, smp, inv, codes[tdt], out.data_ptr(), out_pitch, out_plane, out_image,
+                                    occ.data_ptr() if occ is not None else None, ogeom[0], ogeom[1],
+                                    valid.data_ptr() if return_valid else None, W, H * W)
+        return (out, valid) if return_valid else out
 
     # -- the global (camera) motion of a flow: robust fit, removal, moving mask (dfx_global_motion_device) ----
     def global_motion_device(self, d_flow_ptr: int, row_pitch_floats: int, plane_stride_floats: int, flow_stride_floats: int,
