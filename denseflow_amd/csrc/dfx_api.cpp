@@ -579,6 +579,59 @@ template <class Desc>
 bool post_begin(dfx_handle h, const Desc *d, int *status) {
     return post_begin(h, d != nullptr, d ? d->n : 0, status);
 }
+
+// What dfx_flow_project_device and dfx_splat_device check alike (their descriptors name these fields alike), in three pieces
+// so that each call keeps the order of its refusals: the outputs and the parameters (scale: 0 from a call that has none);
+// the workspace, of per_item bytes an item (`sizer` names the call that gives them); the planes, with the call's own outputs
+// (out_bad: their strides do not span them) between occ and hole.  scatter_fill: the FsSource fields of either descriptor.
+template <class Desc>
+int scatter_check_params(dfx_handle h, const Desc *d, float scale) {
+    if (!d->d_out && !d->d_hole && !d->d_coverage)
+        return dfx_fail(h, DFX_ERR_INVALID, "one of d_out, d_hole and d_coverage is required");
+    if (!std::isfinite(d->t) || d->t == 0.0f)
+        return dfx_fail(h, DFX_ERR_INVALID, "t must be finite and nonzero");
+    if (!std::isfinite(scale))
+        return dfx_fail(h, DFX_ERR_INVALID, "scale must be finite");
+    if (!std::isfinite(d->min_weight) || !(d->min_weight >= 0.0f))
+        return dfx_fail(h, DFX_ERR_INVALID, "min_weight must be finite and >= 0");
+    return DFX_OK;
+}
+template <class Desc>
+int scatter_check_work(dfx_handle h, const Desc *d, size_t per_item, const char *sizer) {
+    if ((size_t)d->d_work % 8 != 0)
+        return dfx_fail(h, DFX_ERR_INVALID, "d_work must be 8-byte aligned");
+    if (d->work_bytes < per_item)
+        return dfx_fail(h, DFX_ERR_INVALID, std::string("work_bytes must be at least ") + sizer);
+    return DFX_OK;
+}
+template <class Desc>
+int scatter_check_planes(dfx_handle h, const Desc *d, bool out_bad, const char *out_text) {
+    if (planar_strides_bad(h, d->row_pitch_floats, d->plane_stride_floats, d->flow_stride_floats))
+        return dfx_fail(h, DFX_ERR_INVALID, kPlanarStrides);
+    if (int e = plane_check(h, d->d_importance != nullptr, d->importance_pitch_floats, d->importance_stride_floats, "importance",
+                            "importance", "_floats"))
+        return e;
+    if (int e = plane_check(h, d->d_occ != nullptr, d->occ_pitch, d->occ_stride, "mask", "occ"))
+        return e;
+    if (out_bad)
+        return dfx_fail(h, DFX_ERR_INVALID, out_text);
+    if (int e = plane_check(h, d->d_hole != nullptr, d->hole_pitch, d->hole_stride, "hole", "hole"))
+        return e;
+    return plane_check(h, d->d_coverage != nullptr, d->coverage_pitch_floats, d->coverage_stride_floats, "coverage", "coverage",
+                       "_floats");
+}
+template <class Desc>
+void scatter_fill(FsSource &a, dfx_handle h, const Desc *d) {
+    a.flow = d->d_flow, a.imp = d->d_importance, a.occ = d->d_occ, a.hole = d->d_hole, a.cov = d->d_coverage;
+    a.work = static_cast<unsigned long long *>(d->d_work);
+    a.n = d->n, a.w = h->W, a.h = h->H, a.t = d->t, a.wmin = fp_wmin(d->min_weight);
+    a.row_pitch = (long long)d->row_pitch_floats, a.plane_stride = (long long)d->plane_stride_floats;
+    a.flow_stride = (long long)d->flow_stride_floats;
+    a.imp_pitch = (long long)d->importance_pitch_floats, a.imp_stride = (long long)d->importance_stride_floats;
+    a.occ_pitch = (long long)d->occ_pitch, a.occ_stride = (long long)d->occ_stride;
+    a.hole_pitch = (long long)d->hole_pitch, a.hole_stride = (long long)d->hole_stride;
+    a.cov_pitch = (long long)d->coverage_pitch_floats, a.cov_stride = (long long)d->coverage_stride_floats;
+}
 }
 
 // ... and what it closes with: the launches' errors, the stream drained.
@@ -866,52 +919,22 @@ int dfx_flow_project_device(dfx_handle h, const dfx_project_desc *d) {
         return st;
     if (!d->d_flow || !d->d_work)
         return dfx_fail(h, DFX_ERR_INVALID, "NULL device flows or workspace");
-    if (!d->d_out && !d->d_hole && !d->d_coverage)
-        return dfx_fail(h, DFX_ERR_INVALID, "one of d_out, d_hole and d_coverage is required");
-    if (!std::isfinite(d->t) || d->t == 0.0f)
-        return dfx_fail(h, DFX_ERR_INVALID, "t must be finite and nonzero");
-    if (!std::isfinite(d->scale))
-        return dfx_fail(h, DFX_ERR_INVALID, "scale must be finite");
-    if (!std::isfinite(d->min_weight) || !(d->min_weight >= 0.0f))
-        return dfx_fail(h, DFX_ERR_INVALID, "min_weight must be finite and >= 0");
+    if (int e = scatter_check_params(h, d, d->scale))
+        return e;
     if (d->d_out == d->d_flow)
         return dfx_fail(h, DFX_ERR_INVALID, "a projection cannot run in place: d_out != d_flow is required");
-    if ((size_t)d->d_work % 8 != 0)
-        return dfx_fail(h, DFX_ERR_INVALID, "d_work must be 8-byte aligned");
     const size_t per_flow = dfx_flow_project_work_bytes(h);
-    if (d->work_bytes < per_flow)
-        return dfx_fail(h, DFX_ERR_INVALID, "work_bytes must be at least dfx_flow_project_work_bytes");
-    if (planar_strides_bad(h, d->row_pitch_floats, d->plane_stride_floats, d->flow_stride_floats))
-        return dfx_fail(h, DFX_ERR_INVALID, kPlanarStrides);
-    if (int e = plane_check(h, d->d_importance != nullptr, d->importance_pitch_floats, d->importance_stride_floats, "importance",
-                            "importance", "_floats"))
+    if (int e = scatter_check_work(h, d, per_flow, "dfx_flow_project_work_bytes"))
         return e;
-    if (int e = plane_check(h, d->d_occ != nullptr, d->occ_pitch, d->occ_stride, "mask", "occ"))
-        return e;
-    if (d->d_out && planar_strides_bad(h, d->out_row_pitch_floats, d->out_plane_stride_floats, d->out_flow_stride_floats))
-        return dfx_fail(h, DFX_ERR_INVALID, kPlanarStridesOut);
-    if (int e = plane_check(h, d->d_hole != nullptr, d->hole_pitch, d->hole_stride, "hole", "hole"))
-        return e;
-    if (int e = plane_check(h, d->d_coverage != nullptr, d->coverage_pitch_floats, d->coverage_stride_floats, "coverage", "coverage",
-                            "_floats"))
+    const bool out_bad = d->d_out && planar_strides_bad(h, d->out_row_pitch_floats, d->out_plane_stride_floats, d->out_flow_stride_floats);
+    if (int e = scatter_check_planes(h, d, out_bad, kPlanarStridesOut))
         return e;
     HIPCHK(h, hipSetDevice(h->device));
     FpArgs a{};
-    a.flow = d->d_flow, a.imp = d->d_importance, a.occ = d->d_occ;
-    a.out = d->d_out, a.hole = d->d_hole, a.cov = d->d_coverage;
-    a.work = static_cast<unsigned long long *>(d->d_work);
-    a.n = d->n, a.w = h->W, a.h = h->H;
-    a.t = d->t;
-    a.sc = (double)d->scale / 256.0;
-    a.wmin = fp_wmin(d->min_weight);
-    a.row_pitch = (long long)d->row_pitch_floats, a.plane_stride = (long long)d->plane_stride_floats;
-    a.flow_stride = (long long)d->flow_stride_floats;
-    a.imp_pitch = (long long)d->importance_pitch_floats, a.imp_stride = (long long)d->importance_stride_floats;
-    a.occ_pitch = (long long)d->occ_pitch, a.occ_stride = (long long)d->occ_stride;
+    scatter_fill(a, h, d);
+    a.out = d->d_out, a.sc = (double)d->scale / 256.0;
     a.out_pitch = (long long)d->out_row_pitch_floats, a.out_plane = (long long)d->out_plane_stride_floats;
     a.out_stride = (long long)d->out_flow_stride_floats;
-    a.hole_pitch = (long long)d->hole_pitch, a.hole_stride = (long long)d->hole_stride;
-    a.cov_pitch = (long long)d->coverage_pitch_floats, a.cov_stride = (long long)d->coverage_stride_floats;
     fp_launch(h->stream, a, (long long)(d->work_bytes / per_flow));
     return post_finish(h);
 }
@@ -1110,12 +1133,8 @@ int dfx_splat_device(dfx_handle h, const dfx_splat_desc *d) {
         return st;
     if (!d->d_src || !d->d_flow || !d->d_work)
         return dfx_fail(h, DFX_ERR_INVALID, "NULL device sources, flows or workspace");
-    if (!d->d_out && !d->d_hole && !d->d_coverage)
-        return dfx_fail(h, DFX_ERR_INVALID, "one of d_out, d_hole and d_coverage is required");
-    if (!std::isfinite(d->t) || d->t == 0.0f)
-        return dfx_fail(h, DFX_ERR_INVALID, "t must be finite and nonzero");
-    if (!std::isfinite(d->min_weight) || !(d->min_weight >= 0.0f))
-        return dfx_fail(h, DFX_ERR_INVALID, "min_weight must be finite and >= 0");
+    if (int e = scatter_check_params(h, d, 0.0f))
+        return e;
     if (d->src_dtype != DFX_WARP_U8 && d->src_dtype != DFX_PLANAR_F32)
         return dfx_fail(h, DFX_ERR_INVALID, "src_dtype must be DFX_WARP_U8 or DFX_PLANAR_F32");
     const bool f32 = d->src_dtype == DFX_PLANAR_F32;
@@ -1133,51 +1152,28 @@ int dfx_splat_device(dfx_handle h, const dfx_splat_desc *d) {
         return dfx_fail(h, DFX_ERR_INVALID, "out_dtype DFX_WARP_U8 needs an 8-bit source and DFX_SPLAT_MEAN");
     if (d->d_out == d->d_src)
         return dfx_fail(h, DFX_ERR_INVALID, "a splat cannot run in place: d_out != d_src is required");
-    if ((size_t)d->d_work % 8 != 0)
-        return dfx_fail(h, DFX_ERR_INVALID, "d_work must be 8-byte aligned");
     const size_t per_image = dfx_splat_work_bytes(h, d->channels);
-    if (d->work_bytes < per_image)
-        return dfx_fail(h, DFX_ERR_INVALID, "work_bytes must be at least dfx_splat_work_bytes");
+    if (int e = scatter_check_work(h, d, per_image, "dfx_splat_work_bytes"))
+        return e;
     const bool planes = d->channels > 1 && d->layout == DFX_SRC_PLANAR, il3 = d->channels == 3 && !planes;
     if (f32 ? splat_f32_strides_bad(h, d->channels, d->src_pitch, d->src_plane_stride, d->src_image_stride)
             : warp_image_strides_bad(h, il3, planes, d->src_pitch, d->src_plane_stride, d->src_image_stride))
         return dfx_fail(h, DFX_ERR_INVALID, "sources: a pitch or stride smaller than what it spans");
-    if (planar_strides_bad(h, d->row_pitch_floats, d->plane_stride_floats, d->flow_stride_floats))
-        return dfx_fail(h, DFX_ERR_INVALID, kPlanarStrides);
-    if (int e = plane_check(h, d->d_importance != nullptr, d->importance_pitch_floats, d->importance_stride_floats, "importance",
-                            "importance", "_floats"))
-        return e;
-    if (int e = plane_check(h, d->d_occ != nullptr, d->occ_pitch, d->occ_stride, "mask", "occ"))
-        return e;
-    if (d->d_out && (f32 ? splat_f32_strides_bad(h, d->channels, d->out_pitch, d->out_plane_stride, d->out_image_stride)
-                         : warp_image_strides_bad(h, il3, planes, d->out_pitch, d->out_plane_stride, d->out_image_stride)))
-        return dfx_fail(h, DFX_ERR_INVALID, "splatted images: a pitch or stride smaller than what it spans");
-    if (int e = plane_check(h, d->d_hole != nullptr, d->hole_pitch, d->hole_stride, "hole", "hole"))
-        return e;
-    if (int e = plane_check(h, d->d_coverage != nullptr, d->coverage_pitch_floats, d->coverage_stride_floats, "coverage", "coverage",
-                            "_floats"))
+    const bool out_bad = d->d_out && (f32 ? splat_f32_strides_bad(h, d->channels, d->out_pitch, d->out_plane_stride, d->out_image_stride)
+                                          : warp_image_strides_bad(h, il3, planes, d->out_pitch, d->out_plane_stride, d->out_image_stride));
+    if (int e = scatter_check_planes(h, d, out_bad, "splatted images: a pitch or stride smaller than what it spans"))
         return e;
     HIPCHK(h, hipSetDevice(h->device));
     SplatArgs a{};
-    a.src = d->d_src, a.flow = d->d_flow, a.imp = d->d_importance, a.occ = d->d_occ;
-    a.out = d->d_out, a.hole = d->d_hole, a.cov = d->d_coverage;
-    a.work = static_cast<unsigned long long *>(d->d_work);
-    a.n = d->n, a.w = h->W, a.h = h->H;
+    scatter_fill(a, h, d);
+    a.src = d->d_src, a.out = d->d_out;
     a.channels = d->channels, a.src_f32 = f32 ? 1 : 0, a.interleaved = il3 ? 1 : 0;
     a.out_u8 = d->out_dtype == DFX_WARP_U8 ? 1 : 0, a.sum = d->mode == DFX_SPLAT_SUM ? 1 : 0;
     a.keep = d->hole_mode == DFX_SPLAT_HOLE_KEEP ? 1 : 0;
-    a.t = d->t;
-    a.wmin = fp_wmin(d->min_weight);
     a.src_pitch = (long long)d->src_pitch, a.src_plane = (long long)d->src_plane_stride;
     a.src_image = (long long)d->src_image_stride;
-    a.row_pitch = (long long)d->row_pitch_floats, a.plane_stride = (long long)d->plane_stride_floats;
-    a.flow_stride = (long long)d->flow_stride_floats;
-    a.imp_pitch = (long long)d->importance_pitch_floats, a.imp_stride = (long long)d->importance_stride_floats;
-    a.occ_pitch = (long long)d->occ_pitch, a.occ_stride = (long long)d->occ_stride;
     a.out_pitch = (long long)d->out_pitch, a.out_plane = (long long)d->out_plane_stride;
     a.out_image = (long long)d->out_image_stride;
-    a.hole_pitch = (long long)d->hole_pitch, a.hole_stride = (long long)d->hole_stride;
-    a.cov_pitch = (long long)d->coverage_pitch_floats, a.cov_stride = (long long)d->coverage_stride_floats;
     splat_launch(h->stream, a, (long long)(d->work_bytes / per_image));
     return post_finish(h);
 }

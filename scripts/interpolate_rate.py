@@ -42,7 +42,7 @@ def parse_trace(directory, form, calls, pairs):
     files = glob.glob(os.path.join(directory, "**", "*_kernel_trace.csv"), recursive=True)
     if not files:
         raise SystemExit(f"no *_kernel_trace.csv under {directory}")
-    fam = {"k_fp_zero": [], "k_fp_scatter": [], "k_fp_normalise": [], "k_flow_median": [], "k_interp_synth": []}
+    fam = {"k_fs_zero": [], "k_fp_scatter": [], "k_fp_normalise": [], "k_flow_median": [], "k_interp_synth": []}
     for r in csv.DictReader(open(files[0])):
         for k in fam:
             if k in r["Kernel_Name"]:

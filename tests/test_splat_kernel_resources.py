@@ -1,5 +1,6 @@
-"""Register, scratch and LDS budgets of the forward-warp kernels (k_splat_zero, k_splat_scatter<channels, source form, lds
-window>, k_splat_normalise<channels, interleaved>; denseflow_amd/csrc/splat_kernels.hip), read from the built library's gfx950
+"""Register, scratch and LDS budgets of the forward-warp kernels (k_splat_scatter<channels, source form, lds window>,
+k_splat_normalise<channels, interleaved>; denseflow_amd/csrc/splat_kernels.hip) and of the zero pass they launch (k_fs_zero;
+denseflow_amd/csrc/flow_scatter.hip), read from the built library's gfx950
 code object with the method of tests/test_farneback_kernel_resources.py (no GPU needed): the instantiations are the seven
 scatter forms and the five normalising forms the launcher names, all of the shipped LDS-window form; none of the kernels has
 scratch; the scatter's window is 48 x 16 pixels of (1 + C) 64-bit words — 12 / 18 / 24 / 30 KiB, so at C = 4 five workgroups of
@@ -14,7 +15,7 @@ U8, U8_IL, F32 = 0, 1, 2  # the source forms of splat_kernels.hip: byte planes, 
 SCATTERS = [(1, U8), (3, U8_IL), (3, U8), (1, F32), (2, F32), (3, F32), (4, F32)]  # (channels, source form)
 NORMALISES = [(1, False), (2, False), (3, False), (4, False), (3, True)]            # (channels, interleaved)
 VGPR_BOUND = 64
-ZERO = "_ZN12_GLOBAL__N_112k_splat_zeroEPyx"
+ZERO = "_ZN12_GLOBAL__N_19k_fs_zeroEPyx"
 
 
 def _scatter(c, form, window=True):  # k_splat_scatter<c, form, window> in the anonymous namespace
@@ -27,7 +28,7 @@ def _normalise(c, il):  # k_splat_normalise<c, il>
 
 def test_the_instantiations_are_the_ones_the_launcher_names(kernels):  # noqa: F811
     want = [_scatter(*f) for f in SCATTERS] + [_normalise(*f) for f in NORMALISES] + [ZERO]
-    assert sorted(k for k in kernels if "k_splat_" in k) == sorted(want)
+    assert sorted(k for k in kernels if "k_splat_" in k or "k_fs_" in k) == sorted(want)
 
 
 @pytest.mark.parametrize("c,form", SCATTERS)
